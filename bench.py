@@ -8,8 +8,13 @@ stream: TemporalSampler.sample() (2 layers, fanout [10,10], most-recent, 1800 ro
 (edge + node cache ratio 0.2, 172-d features) — BASELINE.json configs[1].  Inputs
 (roots, timestamps, feature tables, graph) are resident in HBM before the timed region.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps (--dump-outputs DIR: then writes what the last
+timed step returned to its caller as DIR/<name>.npy) and prints the line.  Everything else the
+line can carry — the other legs, the CPU baseline, config 3, the all-to-all micro-measurement —
+runs only with --full.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment launches its own N
 ranks: the parent — before importing torch or touching HIP — starts N fresh children of this
@@ -20,17 +25,21 @@ The workload is the CHRONOLOGICAL REPLAY of the whole stream (1121 batches): ear
 batches sample almost nothing and late ones ~25k edges, and the LRU cache only behaves
 like the real thing when consecutive batches follow each other.  So the timed region is
 `repeats` back-to-back windows of K consecutive batches, starting at batch 0 on a freshly
-initialised cache and wrapping around at the end of the stream.  Unless --repeats says
-otherwise, `repeats` covers >= --min-replays (4) whole replays AND >= --min-seconds (2 s) of
-wall time — the step time comes from an untimed calibration replay, the maximum over the ranks —
-so whatever K is, edges_per_step is the full-replay mean and a clock outside the process sees
-the region.  ms_per_step = elapsed / (K * repeats); `timed_steps` = K * repeats and
-`timed_seconds` sit next to `steps` in the line.  The loop itself is
+initialised cache and wrapping around at the end of the stream.  `repeats` is 1 unless --repeats
+says otherwise: the timed region is then exactly K steps.  The W warm-up steps replay the last W
+batches of that window, its largest (the graph grows along the stream), so that the buffers have
+their size before the region starts.  --repeats 0 calibrates `repeats` instead to cover
+>= --min-replays (4) whole replays AND >= --min-seconds (2 s) of wall time — the step time comes
+from an untimed calibration replay, the maximum over the ranks —, so that edges_per_step is the
+full-replay mean whatever K is.  ms_per_step = elapsed / (K * repeats); `timed_steps` = K * repeats
+and `timed_seconds` sit next to `steps` in the line.  The loop itself is
 gnnflow_amd.pipeline.ReplayPipeline.run — the function tests/test_gpu_pipeline_parity.py
 checks against the oracle.
 
 Prints ONE JSON line (rank 0) with the contract fields plus
-  "roofline":     feature-gather kernel, algorithmic bytes / HIP-event time vs 8 TB/s
+  "roofline":     feature-gather kernel, algorithmic bytes / HIP-event time vs 8 TB/s, from
+                  events on every 61st gather launch of the timed region itself
+and, with --full only,
   "cpu_baseline": the CPU oracle (C port of the reference algorithm) timed on this
                   host on a bounded sample of the same batches (rank 0, N=1 only)
   "config3":      (N=1) BASELINE configs[2] — uniform sampling on the synthetic power-law graph
@@ -43,17 +52,18 @@ the roots travel to their owners and the sampled neighbours back as RCCL all-to-
 (gnnflow_amd.dist.DevicePartitionedSampler, slotted exchange: no host synchronisation
 inside a sample).  Feature tables (REDDIT-shaped: 463 MB) are replicated, the LRU cache is
 per GPU.  The per-GPU-replica figure (no data-path collective; what the reference does
-inside one machine) rides along as the extra key "replica"; `--partition replica` makes
+inside one machine) rides along as the extra key "replica" (--full); `--partition replica` makes
 it the main loop.  RCCL between ranks runs for the first time in the driver's scaling run, so
 an N > 1 run walks a LADDER (supervise(), RUNGS), each rung in fresh worker processes: the hash
 loop as above; should it FAIL or HANG (a collective some rank never joins: the worker's watchdog
 fires after GNNFLOW_HASH_MAIN_TIMEOUT seconds), the hash loop on ONE lane (one communicator) with
 shared chains; then on one lane with single chains and slot capacity 2.0; then the replica loop.
 The one line says which rung produced it and what happened before ("ladder").
-At N = 1 the main loop is the plain single-GPU path; the hash path rides along twice: "hash_partition"
+At N = 1 the main loop is the plain single-GPU path; with --full the hash path rides along twice: "hash_partition"
 (every root is the rank's own, no exchange) and "hash_partition_over_rccl_one_rank" (the chain an
 N > 1 run issues — slotted exchange, lanes, up to four samples per chain — with every message
-going through RCCL to the rank itself).
+going through RCCL to the rank itself), beside the other feature placements ("sample_only",
+"cache_free_device", "pinned_placement").
 """
 import argparse
 import json
@@ -70,8 +80,10 @@ PMC_TRAFFIC_FILE = "r06_pmc_gather_traffic.json"
 
 
 def workload_key(args):
-    """What a committed PMC traffic measurement must have been taken with to be quoted (the
-    per-launch traffic of the gather does not depend on how often the replay is repeated)."""
+    """What a committed PMC traffic measurement must have been taken with to be quoted.  The
+    committed measurements cover whole replays, so they are quoted only for a calibrated timed
+    region (--repeats 0); over whole replays the per-launch traffic of the gather does not
+    depend on how often the replay is repeated."""
     return {"steps": args.steps, "warmup": args.warmup,
             "batch_size": args.batch_size, "fanouts": args.fanouts, "strategy": args.strategy,
             "cache_ratio": args.cache_ratio, "undirected": bool(args.undirected),
@@ -85,9 +97,15 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1121)   # one full chronological replay
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=0,
+    ap.add_argument("--repeats", type=int, default=1,
                     help="windows of --steps consecutive batches in the timed region "
                          "(0 = enough for --min-replays whole replays and --min-seconds)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the other legs, the CPU baseline, config 3 and the "
+                         "all-to-all micro-measurement (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what its last step returned to the "
+                         "caller (sampled blocks, gathered features) as DIR/<name>.npy")
     ap.add_argument("--min-replays", type=float, default=4.0)
     ap.add_argument("--min-seconds", type=float, default=2.0,
                     help="lower bound of the timed region's wall time (an outside clock and "
@@ -430,9 +448,13 @@ def time_leg(ctx, sampler, cache, main_leg, min_seconds, min_replays, probe=None
         dist.all_reduce(t, op=op)
         return float(t)
 
-    pipe.run(0, args.warmup if main_leg else min(args.warmup, nb))
     steps = args.steps if main_leg else nb
     repeats = args.repeats if (main_leg and args.repeats > 0) else 0
+    if repeats:
+        # the last batches of the timed window, its largest: the buffers grow to their size here
+        pipe.run(max(min(steps, nb) - args.warmup, 0), args.warmup)
+    else:
+        pipe.run(0, args.warmup if main_leg else min(args.warmup, nb))
     if repeats == 0:
         # calibration: the mean step time of a whole replay (15 % on top: the timed region
         # must not end up just short of --min-seconds)
@@ -467,12 +489,15 @@ def time_leg(ctx, sampler, cache, main_leg, min_seconds, min_replays, probe=None
         ctx.lib.gf_profile_enable((1 << ctx.capi.PROFILE_SLOTS["gather"]) |
                                   (1 << ctx.capi.PROFILE_SLOTS["lru"]))
     probe0 = probe() if probe else None     # (may synchronise: outside the timed region)
-    acc = {"edges": 0}
+    acc = {"edges": 0, "steps": 0, "last": None}
 
     def account(_i, mfgs):
         for mfg in mfgs:
             for b in mfg:
                 acc["edges"] += b.num_edges()
+        acc["steps"] += 1
+        if acc["steps"] == timed_steps:
+            acc["last"] = mfgs          # what the last step returned (--dump-outputs)
 
     ctx.barrier()
     t0 = time.perf_counter()
@@ -489,7 +514,57 @@ def time_leg(ctx, sampler, cache, main_leg, min_seconds, min_replays, probe=None
         elapsed_max, edges_all = elapsed, float(acc["edges"])
     return dict(elapsed=elapsed_max, edges_all=edges_all, edges=acc["edges"], steps=steps,
                 repeats=repeats, timed_steps=timed_steps, pipe=pipe, probe0=probe0,
-                probe1=probe() if probe else None)
+                probe1=probe() if probe else None, last_mfgs=acc["last"])
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, mfgs, cache):
+    """What the caller of the timed path received in its last step, as float32 / float64 .npy
+    files: per layer l and block b the sampled block (src node ids and timestamps, edge ids and
+    delta timestamps, edges as (col, row) = (src index, dst index)), the gathered features
+    (srcdata['h'] / edata['f'] of the blocks the fetch gave them to) and the target edge
+    features.  Ids are exact in float64.  If all files together would exceed 64 MB, every array
+    is cut to a fixed, seeded sample of its rows; the sampled row indices are written as
+    <name>.rows.npy next to it."""
+    import numpy as np
+    arrays = {}
+
+    def put(name, t, dtype):
+        arrays[name] = t.detach().cpu().numpy().astype(dtype, copy=False)
+    for l, mfg in enumerate(mfgs):
+        for b, blk in enumerate(mfg):
+            p = "l{}_b{}_".format(l, b)
+            put(p + "src_ID", blk.srcdata["ID"], np.float64)
+            put(p + "src_ts", blk.srcdata["ts"], np.float32)
+            put(p + "edge_ID", blk.edata["ID"], np.float64)
+            put(p + "edge_dt", blk.edata["dt"], np.float32)
+            col, row = blk.edges()
+            put(p + "edge_col", col, np.float64)
+            put(p + "edge_row", row, np.float64)
+            if "h" in blk.srcdata:
+                put(p + "src_h", blk.srcdata["h"], np.float32)
+            if "f" in blk.edata:
+                put(p + "edge_f", blk.edata["f"], np.float32)
+    if cache is not None and cache.target_edge_features is not None:
+        put("target_edge_features", cache.target_edge_features, np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        # the same fraction of every array's rows; with their float64 row indices (at most twice
+        # the bytes of a float32 column) the files take at most 3/4 of the limit
+        keep = DUMP_LIMIT_BYTES / (4.0 * total)
+        rng = np.random.RandomState(0)
+        for k in [k for k, a in arrays.items() if len(a)]:
+            a = arrays[k]
+            rows = np.sort(rng.choice(len(a), max(int(len(a) * keep), 1), replace=False))
+            arrays[k] = a[rows]
+            arrays[k + ".rows"] = rows.astype(np.float64)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT_BYTES
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {"dir": out_dir, "files": len(arrays), "bytes": int(sum(a.nbytes for a in arrays.values()))}
 
 
 def agree(ctx, ok):
@@ -925,6 +1000,11 @@ def main():
             main.done.set()
         os._exit(1)
     sampler, pipe = res["sampler"], res["pipe"]
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # now, before any other leg reuses the sampler's output buffers or the cache
+        dumped = dump_outputs(args.dump_outputs, res["last_mfgs"], cache)
+    res["last_mfgs"] = None
     elapsed_max, edges_all, edges = res["elapsed"], res["edges_all"], res["edges"]
     repeats, timed_steps = res["repeats"], res["timed_steps"]
     pipelined = pipe.pipelined
@@ -996,6 +1076,8 @@ def main():
             "host_logical_cpus": os.cpu_count(),
         },
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if cache is not None and g_n.value:
         # dominant kernel by bytes: the fused feature gather (one launch per fetch round):
         # algorithmic bytes per launch (all launches) / average duration of the launches
@@ -1027,7 +1109,7 @@ def main():
         if os.path.exists(pmc):
             with open(pmc) as f:
                 rec = json.load(f)
-            if rec.get("bench_args") == workload_key(args):
+            if args.repeats == 0 and rec.get("bench_args") == workload_key(args):
                 out["roofline"]["traffic_from_profile"] = rec["hbm_traffic_bytes_per_dispatch"]
                 out["roofline"]["traffic_source"] = "profiles/" + PMC_TRAFFIC_FILE
         out["cache_edge_ratio"] = float(cache.cache_edge_ratio)
@@ -1130,13 +1212,13 @@ def main():
         out["multi_gpu"] = multi_gpu_record(ctx, sampler, cache)
     # (before the hash legs: their lanes, clones and communicators create streams, and which
     # hardware queue a stream lands on depends on how many the process created before it)
-    if rank == 0 and world == 1 and main_kind == "replica" and cache is not None \
+    if args.full and rank == 0 and world == 1 and main_kind == "replica" and cache is not None \
             and not args.no_placement_legs and not sharded:
         placement_legs(ctx, out, res["sampler"], node_feats, edge_feats)
     if history and main_kind == "replica":
         out["hash_partition"] = {"error": history[0]["error"], "ladder": history,
                                  "fallback": "replica loop timed instead"}
-    elif cache is not None and not args.no_second_leg:
+    elif args.full and cache is not None and not args.no_second_leg:
         # The other kind of graph in the same line, over the same batches, cache and pipeline:
         # the hash-partitioned one when the main loop ran on replicas (at P = 1 every root is
         # the rank's own: the figure then prices the bucketing / fixed-slot / merge kernels
@@ -1155,7 +1237,7 @@ def main():
             # itself: what the multi-rank path costs before any real peer exists
             out["hash_partition_over_rccl_one_rank"] = second_leg(ctx, "hash", cache,
                                                                   always_exchange=True)
-    if main_kind == "hash" and world > 1 and "multi_gpu" in out:
+    if args.full and main_kind == "hash" and world > 1 and "multi_gpu" in out:
         # last of all, and guarded: a collective micro-measurement on the lanes' communicators
         guarded_aux(ctx, out, "all_to_all_measurement", 45.0,
                     lambda: all_to_all_record(ctx, sampler, out["multi_gpu"]))
@@ -1173,9 +1255,9 @@ def main():
             bd[name] = {"total_ms": ms.value, "intervals": int(n.value)}
         out["kernel_breakdown_200_steps"] = bd
 
-    if rank == 0 and world == 1 and not args.no_config3:
+    if args.full and rank == 0 and world == 1 and not args.no_config3:
         out["config3"] = config3_leg(args, dev)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(g, batches[:min(timed_steps, nb)], fanouts, args,
                                            edge_feats.cpu().numpy(), node_feats.cpu().numpy(),
                                            cache is not None)
@@ -1312,7 +1394,8 @@ def placement_legs(ctx, out, sampler, node_feats, edge_feats):
         import subprocess
         cmd = [sys.executable, os.path.abspath(__file__), "--feature-placement", "pinned",
                "--no-config3", "--no-hash-leg", "--no-cpu-baseline", "--no-placement-legs",
-               "--min-seconds", str(secs), "--steps", str(ctx.nb), "--warmup", str(args.warmup),
+               "--min-seconds", str(secs), "--steps", str(ctx.nb), "--repeats", "0",
+               "--warmup", str(args.warmup),
                "--batch-size", str(args.batch_size), "--fanouts", args.fanouts,
                "--strategy", args.strategy, "--cache-ratio", str(args.cache_ratio)]
         env = dict(os.environ)

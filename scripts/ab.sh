@@ -8,7 +8,7 @@ OUT=gpurun_out/ab_$TAG; mkdir -p $OUT
 for i in $(seq 1 $PAIRS); do
   for side in A B; do
     if [ $side = A ]; then E="$A"; else E="$B"; fi
-    env $E python bench.py --no-hash-leg --no-config3 --no-cpu-baseline "$@" > $OUT/${side}_$i.json 2> $OUT/${side}_$i.err || exit 1
+    env $E python bench.py --repeats 0 --no-hash-leg --no-config3 --no-cpu-baseline "$@" > $OUT/${side}_$i.json 2> $OUT/${side}_$i.err || exit 1
     python - "$OUT/${side}_$i.json" "$side" "$E" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -14,7 +14,7 @@ export TMPDIR=/tmp
 O=gpurun_out/$R; mkdir -p $O /tmp/prof gpurun_out/prof gpurun_out/pmc
 for s in $STEPS; do case $s in
 bench) timeout -k 10 500 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_$TAG.json 2> $O/bench_$TAG.err; echo "bench rc=$?"; cut -c1-300 $O/bench_$TAG.json;;
-trace) timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -o ${R}_$TAG -- python3 bench.py --no-hash-leg --no-config3 --no-cpu-baseline --no-placement-legs --steps 20 --warmup 5 > gpurun_out/prof/${R}_${TAG}_bench.log 2>&1; echo "trace rc=$?"
+trace) timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/../prof -o ${R}_$TAG -- python3 bench.py --repeats 0 --no-hash-leg --no-config3 --no-cpu-baseline --no-placement-legs --steps 20 --warmup 5 > $O/../prof/${R}_${TAG}_bench.log 2>&1; echo "trace rc=$?"
    python3 scripts/step_timeline.py ${R}_$TAG 20 4000 --summary $O/prof_${TAG}_step_timeline.txt > $O/prof_${TAG}_step_timeline.csv; cat $O/prof_${TAG}_step_timeline.txt
    cp gpurun_out/prof/${R}_${TAG}_kernel_stats.csv $O/prof_${TAG}_kernel_stats_replica_only.csv; rm -f gpurun_out/prof/${R}_${TAG}_kernel_trace.csv;;
 pmc) timeout -k 10 400 bash scripts/rocprof_pmc.sh ${R}_$TAG > $O/pmc_${TAG}.log 2>&1; echo "pmc rc=$?"; tail -2 $O/pmc_${TAG}.log; rm -f gpurun_out/pmc/*_counter_collection.csv gpurun_out/pmc/*_agent_info.csv;;

@@ -8,7 +8,7 @@ set -o pipefail
 out=gpurun_out/r03_part_bench.jsonl
 : > $out
 run() { echo "# $*" >&2; "$@" 2>>gpurun_out/r03_part_bench.err | grep '^{' >> $out || echo '{"error": "'"$*"'"}' >> $out; }
-C="--no-cpu-baseline --no-second-leg --steps 1121 --warmup 20"
+C="--repeats 0 --no-cpu-baseline --no-second-leg --steps 1121 --warmup 20"
 run python bench.py $C
 run python bench.py $C --partition hash
 run python bench.py $C --partition hash --always-exchange

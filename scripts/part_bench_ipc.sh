@@ -7,7 +7,7 @@ set -o pipefail
 out=gpurun_out/r03_part_bench_ipc.jsonl
 : > $out
 run() { echo "# $*" >&2; "$@" 2>>gpurun_out/r03_part_bench_ipc.err | grep '^{' >> $out || echo '{"error": "'"$*"'"}' >> $out; }
-C="--no-cpu-baseline --no-second-leg --steps 1121 --warmup 20 --min-replays 2"
+C="--repeats 0 --no-cpu-baseline --no-second-leg --steps 1121 --warmup 20 --min-replays 2"
 export GNNFLOW_BENCH_DEVICE=0 GNNFLOW_BENCH_BACKEND=gloo GNNFLOW_PART_TRANSPORT=ipc
 run python bench.py $C --partition hash
 for n in 2 4; do

@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 TAG=${1:-r06}
 mkdir -p /tmp/prof gpurun_out/$TAG
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o pin -- python3 bench.py --no-cpu-baseline --no-config3 --no-hash-leg --no-placement-legs --feature-placement pinned --steps 20 --warmup 5 > /tmp/prof/pin.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $TMPDIR/prof -o pin -- python3 bench.py --repeats 0 --no-cpu-baseline --no-config3 --no-hash-leg --no-placement-legs --feature-placement pinned --steps 20 --warmup 5 > $TMPDIR/prof/pin.log 2>&1
 grep "^{" /tmp/prof/pin.log | tail -1 > gpurun_out/$TAG/pinned_bench_profiled.json
 cp /tmp/prof/pin_kernel_stats.csv gpurun_out/$TAG/pinned_kernel_stats.csv
 python3 scripts/kernel_stats_summary.py gpurun_out/$TAG/pinned_kernel_stats.csv --top 8

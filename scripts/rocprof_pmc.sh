@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 TAG=${1:-r1}
 shift
-ARGS="${*:---steps 20 --warmup 5}"
+ARGS="--repeats 0 ${*:---steps 20 --warmup 5}"
 mkdir -p gpurun_out/pmc
 for C in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $C --output-format csv -d gpurun_out/pmc -o ${TAG}_$C -- python3 bench.py --no-cpu-baseline --no-hash-leg --no-config3 --no-placement-legs --min-seconds 0.2 $ARGS > gpurun_out/pmc/${TAG}_$C.log 2>&1

@@ -192,6 +192,9 @@ def _sampler_worker(rank, world, port, ret):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     os.environ["LOCAL_RANK"] = str(rank)
+    # the draw stays on the host even where a GPU is visible: LOCAL_RANK 1 would name a second
+    # GPU, which a one-GPU machine does not have
+    D._local_device = lambda: torch.device("cpu")
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
         torch.manual_seed(100 + rank)       # rank 0's draw must win on every rank

@@ -1,5 +1,6 @@
 """bench.py's output contract on a real GPU: one JSON line from rank 0 with the fields the
-driver reads, the roofline / cpu_baseline / config3 objects, a 2-rank launch through torchrun
+driver reads, a plain run that times exactly --steps steps and dumps its last step's outputs,
+the roofline / cpu_baseline / config3 objects of --full, a 2-rank launch through torchrun
 and the same through bench.py's own launcher (`python bench.py --gpus 2`, the shape of the
 driver's command; both ranks on the one GPU of the test box, gloo carries the bookkeeping
 collectives), and the fall-back to the replica loop when the hash-partitioned one fails."""
@@ -41,8 +42,9 @@ def _check_common(d, n_gpus, steps, warmup):
 
 
 def test_single_gpu_line_with_roofline_and_cpu_baseline():
-    d = _run([sys.executable, "bench.py", "--steps", "60", "--warmup", "5", "--cpu-seconds", "1",
-              "--min-seconds", "0.1", "--config3-nodes", "200000", "--config3-edges", "4000000",
+    d = _run([sys.executable, "bench.py", "--full", "--repeats", "0", "--steps", "60",
+              "--warmup", "5", "--cpu-seconds", "1", "--min-seconds", "0.1",
+              "--config3-nodes", "200000", "--config3-edges", "4000000",
               "--config3-batches", "600,6000"])
     _check_common(d, 1, 60, 5)
     r = d["roofline"]
@@ -110,16 +112,48 @@ def test_single_gpu_line_with_roofline_and_cpu_baseline():
         assert 0 < row["search_frac"] < 1 and 0 < row["emit_frac"] < 1
 
 
-def test_driver_command_line_is_representative():
-    """`--steps 20 --warmup 5` (what the driver runs): full-replay mean edges per step, and a
-    timed region an outside clock can see (>= 2 s)."""
-    d = _run([sys.executable, "bench.py", "--steps", "20", "--warmup", "5", "--no-cpu-baseline",
-              "--no-config3"])
+def test_plain_run_times_exactly_its_steps_and_dumps_its_outputs(tmp_path):
+    """`--gpus 1 --steps K --warmup W`: the timed region is K steps, nothing beyond the headline
+    and its roofline runs, and --dump-outputs writes the last step's blocks and features — the
+    same arrays from run to run."""
+    dirs = [str(tmp_path / "a"), str(tmp_path / "b")]
+    lines = [_run([sys.executable, "bench.py", "--gpus", "1", "--steps", "1121", "--warmup", "5",
+                   "--dump-outputs", o]) for o in dirs]
+    d = lines[0]
+    _check_common(d, 1, 1121, 5)
+    assert d["repeats"] == 1 and d["timed_steps"] == 1121 == d["config"]["timed_steps"]
+    assert d["ms_per_step"] == pytest.approx(1e3 * d["timed_seconds"] / 1121)
+    assert d["roofline"]["launches_timed"] > 0
+    for k in ("cpu_baseline", "config3", "hash_partition", "hash_partition_over_rccl_one_rank",
+              "sample_only", "cache_free_device", "pinned_placement"):
+        assert k not in d, k
+    import numpy as np
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1])) and d["dumped_outputs"]["files"] == len(names)
+    assert {"l0_b0_src_ID.npy", "l0_b0_src_h.npy", "l1_b0_edge_f.npy",
+            "target_edge_features.npy"} <= set(names)
+    total = 0
+    for n in names:
+        a, b = (np.load(os.path.join(x, n)) for x in dirs)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+        total += a.nbytes
+    assert 0 < total <= 64 << 20
+    # the stream's last batch (its remainder: 672447 edges = 1120 x 600 + 447), 172-d; one
+    # feature row per sampled edge
+    assert np.load(os.path.join(dirs[0], "target_edge_features.npy")).shape == (447, 172)
+    assert len(np.load(os.path.join(dirs[0], "l1_b0_edge_ID.npy"))) == \
+        len(np.load(os.path.join(dirs[0], "l1_b0_edge_f.npy"))) > 0
+
+
+def test_calibrated_region_is_representative():
+    """`--steps 20 --warmup 5 --repeats 0`: full-replay mean edges per step, and a timed region
+    an outside clock can see (>= 2 s)."""
+    d = _run([sys.executable, "bench.py", "--steps", "20", "--warmup", "5", "--repeats", "0"])
     _check_common(d, 1, 20, 5)
     assert d["repeats"] >= 225 and d["timed_seconds"] >= 1.9
     assert d["roofline"].get("traffic_source", "").startswith("profiles/") or \
         "traffic_from_profile" not in d["roofline"]
-    full = _run([sys.executable, "bench.py", "--no-cpu-baseline", "--no-config3",
+    full = _run([sys.executable, "bench.py", "--repeats", "0",
                  "--min-seconds", "0.05"])      # (four replays take ~0.1 s)
     assert full["repeats"] == 4
     assert d["config"]["edges_per_step"] == pytest.approx(full["config"]["edges_per_step"],
@@ -128,8 +162,9 @@ def test_driver_command_line_is_representative():
 
 def test_two_ranks_through_torchrun():
     d = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-              "--master-addr", "127.0.0.1", "--master-port", "29533", "bench.py", "--gpus", "2",
-              "--steps", "40", "--warmup", "5", "--min-replays", "1"],
+              "--master-addr", "127.0.0.1", "--master-port", "29533", "bench.py", "--full",
+              "--gpus", "2", "--steps", "40", "--warmup", "5", "--repeats", "0",
+              "--min-replays", "1"],
              env={"GNNFLOW_BENCH_DEVICE": "0", "GNNFLOW_BENCH_BACKEND": "gloo"})
     _check_common(d, 2, 40, 5)
     # N > 1: the headline is north_star's split — the graph hash-partitioned over the ranks,
@@ -144,8 +179,8 @@ def test_two_ranks_through_torchrun():
 def test_bench_launches_its_own_ranks():
     """`python bench.py --gpus 2 --steps 20 --warmup 5` — no torchrun, no WORLD_SIZE: the parent
     starts the ranks itself (before touching HIP) and relays rank 0's one line."""
-    d = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "20", "--warmup", "5",
-              "--min-replays", "1", "--min-seconds", "0.2"],
+    d = _run([sys.executable, "bench.py", "--full", "--gpus", "2", "--steps", "20", "--warmup", "5",
+              "--repeats", "0", "--min-replays", "1", "--min-seconds", "0.2"],
              env={"GNNFLOW_BENCH_DEVICE": "0", "GNNFLOW_BENCH_BACKEND": "gloo"})
     _check_common(d, 2, 20, 5)
     assert d["config"]["parallelism"] == "hash-dp2"
@@ -167,7 +202,7 @@ def test_failing_hash_loop_falls_back_to_the_replica_figure():
     """The hash-partitioned loop raising on every rank (on all three hash rungs of the ladder) must
     not cost the line: fresh ranks time the replica loop and the record says so."""
     d = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "20", "--warmup", "5",
-              "--min-replays", "1", "--min-seconds", "0.2"],
+              "--repeats", "0", "--min-replays", "1", "--min-seconds", "0.2"],
              env={"GNNFLOW_BENCH_DEVICE": "0", "GNNFLOW_BENCH_BACKEND": "gloo",
                   "GNNFLOW_BENCH_FAIL_HASH": "1"})
     _check_common(d, 2, 20, 5)
@@ -194,8 +229,8 @@ def test_hanging_hash_loop_walks_down_the_ladder(who, rungs, final):
            # shared box may need (the whole suite has taken 1.8 x its usual time on one)
            "GNNFLOW_HASH_MAIN_TIMEOUT": {"0": "15,150", "0,1": "15,15,150"}.get(rungs, "15"),
            "GNNFLOW_PART_TRANSPORT": "ipc"}
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "20", "--warmup", "5",
-           "--min-replays", "1", "--min-seconds", "0.2"]
+    cmd = [sys.executable, "bench.py", "--full", "--gpus", "2", "--steps", "20", "--warmup", "5",
+           "--repeats", "0", "--min-replays", "1", "--min-seconds", "0.2"]
     if who == "all":        # the driver's torchrun form: the agent's store must not be reused
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                "--master-addr", "127.0.0.1", "--master-port", "29577"] + cmd[1:]
@@ -239,7 +274,7 @@ def test_four_ranks_sharing_the_gpu_finish_the_hash_loop():
     recount fall-back this run ended in "a look-back granule did not arrive" and the bench fell
     back to the replica loop)."""
     d = _run([sys.executable, "bench.py", "--gpus", "4", "--steps", "20", "--warmup", "5",
-              "--min-replays", "1", "--min-seconds", "0.2", "--no-second-leg"],
+              "--repeats", "0", "--min-replays", "1", "--min-seconds", "0.2", "--no-second-leg"],
              env={"GNNFLOW_BENCH_DEVICE": "0", "GNNFLOW_BENCH_BACKEND": "gloo",
                   "GNNFLOW_PART_TRANSPORT": "ipc"})
     _check_common(d, 4, 20, 5)
@@ -252,7 +287,7 @@ def test_two_ranks_native_chains_over_the_ipc_transport():
     issued by the enqueue thread) with every message real — carried by the library's hipIpc
     transport instead of RCCL, which refuses ranks that share a GPU."""
     d = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "20", "--warmup", "5",
-              "--min-replays", "1", "--min-seconds", "0.2", "--no-second-leg"],
+              "--repeats", "0", "--min-replays", "1", "--min-seconds", "0.2", "--no-second-leg"],
              env={"GNNFLOW_BENCH_DEVICE": "0", "GNNFLOW_BENCH_BACKEND": "gloo",
                   "GNNFLOW_PART_TRANSPORT": "ipc"})
     _check_common(d, 2, 20, 5)
