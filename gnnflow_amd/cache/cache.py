@@ -25,7 +25,9 @@ _DESC = struct.Struct("iiQQQQ")     # struct gf_fetch_desc: kind, update, d_ids,
 _current_device = getattr(torch._C, "_cuda_getDevice", None) or torch.cuda.current_device
 
 # asynchronous fetch_feature() submissions that may be with the enqueue thread at a time
-_MAX_QUEUED = max(1, int(os.environ.get("GNNFLOW_FETCH_QUEUED", "4")))
+_MAX_QUEUED = 4
+# pipeline.side_stream index of the staging ring's pull stream
+_PULL_STREAM_K = 3
 assert _DESC.size == C.sizeof(_capi.GfFetchDesc)
 
 
@@ -190,8 +192,8 @@ class Cache:
         self._prefetch_stream = None
         self._prefetch_handle = None
         # serve an edge block that is a prefix of the previously fetched one from that
-        # block's rows (LRU only; fetch_feature); GNNFLOW_PREFIX_ALIAS=0 turns it off
-        self.prefix_alias = os.environ.get('GNNFLOW_PREFIX_ALIAS', '1') != '0'
+        # block's rows (LRU only; fetch_feature)
+        self.prefix_alias = True
 
         self._lib = _capi.load()
         self._node = self._edge = None
@@ -420,7 +422,7 @@ class Cache:
         st = self._prefetch_handle
         if st is None:
             from ..pipeline import side_stream
-            self._prefetch_stream = side_stream(self.device, int(os.environ.get('GNNFLOW_PREFETCH_STREAM_K', '3')))
+            self._prefetch_stream = side_stream(self.device, _PULL_STREAM_K)
             st = self._prefetch_handle = C.c_void_p(self._prefetch_stream.cuda_stream)
         # (no record_stream: the blocks stay alive until their own fetch, which is issued after
         # the pull that reads their ids has been)
@@ -545,7 +547,7 @@ class Cache:
             stream = self._prefetch_stream
             if stream is None:
                 from ..pipeline import side_stream
-                stream = self._prefetch_stream = side_stream(dev, int(os.environ.get('GNNFLOW_PREFETCH_STREAM_K', '3')))
+                stream = self._prefetch_stream = side_stream(dev, _PULL_STREAM_K)
         for mfg in mfgs:
             for b in mfg:
                 if hasattr(b, "record_stream"):

@@ -137,7 +137,6 @@ class DeviceBuffer {
 // (8.6 -> 17 GB) and needs old + new at once.  Small buffers stay on hipMalloc: with the pools
 // of the 21 MB REDDIT-shaped graph mapped this way the hash-partitioned replay ran at 76 us
 // per step instead of 52 (unexplained; sampling on the multi-GB graphs is unaffected).
-// GNNFLOW_VMM_POOLS=0: always reallocate.
 class GrowBuffer {
  public:
   static constexpr size_t kInPlaceBytes = size_t(1) << 30;
@@ -164,7 +163,7 @@ class GrowBuffer {
   void reserve(size_t n, size_t keep, hipStream_t stream) {
     if (!vmm_) {
       if (n <= fallback_.bytes()) return;
-      if (n < in_place_bytes() || !start_in_place()) {
+      if (n < kInPlaceBytes || !start_in_place()) {
         fallback_.reserve(n, keep, stream);
         return;
       }
@@ -198,20 +197,8 @@ class GrowBuffer {
   }
 
  private:
-  static size_t in_place_bytes() {
-    static const size_t v = [] {
-      const char* e = std::getenv("GNNFLOW_VMM_MIN_BYTES");   // experiments / tests
-      return e ? static_cast<size_t>(std::atoll(e)) : kInPlaceBytes;
-    }();
-    return v;
-  }
-
   bool start_in_place() {
-    static const bool enabled = [] {
-      const char* v = std::getenv("GNNFLOW_VMM_POOLS");
-      return !(v && std::atoi(v) == 0);
-    }();
-    if (!enabled || max_bytes_ < in_place_bytes()) return false;
+    if (max_bytes_ < kInPlaceBytes) return false;
     va_ = align_up(max_bytes_, kPiece);
     void* base = nullptr;
     if (hipMemAddressReserve(&base, va_, kPiece, nullptr, 0) != hipSuccess) {

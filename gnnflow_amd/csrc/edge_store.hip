@@ -196,25 +196,14 @@ GraphView EdgeStore::view() const {
   v.ts_pool = ts_pool_.as<float>();
   v.nbr_pool = nbr_pool_.as<EdgePair>();
   v.fence = fence_view_;
-  static const bool shortcut = [] {
-    const char* e = std::getenv("GNNFLOW_SEARCH_LAST_TS");   // tests / A-B runs: 0 = always search
-    return !(e && std::atoi(e) == 0);
-  }();
-  // -1: the newest-edge shortcut is off altogether
-  v.nonneg_ts = !shortcut ? -1 : (negative_ts_.load(std::memory_order_relaxed) ? 0 : 1);
+  v.nonneg_ts = negative_ts_.load(std::memory_order_relaxed) ? 0 : 1;
   return v;
 }
 
 // (Re)allocates the fence levels for a pool of `cap` elements and fills them from the first
 // `live` elements of ts_pool_.  Called when the pools grow: rare, and one strided pass.
 void EdgeStore::rebuild_fences(uint64_t cap, uint64_t live) {
-  static const bool enabled = [] {
-    const char* v = std::getenv("GNNFLOW_SEARCH_FENCES");   // tests / A-B runs: 0 = plain search
-    return !(v && std::atoi(v) == 0);
-  }();
-  fences_enabled_ = enabled;
   FenceView f{nullptr, {0}, 0};
-  if (!enabled) { fence_view_ = f; return; }
   uint64_t total = 0;
   for (uint32_t l = 0; l < kFenceMaxLevels; ++l) {
     const uint64_t n = cap >> (4 * (l + 1));

@@ -82,7 +82,7 @@ struct GraphView {
   uint64_t table_len;
   const float* ts_pool;
   const EdgePair* nbr_pool;
-  FenceView fence;   // fence.levels == 0: no fences (GNNFLOW_SEARCH_FENCES=0)
+  FenceView fence;   // fence.levels == 0: no fences (small layers, or a pool under 16 elements)
   int nonneg_ts;     // no negative timestamp was ever ingested: a window that starts at 0 starts
                      // at the node's first edge (no search for the lower end either)
 };
@@ -276,7 +276,6 @@ class EdgeStore {
   DeviceBuffer fence_;              // every 16^l-th timestamp of ts_pool_ (FenceView)
   DeviceBuffer fence_prev_;         // the previous generation (samples enqueued before a growth)
   FenceView fence_view_{nullptr, {0}, 0};
-  bool fences_enabled_ = true;
   std::atomic<bool> negative_ts_{false};   // an edge with a negative timestamp was ingested
   void rebuild_fences(uint64_t cap, uint64_t live);
   bool pools_ready_ = false;

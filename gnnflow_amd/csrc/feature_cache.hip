@@ -2664,11 +2664,6 @@ inline void set_odd4(Ctx& c, size_t dim, bool allowed) {
   c.odd4 = 0;
   c.tail = 0;
   if (c.vec4 || !allowed || dim < 8) return;
-  static const bool enabled = [] {
-    const char* v = std::getenv("GNNFLOW_GATHER_ODD_VEC4");   // tuning / tests; 0 = scalar rows
-    return !(v && std::atoi(v) == 0);
-  }();
-  if (!enabled) return;
   c.odd4 = 1;
   c.dimv = static_cast<uint32_t>((dim + 3) / 4);   // the last vector overlaps its neighbour
   c.tail = static_cast<uint32_t>(dim % 4);
@@ -2694,17 +2689,6 @@ inline size_t queue_min_capacity() {
 // chunks of kRowTile queue entries the victim walk covers behind the head: twice the rows
 // of the block (at most that many victims are needed) + 2
 inline size_t victim_chunks(size_t n) { return (2 * n + kRowTile - 1) / kRowTile + 2; }
-
-// list form: blocks that need more list tiles than this for their victims fall back to the
-// one-workgroup walk (kMaxStageTiles: the install kernel keeps the tile prefix in LDS)
-inline size_t max_stage_tiles() {
-  static const size_t v = [] {
-    const char* e = std::getenv("GNNFLOW_LRU_STAGE_TILES_MAX");   // tuning / tests; 0: always walk
-    const size_t x = e ? static_cast<size_t>(std::atoll(e)) : kMaxStageTiles;
-    return std::min<size_t>(x, kMaxStageTiles);
-  }();
-  return v;
-}
 
 // entries of the victim staging arrays: list form — the tiles at the front of the list (at most
 // the whole list, at most kMaxStageTiles); queue form — the chunks behind the head
@@ -2734,11 +2718,6 @@ inline size_t qbits_bytes(size_t queue_cap) {
 // rows per wave: 64 for big blocks; fewer for small ones so the block still spreads
 // over >= 1024 waves (4 per CU)
 inline uint32_t pick_tile_rows(size_t n) {
-  static const int forced = [] {
-    const char* v = std::getenv("GNNFLOW_GATHER_TILE_ROWS");   // tuning / tests
-    return v ? std::atoi(v) : 0;
-  }();
-  if (forced >= 1 && forced <= 64) return static_cast<uint32_t>(forced);
   // measured on the batch-600 blocks (10k-30k rows): 16 rows per wave beats both 4 (more,
   // shorter waves: 17.8 us/launch) and 32 (16.7 us) at 13.8 us; aim for >= 1024 waves, but
   // never below 16 rows — a 16-row tile of 172-d rows is one trip of 11 loads per lane, and
@@ -2749,13 +2728,7 @@ inline uint32_t pick_tile_rows(size_t n) {
   return t;
 }
 
-inline uint32_t pick_inflight() {
-  static const int v = [] {
-    const char* e = std::getenv("GNNFLOW_GATHER_INFLIGHT");   // tuning / tests
-    return e ? std::atoi(e) : 12;   // a 16-row tile of 172-d rows = 11 loads per lane: one trip
-  }();
-  return static_cast<uint32_t>(v);
-}
+constexpr uint32_t kGatherInflight = 12;   // a 16-row tile of 172-d rows = 11 loads per lane: one trip
 
 inline unsigned gather_grid_for(size_t n, uint32_t tile_rows) {
   const size_t waves = (n + tile_rows - 1) / tile_rows;
@@ -2779,11 +2752,6 @@ inline RoundFork& round_fork() {
   return f;
 }
 inline bool fork_round(hipStream_t stream, hipStream_t* side) {
-  static const bool enabled = [] {
-    const char* v = std::getenv("GNNFLOW_LRU_FORK");   // tuning / tests; 0: one stream
-    return !(v && std::atoi(v) == 0);
-  }();
-  if (!enabled) return false;
   RoundFork& f = round_fork();
   int dev = 0;
   GF_HIP(hipGetDevice(&dev));
@@ -2824,7 +2792,7 @@ void launch_round(Round& r, hipStream_t stream) {
     bool lean = true, staged = false, direct = true;
     for (int i = 0; i < r.count; ++i) {
       const Ctx& c = r.c[i];
-      lean = lean && c.vec4 && !c.qmode && c.inflight >= 12;
+      lean = lean && c.vec4 && !c.qmode;
       staged = staged || c.pmap != nullptr;
       direct = direct && !c.cache_buf && !c.miss_rows && !c.remap && !c.pmap;
     }
@@ -2833,10 +2801,6 @@ void launch_round(Round& r, hipStream_t stream) {
       // robin, and the launch ends with the CUs that received a third one (~2.3 us per further
       // workgroup: profiles/r06_gather_hop_trace.txt).  If slightly larger tiles — still one trip
       // of loads — bring the round down to 512 workgroups, take them.
-      static const bool fit = [] {
-        const char* v = std::getenv("GNNFLOW_GATHER_FIT_CUS");   // A/B
-        return !(v && std::atoi(v) == 0);
-      }();
       auto wgs = [&](uint32_t t) {
         size_t total = 0;
         for (int i = 0; i < r.count; ++i) total += ((r.c[i].n + t - 1) / t + 3) / 4;
@@ -2851,7 +2815,7 @@ void launch_round(Round& r, hipStream_t stream) {
         dimv = std::max(dimv, r.c[i].dimv);
       }
       const uint32_t t_max = std::min<uint32_t>(64u, 13u * 64u / dimv);
-      if (fit && same && t0 == 16 && wgs(t0) > 512 && t_max > t0) {
+      if (same && t0 == 16 && wgs(t0) > 512 && t_max > t0) {
         uint32_t t = t0 + 1;
         while (t < t_max && wgs(t) > 512) ++t;
         if (wgs(t) <= 512) {
@@ -3003,7 +2967,7 @@ Ctx plain_ctx(const float* feats, size_t num_rows, size_t dim, const int64_t* id
   c.dimv = static_cast<uint32_t>(c.vec4 ? dim / 4 : dim);
   set_odd4(c, dim, true);
   c.tile_rows = pick_tile_rows(n);
-  c.inflight = pick_inflight();
+  c.inflight = kGatherInflight;
   c.out = out;
   c.feats = feats;
   c.num_ids = num_rows;
@@ -3181,14 +3145,6 @@ void FeatureCache::staging_state(uint64_t out[9]) {
   }
 }
 
-static inline bool stage_risk_enabled() {
-  static const bool on = [] {
-    const char* v = std::getenv("GNNFLOW_STAGE_AT_RISK");   // tuning / tests; 0: absent ids only
-    return !(v && std::atoi(v) == 0);
-  }();
-  return on;
-}
-
 // The window of generations a launch may read when `issued` is the newest one: region g & mask
 // is rewritten by generation g + G, and up to kStageAhead newer generations may be pulled while
 // the launch runs.
@@ -3283,7 +3239,7 @@ bool FeatureCache::stage_begin(void* stage_ctx_out, const int64_t* d_ids, size_t
   // (only a cache that kStageAhead blocks of this size can turn over: for a larger one the
   // entries at the front of the order are rarely among a block's hits, and the rule pulled 370
   // rows per step for the headline's edge cache — 134 k slots, 9.5 k-row blocks — to save 4)
-  if (c.map && policy_ == GF_CACHE_LRU && stage_risk_enabled() &&
+  if (c.map && policy_ == GF_CACHE_LRU &&
       capacity_ <= size_t{kStageAhead} * n) {
     c.qpos = qpos_.as<uint32_t>();
     c.qstate = queue_form_ ? qstate_.as<QueueState>() : nullptr;
@@ -3660,7 +3616,7 @@ void FeatureCache::prepare(const int64_t* d_ids, size_t n, float* d_out, bool up
   c.inst_from_table = table_on_device_ ? 1 : 0;
   set_odd4(c, dim_, policy_ == GF_CACHE_LRU || !update || capacity_ == 0);
   c.tile_rows = pick_tile_rows(n);
-  c.inflight = pick_inflight();
+  c.inflight = kGatherInflight;
   c.out = d_out;
   c.feats = feats_;
   c.num_ids = num_ids_;
@@ -3697,12 +3653,10 @@ void FeatureCache::prepare(const int64_t* d_ids, size_t n, float* d_out, bool up
       // list form: the tiles at the front of the list that stage their entries
       const size_t list_tiles = (capacity_ + kRowTile - 1) / kRowTile;
       const size_t st = std::min(list_tiles, (2 * n + kRowTile - 1) / kRowTile + 2);
-      c.stage_tiles = st <= max_stage_tiles() ? static_cast<uint32_t>(st) : 0u;
-      static const uint32_t stage_min = [] {
-        const char* e = std::getenv("GNNFLOW_LRU_STAGE_MIN_WANT");   // tuning / tests
-        return e ? static_cast<uint32_t>(std::atoll(e)) : kStageMinWant;
-      }();
-      c.stage_min = stage_min;
+      // more tiles than kMaxStageTiles (the install kernel keeps the tile prefix in LDS): the
+      // one-workgroup walk
+      c.stage_tiles = st <= kMaxStageTiles ? static_cast<uint32_t>(st) : 0u;
+      c.stage_min = kStageMinWant;
       c.stage_hits = st == list_tiles ? 1 : 0;
     }
     c.qpos = qpos_.as<uint32_t>();
@@ -3739,11 +3693,7 @@ void FeatureCache::prepare(const int64_t* d_ids, size_t n, float* d_out, bool up
     // enough for every count and row workgroup to be resident from the start (1 024-thread
     // workgroups: one per CU; with 256 rows the headline's row workgroups entered 2.6 us into the
     // launch, behind the count workgroups — profiles/r06_lru_hop_trace.txt).
-    static const bool wide_rows = [] {
-      const char* v = std::getenv("GNNFLOW_LRU_FUSE_WIDE_ROWS");   // A/B
-      return !(v && std::atoi(v) == 0);
-    }();
-    c.fuse_rows = (n > size_t{kInstRows} * kFuseMaxRowWgs || (wide_rows && !mirror_)) ? kWide : kInstRows;
+    c.fuse_rows = (n > size_t{kInstRows} * kFuseMaxRowWgs || !mirror_) ? kWide : kInstRows;
     if (!c.qmode && lru_fused_enabled() &&
         (capacity_ + kFuseTile - 1) / kFuseTile <= kFuseMaxTiles &&
         (n + c.fuse_rows - 1) / c.fuse_rows <= kFuseMaxRowWgs) {
@@ -3953,11 +3903,7 @@ bool prefetch_blocks(FeatureCache* node, FeatureCache* edge, const gf_fetch_desc
     }
     // 8 rows per wave, 4 waves per workgroup; the kernel reads the rows really claimed
     // (grid-stride: 64 workgroups = 256 waves; 192 stretched the GDELT-scale gathers beside the pull from 254 to 578 us)
-    static const size_t max_wgs = [] {
-      const char* v = std::getenv("GNNFLOW_STAGE_PULL_WGS");   // tuning
-      return v ? static_cast<size_t>(std::max(1, std::atoi(v))) : size_t{64};
-    }();
-    const unsigned grid = static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>((most + 31) / 32, max_wgs)));
+    const unsigned grid = static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>((most + 31) / 32, 64)));
     stage_pull_kernel<<<dim3(grid, jobs.count), dim3(256), 0, stream>>>(jobs);
     GF_HIP(hipGetLastError());
   }

@@ -53,10 +53,7 @@ constexpr int kScanThreads = 1024;
 constexpr int kScanItems = 4;  // per thread per tile
 constexpr size_t kSmallRoots = 32768;  // layers up to this many roots skip the scan launch
 constexpr uint32_t kGranuleSpins = 1u << 12;   // ~ a few ms of polling before a tile is recounted
-static size_t kLaneSearchRoots = [] {   // layers from this many roots: lane-per-root pass
-  const char* v = std::getenv("GNNFLOW_LANE_SEARCH_MIN_ROOTS");   // tuning
-  return v ? static_cast<size_t>(std::atoll(v)) : (size_t{1} << 20);
-}();
+constexpr size_t kLaneSearchRoots = size_t{1} << 20;   // layers from this many roots: lane-per-root pass
 constexpr uint32_t kMaxHubSegs = 2048;         // = the lane pass's largest grid
 
 // sampling_kernels.cu:28-40
@@ -120,7 +117,7 @@ __device__ inline uint32_t lower_bound_fenced(const GraphView& g, uint64_t s, ui
                                               int lane, int group_in_wave) {
   constexpr int V = 16 / GROUP;   // consecutive values per lane: the group covers 16 per round
   uint64_t lo = s, hi = s + n;    // the answer lies in [lo, hi]
-  if (g.fence.levels == 0)   // small layers (view_for), or fences switched off
+  if (g.fence.levels == 0)   // small layers (view_for), or a pool too small for fences
     return lower_bound_group<GROUP>(g.ts_pool + s, n, x, lane, group_in_wave);
   if (n > 16) {
     int top = (31 - __clz(n - 1)) >> 2;   // coarsest level with 16^top < n
@@ -194,7 +191,7 @@ __device__ inline void window_bounds(const GraphView& g, const NodeEntry& e, flo
                                      int lane, int group_in_wave, uint32_t* lo_out,
                                      uint32_t* hi_out) {
   uint32_t hi;
-  if (g.nonneg_ts >= 0 && end > __uint_as_float(e.last_ts_bits)) hi = e.size;
+  if (end > __uint_as_float(e.last_ts_bits)) hi = e.size;
   else hi = lower_bound_fenced<GROUP>(g, e.start, e.size, end, lane, group_in_wave);
   uint32_t lo = 0;
   if (!(g.nonneg_ts > 0 && start <= 0.0f) && hi > 0) {
@@ -584,7 +581,7 @@ __global__ __launch_bounds__(kEmitThreads) void sample_emit_kernel(
     const uint32_t* __restrict__ rec_cnt, const uint32_t* __restrict__ base,
     int64_t* __restrict__ all_nodes, float* __restrict__ all_ts, float* __restrict__ dt,
     int64_t* __restrict__ eids, int64_t* __restrict__ row, int64_t* __restrict__ col,
-    Publish pub, int unroll) {
+    Publish pub) {
   const uint64_t R = d_R ? *d_R : R_host;
   const uint64_t total = R * fanout;
   if (pub.num_words && blockIdx.x == 0 && threadIdx.x == 0) {   // sizes: final before this launch
@@ -595,11 +592,11 @@ __global__ __launch_bounds__(kEmitThreads) void sample_emit_kernel(
   // sampled edge is ONE random 32-byte record, and what bounds this kernel at large batches is
   // how many of those reads are in flight (HBM's random-access rate), not bytes.  One slot per
   // trip left each wave with a single record read outstanding between two dependent hops
-  // (count / end -> record -> stores); GNNFLOW_EMIT_UNROLL=1 is that form.
+  // (count / end -> record -> stores).
   const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
   const uint64_t first = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   constexpr int K = 4;
-  for (uint64_t t0 = first; t0 < total; t0 += (unroll ? K : 1) * stride) {
+  for (uint64_t t0 = first; t0 < total; t0 += K * stride) {
     uint64_t t[K], r[K], end[K];
     uint32_t j[K], n[K], bs[K];
     float rts[K];
@@ -607,7 +604,7 @@ __global__ __launch_bounds__(kEmitThreads) void sample_emit_kernel(
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       t[k] = t0 + static_cast<uint64_t>(k) * stride;
-      in[k] = (k == 0 || unroll) && t[k] < total;
+      in[k] = t[k] < total;
       r[k] = in[k] ? t[k] / fanout : 0;
       j[k] = static_cast<uint32_t>(t[k] - r[k] * fanout);
     }
@@ -1584,9 +1581,7 @@ Sampler::Sampler(EdgeStore* graph, const uint32_t* fanouts, size_t num_layers, i
   search_group_ = group_width_from_env("GNNFLOW_SEARCH_GROUP", 16);
   large_group_ = group_width_from_env("GNNFLOW_SEARCH_GROUP_LARGE", 4);
   {
-    const char* v = std::getenv("GNNFLOW_SAMPLER_FUSED_SCAN");
-    fused_scan_ = !(v && std::atoi(v) == 0);
-    v = std::getenv("GNNFLOW_SAMPLER_HYBRID_SEARCH");   // tests / A-B runs
+    const char* v = std::getenv("GNNFLOW_SAMPLER_HYBRID_SEARCH");   // tests
     hybrid_search_ = !(v && std::atoi(v) == 0);
   }
   DeviceGuard dg(graph_->device());
@@ -1683,7 +1678,7 @@ void Sampler::enqueue_layer(const int64_t* d_roots, const float* d_ts, size_t Rb
   // prefix + emit in ONE launch through look-back granules was built and measured: 17 us per
   // layer against 6.5 + 6 us + a 1.5 us boundary — across XCDs a count reaches its readers
   // through memory, which a kernel boundary does for free; profiles/README, round 5.)
-  const bool small = fused_scan_ && Rb <= kSmallRoots;
+  const bool small = Rb <= kSmallRoots;
   const unsigned roots_per_wg = kSearchThreads / search_group_;
   {
     ProfileScope ps(kProfSearch, stream);
@@ -1755,14 +1750,9 @@ void Sampler::enqueue_layer(const int64_t* d_roots, const float* d_ts, size_t Rb
   {
     ProfileScope ps(kProfEmit, stream);
     unsigned grid = capped_grid(static_cast<uint64_t>(Rb) * F, kEmitThreads, 256 * 16);
-    static const int unroll = [] {
-      const char* v = std::getenv("GNNFLOW_EMIT_UNROLL");   // A/B runs: 1 = one slot per trip
-      return (v && std::atoi(v) == 1) ? 0 : 1;
-    }();
     sample_emit_kernel<<<dim3(grid), dim3(kEmitThreads), 0, stream>>>(
         gv, d_roots, d_ts, d_R, R_host, F, uniform, prop_time_ ? 1 : 0, seed_, call, rec_end,
-        rec_cnt, base, out.all_nodes, out.all_ts, out.dt, out.eids, out.row, out.col, pub,
-        unroll);
+        rec_cnt, base, out.all_nodes, out.all_ts, out.dt, out.eids, out.row, out.col, pub);
     GF_HIP(hipGetLastError());
   }
 }
@@ -1824,12 +1814,8 @@ void Sampler::sample_begin(const int64_t* d_roots, const float* d_ts, size_t R, 
   // No publish kernel: the sample's LAST kernel copies the sizes to pinned memory and the host
   // polls the stream's event for completion — one launch less per sample on the sampling
   // stream (round 4, seven same-box pairs: 32.6-32.8 us per step against 33.0-33.7, and none of
-  // the occasional 36-37 us runs; GNNFLOW_PUBLISH_EVENT=0: the publish kernel and its flag)
-  static const bool by_event = [] {
-    const char* v = std::getenv("GNNFLOW_PUBLISH_EVENT");
-    return !(v && std::atoi(v) == 0);
-  }();
-  slot->by_event = by_event;
+  // the occasional 36-37 us runs against a publish kernel and its flag)
+  slot->by_event = true;
   for (size_t l = 0; l < L; ++l) {
     const size_t Rb = root_bound(R, l);
     for (size_t s = 0; s < NS; ++s) {
@@ -1837,7 +1823,7 @@ void Sampler::sample_begin(const int64_t* d_roots, const float* d_ts, size_t R, 
       uint64_t* cslot = d_counts + 2 * b;
       // the next layer of the same snapshot reads its root count R + S from next_R
       uint64_t* next_R = (l + 1 < L) ? cslot + 2 * NS : nullptr;
-      const void* last = (by_event && b + 1 == L * NS) ? &pub : nullptr;
+      const void* last = (b + 1 == L * NS) ? &pub : nullptr;
       if (l == 0) {
         enqueue_layer(d_roots, d_ts, Rb, nullptr, R, l, s, ptrs[b], cslot, next_R, stream, last);
       } else {
@@ -1846,10 +1832,6 @@ void Sampler::sample_begin(const int64_t* d_roots, const float* d_ts, size_t R, 
                       stream, last);
       }
     }
-  }
-  if (!by_event) {
-    sample_publish_kernel<<<dim3(1), dim3(64), 0, stream>>>(pub);
-    GF_HIP(hipGetLastError());
   }
   GF_HIP(hipEventRecord(slot->done, stream));
   std::lock_guard<std::mutex> lk(ring_mu_);
@@ -2174,18 +2156,13 @@ uint32_t* Sampler::part_root_of() const {
 }
 // Layers that take the fused merge get their own share's counts from the sampling kernel.
 bool Sampler::part_own_counts(size_t root_bound) const {
-  return fused_scan_ && root_bound <= kSmallRoots && root_bound > 0;
+  return root_bound <= kSmallRoots && root_bound > 0;
 }
 
 // Slotted form, layers of <= kSmallRoots roots: the merge is ONE launch (merge_slots_fused_kernel);
-// neither the per-root counts nor root_of[] are needed then.  GNNFLOW_PART_FUSED_MERGE=0: the
-// count + emit pair.
+// neither the per-root counts nor root_of[] are needed then.  Other layers: the count + emit pair.
 bool Sampler::part_fused_merge(size_t root_bound, uint32_t fanout) const {
-  static const bool on = [] {
-    const char* v = std::getenv("GNNFLOW_PART_FUSED_MERGE");
-    return !(v && std::atoi(v) == 0);
-  }();
-  return on && part_.slack > 0.0 && part_own_counts(root_bound) && fanout <= kEmitThreads &&
+  return part_.slack > 0.0 && part_own_counts(root_bound) && fanout <= kEmitThreads &&
          (root_bound * fanout + kEmitThreads - 1) / kEmitThreads <= ws_roots_;
 }
 
@@ -2614,7 +2591,7 @@ size_t Sampler::group_ws_bytes(const Sampler& a, const size_t* R, int m, int wor
 }
 
 bool Sampler::group_ok(const size_t* R, int m) const {
-  if (num_snapshots_ != 1 || m < 1 || m > kMaxGroup || !fused_scan_) return false;
+  if (num_snapshots_ != 1 || m < 1 || m > kMaxGroup) return false;
   for (size_t l = 0; l < fanouts_.size(); ++l) {
     if (fanouts_[l] > kEmitThreads) return false;
     for (int j = 0; j < m; ++j) {
@@ -2785,12 +2762,9 @@ void Sampler::sample_partitioned_group(const GroupSample* gs, int m, void* d_ws,
       // 2 lanes per root from 4 096 roots on (batch 600, 4 samples per chain, one rank over
       // RCCL: 56.7 us per step with 16 lanes, 50.7 with 4, 46.8 with 2, 43.8 with 2 also for
       // the 7 200-root first layer; profiles/README.md round 4)
-      static const int chain_width = group_width_from_env("GNNFLOW_PART_CHAIN_WIDTH", 2);
-      static const size_t chain_small = [] {
-        const char* v = std::getenv("GNNFLOW_PART_CHAIN_SMALL");
-        return v ? static_cast<size_t>(std::atol(v)) : size_t{4096};
-      }();
-      const int width = static_cast<size_t>(m) * bound > chain_small ? chain_width : a.search_group_;
+      constexpr int kChainWidth = 2;
+      constexpr size_t kChainSmall = 4096;
+      const int width = static_cast<size_t>(m) * bound > kChainSmall ? kChainWidth : a.search_group_;
       const unsigned grid = capped_grid(n_max, kSearchThreads / width, 256 * 8);
       const PaddedCommon pc{0, 1, a.window_, F, a.policy_ == GF_SAMPLING_POLICY_UNIFORM ? 1 : 0,
                             a.prop_time_ ? 1 : 0, a.seed_, narrow ? 1 : 0};

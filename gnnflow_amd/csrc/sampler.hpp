@@ -159,7 +159,6 @@ class Sampler {
  private:
   int search_group_ = 16;   // lanes per root, layers of <= 32 768 roots
   int large_group_ = 4;     // lanes per root, larger layers (sampler.hip: group_width_from_env)
-  bool fused_scan_ = true;
   bool hybrid_search_ = true;   // large layers: lane-per-root search, groups for the hubs
   // begun, not yet ended samples (FIFO).  begin() may run on the library's enqueue thread
   // while end() runs on the caller's: the ring bookkeeping is under ring_mu_.

@@ -578,7 +578,7 @@ class DevicePartitionedSampler:
     owns, see PartitionedGraph)."""
 
     def __init__(self, sampler, group=None, always_exchange=False, slack=None, slot_roots=None,
-                 comm=None, overlap=None, lanes=None, pair=None, chain_samples=None,
+                 comm=None, overlap=None, lanes=None, chain_samples=None,
                  narrow_ids=None, adapt_slack=None, edge_fill=None, reuse_roots=None):
         """always_exchange: take the multi-rank path — request / reply exchange, served
         requests, merge — even with one rank (where every message is empty).  For tests: it
@@ -621,7 +621,6 @@ class DevicePartitionedSampler:
         until the chain is full or one of them is waited for (then the chain goes out with
         those held so far).  Default GNNFLOW_PART_CHAIN or 4; needs the library's communicator,
         one snapshot and layers of <= 32 768 roots (else single chains).
-        pair: False = chain_samples 1 (the earlier name of the switch; GNNFLOW_PART_PAIR=0).
         narrow_ids: shared chains carry 12-byte reply slots {destination, edge id, edge time}
         instead of 24-byte ones — half the bytes of the reply exchange — which needs every node
         and edge id of every rank's shard in [0, 2^32 - 2].  It is part of the wire format: the
@@ -692,11 +691,9 @@ class DevicePartitionedSampler:
         if comms and comms[0].transport in ("ipc", "loopback"):
             lanes = min(lanes, len(comms))    # host-synchronising transports: as many as given
         lanes = max(1, min(int(lanes), 4))
-        if pair is None:
-            pair = os.environ.get("GNNFLOW_PART_PAIR", "1") != "0"
         if chain_samples is None:
             chain_samples = int(os.environ.get("GNNFLOW_PART_CHAIN", "4"))
-        chain = max(1, min(int(chain_samples), _capi.GF_PART_GROUP_MAX)) if pair else 1
+        chain = max(1, min(int(chain_samples), _capi.GF_PART_GROUP_MAX))
         if not (self._slack > 0 and self._S == 1):
             chain = 1
         # one rank and nothing to exchange: the shared chain without its all-to-alls (the
@@ -723,8 +720,7 @@ class DevicePartitionedSampler:
         # reference ships back a partition's sampled edges, not fanout records per root,
         # gnnflow/distributed/dist_sampler.py:244-314) — rung "hash-simple" of bench.py's ladder
         groupable = self._slack > 0 and self._S == 1
-        self._chain_of_one = (chain == 1 and groupable and
-                              os.environ.get("GNNFLOW_PART_SINGLE_COMPACT", "1") != "0")
+        self._chain_of_one = chain == 1 and groupable
         self._set_edge_fill(max(0.0, min(float(edge_fill), 1.0))
                             if (chain > 1 or self._chain_of_one) else 0.0)
         self._chain_of_one = self._chain_of_one and self._edge_fill > 0.0
@@ -854,14 +850,9 @@ class DevicePartitionedSampler:
         lane = self._lanes[k]
         if k == 0:
             return lane, stream
-        if lane.stream is None:
-            import os
-            prio = int(os.environ.get("GNNFLOW_PART_LANE_PRIORITY", "0"))
-            if prio:
-                lane.stream = torch.cuda.Stream(device=self._device, priority=prio)
-            else:       # from the process-wide set (pipeline.side_stream: hardware queues)
-                from .pipeline import side_stream
-                lane.stream = side_stream(self._device, k)
+        if lane.stream is None:   # from the process-wide set (pipeline.side_stream: hardware queues)
+            from .pipeline import side_stream
+            lane.stream = side_stream(self._device, k)
         return lane, lane.stream
 
     def sample_async(self, nodes, ts, stream=None, worker_enqueue=False):
@@ -1419,9 +1410,7 @@ class ShardedFeatures:
             self._comm_tried = True
             kind = NativeComm.choose(self.group)
             if self.device.type == "cuda" and dist.is_initialized() and kind is not None:
-                import os
-                mb = int(os.environ.get("GNNFLOW_IPC_MAILBOX_MB", "256"))
-                self._comm = NativeComm(self.device, self.group, kind, mailbox_bytes=mb << 20)
+                self._comm = NativeComm(self.device, self.group, kind, mailbox_bytes=256 << 20)
         return self._comm
 
     def exchange_counts(self, counts: torch.Tensor) -> torch.Tensor:

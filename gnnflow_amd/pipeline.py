@@ -50,7 +50,7 @@ def side_stream(device, k: int = 0, priority: int = 0) -> torch.cuda.Stream:
     key = (device.index, int(k))
     st = _SIDE_STREAMS.get(key)
     if st is None:
-        probe = os.environ.get("GNNFLOW_STREAM_PROBE", "1") != "0" and priority == 0
+        probe = priority == 0
         taken = [torch.cuda.current_stream(device)] + \
             [v for (d, _k), v in _SIDE_STREAMS.items() if d == device.index]
         rejected = _SIDE_STREAMS.setdefault(("rejected", device.index), [])
@@ -103,8 +103,7 @@ class ReplayPipeline:
             # sampling only: the loop runs at the pace of the thread that issues the samples'
             # launches (19 us per sample) unless each lane has an issuer of its own; with a cache
             # the fetch's issuer is a third busy thread and a fourth did not pay (profiles/README)
-            two_issuers = cache is None and \
-                os.environ.get("GNNFLOW_SAMPLE_ENQUEUE_THREADS", "2") != "1"
+            two_issuers = cache is None
             for k in range(1, min(int(sample_lanes), 4)):
                 clone = sampler.clone()
                 if two_issuers and k % 2 == 1 and hasattr(clone, "set_enqueue_lane"):
@@ -119,11 +118,6 @@ class ReplayPipeline:
             depth = 3 if len(self.lanes) > 1 else 2
         self.depth = max(1, min(int(depth), 3 * max(1, getattr(self.sampler, "lanes", 1)) *
                                 max(1, getattr(self.sampler, "chain_samples", 1))))
-        # GNNFLOW_PIPELINE_FETCH_FIRST=1: submit batch i's fetch before the sample of batch
-        # i + depth (the chains of a partitioned sampler over a communicator share the fetches'
-        # issuing thread; measured: no consistent difference, profiles/README.md round 4)
-        ff = os.environ.get("GNNFLOW_PIPELINE_FETCH_FIRST")
-        self.fetch_first = ff is not None and ff != "0"
 
     def step(self, i: int):
         r, t, e = self.batches[i % len(self.batches)]
@@ -193,14 +187,13 @@ class ReplayPipeline:
         while nxt < last and len(pending) < depth:
             pending.append(begin(nxt))
             nxt += 1
-        fetch_first = self.fetch_first
         if staged:
             # Batch i+2's announcement rides in batch i's fetch submission: the pull has two steps
             # to land, and the fetch of batch i depends on the announcements up to batch i's own
             # only (set_staging_lag), so that it finds the event it needs complete when it is
             # issued — a stream that really has to wait for another stream's event loses
             # 12-20 us per hand-over (profiles/README.md, round 6).
-            lead = max(1, min(int(os.environ.get("GNNFLOW_STAGE_LEAD", "2")), 3))
+            lead = 2
             ready = deque()           # MFGs waited for and announced, in batch order
             cache.set_staging_lag(0)
             j = first
@@ -241,16 +234,13 @@ class ReplayPipeline:
             return
         for i in range(first, last):
             mfgs = pending.popleft().wait()
-            if nxt < last and not fetch_first:
+            if nxt < last:
                 pending.append(begin(nxt))
                 nxt += 1
             for mfg in mfgs:
                 for b in mfg:
                     b.record_stream(main)
             cache.fetch_feature(mfgs, batches[i % nb][2], async_enqueue=True)
-            if nxt < last and fetch_first:
-                pending.append(begin(nxt))
-                nxt += 1
             if on_step:
                 on_step(i % nb, mfgs)
         cache.wait_enqueued()

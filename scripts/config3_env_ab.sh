@@ -1,10 +1,8 @@
 #!/bin/bash
 # Config 3's sampler sweep under two environments on ONE box:
 #   bash scripts/config3_env_ab.sh "ENV_A" "ENV_B" [batches=6000,60000,300000] [policies=uniform,recent]
-# e.g. "GNNFLOW_SEARCH_FENCES=1" "GNNFLOW_SEARCH_FENCES=0" (round 3: the timestamp fences),
-#      "GNNFLOW_SEARCH_LAST_TS=1" "GNNFLOW_SEARCH_LAST_TS=0" (the newest-edge shortcut),
-#      "GNNFLOW_LANE_SEARCH_MIN_ROOTS=65536" "GNNFLOW_LANE_SEARCH_MIN_ROOTS=1048576" (lane pass),
-#      "GNNFLOW_EMIT_UNROLL=1" "" (round 6: emit slots per thread).
+# e.g. "GNNFLOW_SEARCH_GROUP_LARGE=4" "GNNFLOW_SEARCH_GROUP_LARGE=8" (lanes per root, large layers),
+#      "GNNFLOW_SAMPLER_HYBRID_SEARCH=1" "GNNFLOW_SAMPLER_HYBRID_SEARCH=0" (the lane-per-root pass).
 A=$1; B=$2; BATCHES=${3:-6000,60000,300000}; POL=${4:-uniform,recent}
 mkdir -p gpurun_out/c3ab
 for side in A B; do
