@@ -1,5 +1,5 @@
 """gnnflow.cache.LRUCache on MI355X (gnnflow/cache/lru_cache.py:9-201): the LRU
-replacement itself lives in gnnflow_amd/csrc/feature_cache.hip; this class only adds the
+replacement itself lives in gnnflow_amd/csrc/cache_lru.hip; this class only adds the
 name and the edge-only reset of the reference."""
 import torch
 

@@ -10,6 +10,7 @@
 // A block's edges are grouped by destination (the sampler emits them root-major, `row`
 // non-decreasing), so both are SEGMENT operations over `offsets[num_dst + 1]`:
 // HBM-bound streaming with no atomics on the forward side.  fp32 throughout.
+#include "block_ops.hpp"
 #include "common.hpp"
 
 #include <cfloat>

@@ -14,6 +14,7 @@
 
 #include <unistd.h>
 
+#include "block_ops.hpp"
 #include "comm.hpp"
 #include "common.hpp"
 #include "edge_store.hpp"
@@ -272,39 +273,6 @@ constexpr int kCollectiveLane = 0;
 }  // namespace gf
 
 using gf::guarded;
-
-namespace gf {
-// sampler.hip
-void part_host_us(double out[8], bool reset);
-uint64_t merge_recounts();
-void philox_on_device(const uint64_t* d_in, size_t n, uint32_t* d_out, hipStream_t stream);
-// feature_cache.hip
-uint64_t lru_recounts();
-// partition.hip
-size_t partition_scratch_bytes(size_t R, int world_size);
-void partition_plan(const int64_t* d_nodes, const float* d_ts, size_t R, int world_size, int rank,
-                    int64_t* d_requests, uint32_t* d_pos, uint64_t* d_counts, void* d_scratch,
-                    size_t scratch_bytes, int device, hipStream_t stream);
-// block_ops.hip
-void segment_offsets(const int64_t* d_row, size_t num_edges, size_t num_dst, int64_t* d_offsets,
-                     int device, hipStream_t stream);
-void edge_softmax(const int64_t* d_offsets, size_t num_dst, size_t num_edges, size_t heads,
-                  const float* d_y_or_x, const float* d_grad_y, float* d_out, int device,
-                  hipStream_t stream);
-void segment_reduce_forward(const int64_t* d_offsets, size_t num_dst, const int64_t* d_col,
-                            const float* d_src, size_t dim, const float* d_w, size_t heads,
-                            bool mean, float* d_out, int device, hipStream_t stream);
-void segment_reduce_backward(const int64_t* d_offsets, size_t num_dst, const int64_t* d_col,
-                             const float* d_src, size_t dim, const float* d_w, size_t heads,
-                             bool mean, const float* d_grad_out, float* d_grad_src,
-                             size_t num_src, float* d_grad_w, int device, hipStream_t stream);
-void segment_max_forward(const int64_t* d_offsets, size_t num_dst, const int64_t* d_col,
-                         const float* d_src, size_t dim, float* d_out, int64_t* d_arg, int device,
-                         hipStream_t stream);
-void segment_max_backward(size_t num_dst, const int64_t* d_col, size_t dim,
-                          const float* d_grad_out, const int64_t* d_arg, float* d_grad_src,
-                          size_t num_src, int device, hipStream_t stream);
-}  // namespace gf
 
 extern "C" {
 

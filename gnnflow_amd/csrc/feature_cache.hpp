@@ -26,6 +26,10 @@ void memory_update(float* node_memory, float* node_memory_ts, float* mailbox, fl
                    hipStream_t stream);
 
 class FeatureCache;
+// kernel-argument structs of the cache's translation units (feature_cache_ctx.hpp)
+struct Ctx;
+struct StageCtx;
+struct PullJob;
 void fetch_blocks(FeatureCache* node, FeatureCache* edge, const gf_fetch_desc* descs, size_t n,
                   hipStream_t stream);
 // Pulls the table rows of the ids a coming fetch_blocks(descs) will miss into the caches' staging
@@ -35,7 +39,7 @@ void fetch_blocks(FeatureCache* node, FeatureCache* edge, const gf_fetch_desc* d
 bool prefetch_blocks(FeatureCache* node, FeatureCache* edge, const gf_fetch_desc* descs, size_t n,
                      hipStream_t stream);
 // sharded feature tables (Cache(distributed=True)): plan the pull of a round's contexts,
-// serve received ids from a shard, fetch with the pulled rows (feature_cache.hip)
+// serve received ids from a shard, fetch with the pulled rows (cache_pull.hip)
 void pull_count(const gf_pull_desc* descs, size_t n, int world, FeatureCache* const* caches,
                 uint32_t* d_counts, int device, hipStream_t stream);
 void pull_scatter(const gf_pull_desc* descs, size_t n, int world, FeatureCache* const* caches,
@@ -45,6 +49,8 @@ void gather_rows_indexed(const float* d_rows, size_t num_local_rows, size_t dim,
                          float* d_out, uint32_t* d_flag, int device, hipStream_t stream);
 void fetch_blocks_pulled(FeatureCache* node, FeatureCache* edge, const gf_fetch_pulled_desc* descs,
                          size_t n, hipStream_t stream);
+// Granules of the fused LRU list update that a waiter had to recompute itself (cache_lru.hip)
+uint64_t lru_recounts();
 
 // One fetch round over sharded feature tables as one native call (gf_pull_round): the buffers
 // of the round (grow-only) and the transport (null: one rank, nothing travels).
@@ -76,7 +82,7 @@ class FeatureCache {
                     uint32_t* d_stats, const float* d_miss_rows, const uint32_t* d_miss_index,
                     hipStream_t stream);
   void set_policy(int policy);
-  // off: no copy of the cached rows (the table is in HBM: hits read it too); see feature_cache.hip
+  // off: no copy of the cached rows (the table is in HBM: hits read it too); see feature_cache.hip, set_row_mirror
   void set_row_mirror(bool on);
   bool row_mirror() const { return mirror_; }
   void reset_order(hipStream_t stream);
@@ -91,7 +97,7 @@ class FeatureCache {
   int device() const { return device_; }
   size_t num_ids() const { return num_ids_; }
   int32_t* pull_map() { return capacity_ ? map_.as<int32_t>() : nullptr; }
-  // Staging ring for a HOST-resident table (feature_cache.hip, "staging ring"): `generations`
+  // Staging ring for a HOST-resident table (cache_staging.hip): `generations`
   // (a power of two, >= 4) regions of `rows_per_generation` rows; 0 generations: off.
   void set_staging(size_t generations, size_t rows_per_generation);
   bool staging() const { return stage_gens_ != 0; }
@@ -116,11 +122,11 @@ class FeatureCache {
   friend void fetch_blocks_pulled(FeatureCache*, FeatureCache*, const gf_fetch_pulled_desc*, size_t,
                                   hipStream_t);
   void reserve_workspace(size_t n, hipStream_t stream);
-  // fills a device context (feature_cache.hip: struct Ctx) for one block fetch and advances
+  // fills a device context (feature_cache_ctx.hpp: struct Ctx) for one block fetch and advances
   // the host-side epoch / counter ring (LRU: schedules a queue compaction when due)
   void prepare(const int64_t* d_ids, size_t n, float* d_out, bool update, uint32_t* d_stats,
-               void* ctx_out, hipStream_t stream);
-  void init_queue(hipStream_t stream);   // LRU list (feature_cache.hip header)
+               Ctx* ctx_out, hipStream_t stream);
+  void init_queue(hipStream_t stream);   // LRU list (cache_lru.hip header)
 
   size_t num_ids_, capacity_, dim_;
   const float* feats_;
@@ -138,7 +144,7 @@ class FeatureCache {
                                      // first; two buffers, the device knows which is current
   DeviceBuffer qstate_;    // LRU: parity of the current list buffer (+ head / tail of the
                            // queue form), device resident
-  // LRU of a large cache is kept as a queue with dead entries (feature_cache.hip, "LRU as a
+  // LRU of a large cache is kept as a queue with dead entries (cache_lru.hip, "LRU as a
   // queue"): updates cost O(block rows), not O(capacity)
   DeviceBuffer qpos_;      // uint32[capacity]  position of the slot's (live) list / queue entry
   DeviceBuffer wsnap_;     // uint2 per word of qbits_: {word, hit entries before it in its tile}
@@ -156,7 +162,7 @@ class FeatureCache {
   DeviceBuffer ws_;        // per-fetch scratch
   size_t ws_rows_ = 0;
   DeviceBuffer granules_;  // LRU list form in one launch: {launch tag, count} per list tile / row
-                           // workgroup (feature_cache.hip, lru_list_fused_kernel)
+                           // workgroup (cache_lru.hip, lru_list_fused_kernel)
   uint32_t fuse_tag_ = 0;  // tag of the last such launch: unique per cache, never reset
   DeviceBuffer trace_;     // gf_debug_lru_trace
   uint32_t epoch_ = 0;     // fetches with update so far (host side; kernel argument)
@@ -181,11 +187,11 @@ class FeatureCache {
   uint32_t synced_gen_ = 0;               // newest generation a fetch stream has waited for
   uint32_t stage_lag_ = 0;                // newest generations a fetch does not depend on
   bool stage_advance();                   // takes the next generation; false: dropped
-  bool stage_begin(void* stage_ctx_out, const int64_t* d_ids, size_t n, bool cached);
-  void stage_pull(void* pull_job_out);
+  bool stage_begin(StageCtx* stage_ctx_out, const int64_t* d_ids, size_t n, bool cached);
+  void stage_pull(PullJob* pull_job_out);
   void stage_sync(hipStream_t stream, hipEvent_t* seen, int* num_seen);
   uint32_t stage_hi() const;
-  void stage_fill(void* ctx_out);         // ring fields of a gather context
+  void stage_fill(Ctx* ctx_out);          // ring fields of a gather context
   void stage_round_done();
   uint64_t ring_pos_ = 0;
   int policy_ = GF_CACHE_LRU;

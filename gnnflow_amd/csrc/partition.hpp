@@ -11,6 +11,10 @@ namespace gf {
 
 size_t partition_scratch_bytes(size_t R, int world_size);
 
+void partition_plan(const int64_t* d_nodes, const float* d_ts, size_t R, int world_size, int rank,
+                    int64_t* d_requests, uint32_t* d_pos, uint64_t* d_counts, void* d_scratch,
+                    size_t scratch_bytes, int device, hipStream_t stream);
+
 void partition_plan_dev(const int64_t* d_nodes, const float* d_ts, const uint64_t* d_R,
                         size_t R_bound, int world_size, int rank, int64_t* d_requests,
                         uint32_t* d_pos, uint64_t* d_counts, void* d_scratch,

@@ -210,4 +210,9 @@ class Sampler {
   hipStream_t own_stream_ = nullptr;
 };
 
+// diagnostics and test hooks (sampler.hip)
+void part_host_us(double out[8], bool reset);
+uint64_t merge_recounts();
+void philox_on_device(const uint64_t* d_in, size_t n, uint32_t* d_out, hipStream_t stream);
+
 }  // namespace gf
