@@ -252,6 +252,10 @@ PROTOTYPES = {
     "gf_block_reduce": (C.c_int, [_p, _sz, _p, _p, _sz, _p, _sz, C.c_int, _p, C.c_int, _p]),
     "gf_block_reduce_backward": (C.c_int, [_p, _sz, _p, _p, _sz, _p, _sz, C.c_int, _p, _p, _sz,
                                            _p, C.c_int, _p]),
+    "gf_block_attention": (C.c_int, [_p, _sz, _sz, _sz, _sz, _p, _p, _p, C.c_float, _p, _p,
+                                     C.c_int, _p]),
+    "gf_block_attention_backward": (C.c_int, [_p, _sz, _sz, _sz, _sz, _p, _p, _p, _p, C.c_float,
+                                              _p, _p, _p, _p, C.c_int, _p]),
     "gf_block_reduce_max": (C.c_int, [_p, _sz, _p, _p, _sz, _p, _p, C.c_int, _p]),
     "gf_block_reduce_max_backward": (C.c_int, [_sz, _p, _sz, _p, _p, _p, _sz, C.c_int, _p]),
     "gf_debug_part_host_us": (C.c_int, [C.POINTER(C.c_double), C.c_int]),

@@ -1,0 +1,310 @@
+// Fused temporal attention over a sampled block: the attention of the reference's
+// TransfomerAttentionLayer (gnnflow/models/modules/layers.py:144-159) as ONE segment operation.
+//
+//   z[e,h]     = sum_c q[d,h,c] * k[e,h,c]          d = destination of edge e
+//   s[e,h]     = z > 0 ? z : slope * z
+//   a[e,h]     = softmax of s over the edges of d (max-subtracted)
+//   out[d,h,c] = sum_e a[e,h] * v[e,h,c]
+//
+// The layer computes K and V PER EDGE and a block's edges are grouped by destination, so edge
+// e reads k[e], v[e] and q[row[e]]: no source index, no atomics, forward or backward, and
+// every output address is written exactly once.  fp32 throughout.
+//
+// Work item = one (destination, head) pair, given to a GROUP of G lanes (G = 8, 16, 32 or 64,
+// the smallest that covers the D columns of a head; a head wider than 64 columns gives each
+// lane NC = ceil(D / 64) columns, rounded up to a power of two, at most 16).  A head's
+// columns are contiguous, so a group's loads are one contiguous run and heads need no
+// alignment to the 64-lane stride.  Sums over a head's columns are a per-lane serial sum over
+// its NC columns followed by an xor butterfly over the group; `head_dot()` is the only place a
+// score is computed, forward and backward, so both passes see bit-identical z (the library is
+// built with -ffp-contract=off and without fast-math) and never disagree about its sign.
+//
+// Softmax: TWO PASSES over the scores, which are parked in att[] itself.  Score i of a segment
+// is written, read back and finally replaced by a[i] by the same lane (i mod G) of the same
+// group, so no fence is needed; k and v are each read exactly once by the forward.
+#include "block_ops.hpp"
+#include "common.hpp"
+
+#include <cfloat>
+#include <cstdint>
+
+namespace gf {
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kMaxChunks = 16;   // columns per lane of a 64-lane group: D <= 64 * 16
+
+template <int G>
+__device__ inline float group_sum(float v) {
+#pragma unroll
+  for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// value of lane `j` of the caller's group
+template <int G>
+__device__ inline float group_read(float v, int j) {
+  return __shfl(v, ((threadIdx.x & 63) & ~(G - 1)) + j, 64);
+}
+
+// sum_c a[c] * row[c] over the head's D columns; a[] holds the lane's columns of the other
+// operand (0 past D).  The same value in every lane of the group.
+template <int G, int NC>
+__device__ inline float head_dot(const float (&a)[NC], const float* __restrict__ row,
+                                 uint32_t D, uint32_t lig) {
+  float p = 0.f;
+#pragma unroll
+  for (int j = 0; j < NC; ++j) {
+    const uint32_t c = lig + G * j;
+    if (c < D) p += a[j] * row[c];
+  }
+  return group_sum<G>(p);
+}
+
+template <int G, int NC>
+__device__ inline void load_head(float (&a)[NC], const float* __restrict__ row, uint32_t D,
+                                 uint32_t lig) {
+#pragma unroll
+  for (int j = 0; j < NC; ++j) {
+    const uint32_t c = lig + G * j;
+    a[j] = c < D ? row[c] : 0.f;
+  }
+}
+
+__device__ inline float leaky(float z, float slope) { return z > 0.f ? z : slope * z; }
+
+template <int G, int NC>
+__global__ void block_attention_fwd(const int64_t* __restrict__ offsets, uint64_t items,
+                                    uint32_t H, uint32_t D, const float* __restrict__ q,
+                                    const float* __restrict__ k, const float* __restrict__ v,
+                                    float slope, float* __restrict__ out, float* att) {
+  const uint32_t lig = threadIdx.x & (G - 1);
+  const uint64_t w = (static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / G;
+  if (w >= items) return;                     // group-uniform
+  const uint64_t d = w / H;
+  const uint32_t h = static_cast<uint32_t>(w - d * H);
+  const int64_t b = offsets[d], e = offsets[d + 1];
+  const uint64_t width = static_cast<uint64_t>(H) * D;
+  float* out_row = out + d * width + static_cast<uint64_t>(h) * D;
+  if (e <= b) {                               // no in-edges: exactly 0
+#pragma unroll
+    for (int j = 0; j < NC; ++j)
+      if (lig + G * j < D) out_row[lig + G * j] = 0.f;
+    return;
+  }
+  float qr[NC];
+  load_head<G, NC>(qr, q + d * width + static_cast<uint64_t>(h) * D, D, lig);
+
+  // pass 1 (reads k once): scores into att[], running max
+  float m = -FLT_MAX;
+  for (int64_t i = b; i < e; ++i) {
+    const float s = leaky(head_dot<G, NC>(qr, k + i * width + static_cast<uint64_t>(h) * D, D, lig),
+                          slope);
+    m = fmaxf(m, s);
+    if (static_cast<uint32_t>(i - b) % G == lig) att[i * H + h] = s;
+  }
+  // pass 2a: the lane's own scores -> sum of exponentials
+  float l = 0.f;
+  for (int64_t i = b + lig; i < e; i += G) l += __expf(att[i * H + h] - m);
+  const float inv = 1.f / group_sum<G>(l);
+  // pass 2b (reads v once): a = exp(s - m) / l replaces the score, G edges at a time, and each
+  // a is handed round the group for the weighted sum
+  float acc[NC];
+#pragma unroll
+  for (int j = 0; j < NC; ++j) acc[j] = 0.f;
+  for (int64_t base = b; base < e; base += G) {
+    const int64_t mine = base + lig;
+    float a = 0.f;
+    if (mine < e) {
+      a = __expf(att[mine * H + h] - m) * inv;
+      att[mine * H + h] = a;
+    }
+    const int n = static_cast<int>(e - base < G ? e - base : G);
+    for (int t = 0; t < n; ++t) {
+      const float at = group_read<G>(a, t);
+      const float* vr = v + (base + t) * width + static_cast<uint64_t>(h) * D;
+#pragma unroll
+      for (int j = 0; j < NC; ++j) {
+        const uint32_t c = lig + G * j;
+        if (c < D) acc[j] += at * vr[c];
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NC; ++j)
+    if (lig + G * j < D) out_row[lig + G * j] = acc[j];
+}
+
+// ga[e,h] = sum_c gout[d,h,c] v[e,h,c]        gv[e,h,c] = a[e,h] gout[d,h,c]
+// gs[e,h] = a (ga - sum_e' a ga)              gz = gs * (z > 0 ? 1 : slope)
+// gq[d,h,c] = sum_e gz k[e,h,c]               gk[e,h,c] = gz q[d,h,c]
+// Sweep 1 forms sum a ga; sweep 2 recomputes ga (the same head_dot, so the same bits) instead
+// of parking it anywhere.  A null gq / gk / gv skips that output's work; z is recomputed by
+// the forward's own instruction sequence only when gq or gk is wanted.
+template <int G, int NC>
+__global__ void block_attention_bwd(const int64_t* __restrict__ offsets, uint64_t items,
+                                    uint32_t H, uint32_t D, const float* __restrict__ q,
+                                    const float* __restrict__ k, const float* __restrict__ v,
+                                    const float* __restrict__ att, float slope,
+                                    const float* __restrict__ gout, float* __restrict__ gq,
+                                    float* __restrict__ gk, float* __restrict__ gv) {
+  const uint32_t lig = threadIdx.x & (G - 1);
+  const uint64_t w = (static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / G;
+  if (w >= items) return;
+  const uint64_t d = w / H;
+  const uint32_t h = static_cast<uint32_t>(w - d * H);
+  const int64_t b = offsets[d], e = offsets[d + 1];
+  const uint64_t width = static_cast<uint64_t>(H) * D;
+  const uint64_t head = static_cast<uint64_t>(h) * D;
+  if (e <= b) {
+    if (gq) {
+#pragma unroll
+      for (int j = 0; j < NC; ++j)
+        if (lig + G * j < D) gq[d * width + head + lig + G * j] = 0.f;
+    }
+    return;
+  }
+  float gr[NC];
+  load_head<G, NC>(gr, gout + d * width + head, D, lig);
+
+  if (gv) {
+    for (int64_t i = b; i < e; ++i) {
+      const float a = att[i * H + h];
+#pragma unroll
+      for (int j = 0; j < NC; ++j) {
+        const uint32_t c = lig + G * j;
+        if (c < D) gv[i * width + head + c] = a * gr[j];
+      }
+    }
+  }
+  if (!gq && !gk) return;
+
+  float dot = 0.f;
+  for (int64_t i = b; i < e; ++i)
+    dot += att[i * H + h] * head_dot<G, NC>(gr, v + i * width + head, D, lig);
+
+  float qr[NC], acc[NC];
+  load_head<G, NC>(qr, q + d * width + head, D, lig);
+#pragma unroll
+  for (int j = 0; j < NC; ++j) acc[j] = 0.f;
+  for (int64_t i = b; i < e; ++i) {
+    const float* kr = k + i * width + head;
+    const float ga = head_dot<G, NC>(gr, v + i * width + head, D, lig);
+    const float z = head_dot<G, NC>(qr, kr, D, lig);
+    const float gs = att[i * H + h] * (ga - dot);
+    const float gz = z > 0.f ? gs : gs * slope;
+#pragma unroll
+    for (int j = 0; j < NC; ++j) {
+      const uint32_t c = lig + G * j;
+      if (c < D) {
+        if (gk) gk[i * width + head + c] = gz * qr[j];
+        acc[j] += gz * kr[c];
+      }
+    }
+  }
+  if (gq) {
+#pragma unroll
+    for (int j = 0; j < NC; ++j)
+      if (lig + G * j < D) gq[d * width + head + lig + G * j] = acc[j];
+  }
+}
+
+struct Shape {
+  const int64_t* offsets;
+  uint64_t items;
+  uint32_t H, D;
+};
+
+template <int G, int NC>
+void launch_fwd(const Shape& s, const float* q, const float* k, const float* v, float slope,
+                float* out, float* att, hipStream_t stream) {
+  const uint64_t threads = s.items * G;
+  block_attention_fwd<G, NC><<<dim3(static_cast<unsigned>((threads + kThreads - 1) / kThreads)),
+                               dim3(kThreads), 0, stream>>>(s.offsets, s.items, s.H, s.D, q, k, v,
+                                                            slope, out, att);
+}
+
+template <int G, int NC>
+void launch_bwd(const Shape& s, const float* q, const float* k, const float* v, const float* att,
+                float slope, const float* gout, float* gq, float* gk, float* gv,
+                hipStream_t stream) {
+  const uint64_t threads = s.items * G;
+  block_attention_bwd<G, NC><<<dim3(static_cast<unsigned>((threads + kThreads - 1) / kThreads)),
+                               dim3(kThreads), 0, stream>>>(s.offsets, s.items, s.H, s.D, q, k, v,
+                                                            att, slope, gout, gq, gk, gv);
+}
+
+// calls f.template operator()<G, NC>() for the group size / columns per lane of a D-column head
+template <class F>
+void dispatch(uint32_t D, F&& f) {
+  if (D <= 8) f.template operator()<8, 1>();
+  else if (D <= 16) f.template operator()<16, 1>();
+  else if (D <= 32) f.template operator()<32, 1>();
+  else if (D <= 64) f.template operator()<64, 1>();
+  else if (D <= 128) f.template operator()<64, 2>();
+  else if (D <= 256) f.template operator()<64, 4>();
+  else if (D <= 512) f.template operator()<64, 8>();
+  else f.template operator()<64, kMaxChunks>();
+}
+
+struct Fwd {
+  Shape s; const float *q, *k, *v; float slope; float *out, *att; hipStream_t stream;
+  template <int G, int NC> void operator()() {
+    launch_fwd<G, NC>(s, q, k, v, slope, out, att, stream);
+  }
+};
+struct Bwd {
+  Shape s; const float *q, *k, *v, *att; float slope; const float* gout; float *gq, *gk, *gv;
+  hipStream_t stream;
+  template <int G, int NC> void operator()() {
+    launch_bwd<G, NC>(s, q, k, v, att, slope, gout, gq, gk, gv, stream);
+  }
+};
+
+Shape checked_shape(const int64_t* d_offsets, size_t num_dst, size_t heads, size_t head_dim) {
+  GF_REQUIRE(heads >= 1 && head_dim >= 1, "block_attention: heads and head_dim must be >= 1");
+  GF_REQUIRE(heads <= kBlockAttentionMaxWidth && head_dim <= kBlockAttentionMaxWidth &&
+                 heads * head_dim <= kBlockAttentionMaxWidth,
+             "block_attention: heads * head_dim exceeds GF_BLOCK_ATTENTION_MAX_WIDTH (1024)");
+  static_assert(kBlockAttentionMaxWidth <= 64 * kMaxChunks, "a head must fit one group");
+  GF_REQUIRE(d_offsets != nullptr, "block_attention: null offsets");
+  // one group of up to 64 lanes per (destination, head): the grid stays below 2^31 blocks
+  GF_REQUIRE(num_dst <= (size_t{1} << 32) / heads, "block_attention: too many destinations");
+  return Shape{d_offsets, static_cast<uint64_t>(num_dst) * heads, static_cast<uint32_t>(heads),
+               static_cast<uint32_t>(head_dim)};
+}
+
+}  // namespace
+
+void block_attention_forward(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                             size_t heads, size_t head_dim, const float* d_q, const float* d_k,
+                             const float* d_v, float negative_slope, float* d_out, float* d_att,
+                             int device, hipStream_t stream) {
+  const Shape s = checked_shape(d_offsets, num_dst, heads, head_dim);
+  if (num_dst == 0) return;
+  GF_REQUIRE(d_q && d_out, "block_attention: null q or out");
+  GF_REQUIRE(num_edges == 0 || (d_k && d_v && d_att), "block_attention: null k, v or att");
+  DeviceGuard dg(device);
+  dispatch(s.D, Fwd{s, d_q, d_k, d_v, negative_slope, d_out, d_att, stream});
+  GF_HIP(hipGetLastError());
+}
+
+void block_attention_backward(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                              size_t heads, size_t head_dim, const float* d_q, const float* d_k,
+                              const float* d_v, const float* d_att, float negative_slope,
+                              const float* d_grad_out, float* d_grad_q, float* d_grad_k,
+                              float* d_grad_v, int device, hipStream_t stream) {
+  const Shape s = checked_shape(d_offsets, num_dst, heads, head_dim);
+  if (num_dst == 0 || (!d_grad_q && !d_grad_k && !d_grad_v)) return;
+  GF_REQUIRE(d_grad_out != nullptr, "block_attention backward: null gradient");
+  GF_REQUIRE(num_edges == 0 || (d_att && d_v), "block_attention backward: null att or v");
+  GF_REQUIRE(num_edges == 0 || (!d_grad_q && !d_grad_k) || (d_q && d_k),
+             "block_attention backward: grad_q / grad_k need q and k");
+  if (num_edges == 0 && !d_grad_q) return;
+  DeviceGuard dg(device);
+  dispatch(s.D, Bwd{s, d_q, d_k, d_v, d_att, negative_slope, d_grad_out, d_grad_q, d_grad_k,
+                    d_grad_v, stream});
+  GF_HIP(hipGetLastError());
+}
+
+}  // namespace gf

@@ -1332,6 +1332,30 @@ int gf_block_reduce_max_backward(size_t num_dst, const int64_t* d_col, size_t di
   });
 }
 
+static_assert(GF_BLOCK_ATTENTION_MAX_WIDTH == gf::kBlockAttentionMaxWidth,
+              "gnnflow_hip.h and block_ops.hpp disagree on the attention width limit");
+int gf_block_attention(const int64_t* d_offsets, size_t num_dst, size_t num_edges, size_t heads,
+                       size_t head_dim, const float* d_q, const float* d_k, const float* d_v,
+                       float negative_slope, float* d_out, float* d_att, int device,
+                       void* stream) {
+  return guarded([&] {
+    gf::block_attention_forward(d_offsets, num_dst, num_edges, heads, head_dim, d_q, d_k, d_v,
+                                negative_slope, d_out, d_att, device,
+                                static_cast<hipStream_t>(stream));
+  });
+}
+int gf_block_attention_backward(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                                size_t heads, size_t head_dim, const float* d_q,
+                                const float* d_k, const float* d_v, const float* d_att,
+                                float negative_slope, const float* d_grad_out, float* d_grad_q,
+                                float* d_grad_k, float* d_grad_v, int device, void* stream) {
+  return guarded([&] {
+    gf::block_attention_backward(d_offsets, num_dst, num_edges, heads, head_dim, d_q, d_k, d_v,
+                                 d_att, negative_slope, d_grad_out, d_grad_q, d_grad_k, d_grad_v,
+                                 device, static_cast<hipStream_t>(stream));
+  });
+}
+
 int gf_debug_philox(const uint64_t* d_in, size_t n, uint32_t* d_out, void* stream) {
   return guarded([&] {
     GF_REQUIRE(n == 0 || (d_in != nullptr && d_out != nullptr), "gf_debug_philox: null buffer");

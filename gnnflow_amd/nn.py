@@ -2,7 +2,12 @@
 reference's static models instantiate (gnnflow/models/graphsage.py:27-31, gat.py:28-46), with
 dgl's constructor arguments, parameter names and formulas, on the block ops of
 gnnflow_amd.ops.  dgl (requirements.txt: dgl >= 0.7) is not vendored in the reference; these
-follow its documented layer definitions."""
+follow its documented layer definitions.
+
+TimeEncode / TemporalAttentionLayer are the reference's own temporal attention
+(gnnflow/models/modules/layers.py:16-168, the layer of TGN, TGAT and DySAT) with its constructor
+arguments and parameter names, on ops.block_attention."""
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -154,3 +159,94 @@ class GATConv(nn.Module):
         if get_attention:
             return rst, a.unsqueeze(-1)
         return rst
+
+
+class TimeEncode(nn.Module):
+    """TGAT's time encoding cos(w * dt + b): w = 1 / 10^linspace(0, 9, dim_time), b = 0 at
+    initialisation, both trainable; held as a Linear(1, dim_time) named `w`."""
+
+    def __init__(self, dim_time: int):
+        super().__init__()
+        self.w = nn.Linear(1, dim_time)
+        freq = 1 / 10 ** np.linspace(0, 9, dim_time, dtype=np.float32)
+        self.w.weight = nn.Parameter(torch.from_numpy(freq).reshape(dim_time, 1))
+        self.w.bias = nn.Parameter(torch.zeros(dim_time))
+
+    def forward(self, delta_time: torch.Tensor) -> torch.Tensor:
+        return torch.cos(self.w(delta_time.reshape(-1, 1)))
+
+
+class TemporalAttentionLayer(nn.Module):
+    """Temporal multi-head attention over a sampled block (reads b.srcdata['h'], b.edata['f'],
+    b.edata['dt']):
+
+        Q = w_q([h_dst | time_enc(0)])            per destination
+        K, V = w_k, w_v([h_src | f | time_enc(dt)])   per edge
+        att = edge_softmax(leaky_relu(<Q, K> per head, 0.2)), dropped out with att_dropout
+        out = layer_norm(relu(dropout(w_out([sum_e att V | h_dst]))))
+
+    A width of 0 leaves that part out: without node features the query is the time encoding
+    alone, or a row of ones (and w_q the identity) without a time encoding either.  With
+    attention dropout inactive (p = 0 or eval mode) the attention is one ops.block_attention
+    call; otherwise edge_softmax -> dropout -> block_reduce, so that dropout acts on the
+    attention weights as in the reference."""
+
+    def __init__(self, dim_node: int, dim_edge: int, dim_time: int, dim_out: int, num_head: int,
+                 dropout: float, att_dropout: float):
+        super().__init__()
+        self.use_node_feat = dim_node > 0
+        self.use_edge_feat = dim_edge > 0
+        self.use_time_enc = dim_time > 0
+        self.dim_node, self.dim_time, self.dim_out, self.num_head = \
+            dim_node, dim_time, dim_out, num_head
+        self.dropout = nn.Dropout(dropout)
+        self.att_dropout = nn.Dropout(att_dropout)
+        self.att_act = nn.LeakyReLU(0.2)
+        if self.use_time_enc:
+            self.time_enc = TimeEncode(dim_time)
+        if self.use_node_feat or self.use_time_enc:
+            self.w_q = nn.Linear(dim_node + dim_time, dim_out)
+        else:
+            self.w_q = nn.Identity()
+        self.w_k = nn.Linear(dim_node + dim_edge + dim_time, dim_out)
+        self.w_v = nn.Linear(dim_node + dim_edge + dim_time, dim_out)
+        self.w_out = nn.Linear(dim_node + dim_out, dim_out)
+        self.layer_norm = nn.LayerNorm(dim_out)
+        # False: always the composed edge_softmax -> block_reduce chain (not part of the state)
+        self.fused_attention = True
+
+    def forward(self, b):
+        E, R, dev = b.num_edges(), b.num_dst_nodes(), b.device
+        if E == 0:
+            return torch.zeros((R, self.dim_out), device=dev)
+        parts_q, parts_kv = [], []
+        if self.use_node_feat:
+            h = b.srcdata['h']
+            h_dst = h[:R]
+            parts_q.append(h_dst)
+            parts_kv.append(h[R:])
+        elif not self.use_time_enc:
+            parts_q.append(torch.ones((R, self.dim_out), device=dev))
+        if self.use_edge_feat:
+            parts_kv.append(b.edata['f'])
+        if self.use_time_enc:
+            parts_q.append(self.time_enc(torch.zeros(R, dtype=torch.float32, device=dev)))
+            parts_kv.append(self.time_enc(b.edata['dt']))
+        kv = torch.cat(parts_kv, dim=1) if parts_kv else torch.zeros((E, 0), device=dev)
+        H = self.num_head
+        q = self.w_q(torch.cat(parts_q, dim=1)).reshape(R, H, -1)
+        k = self.w_k(kv).reshape(E, H, -1)
+        v = self.w_v(kv).reshape(E, H, -1)
+        if self.fused_attention and (self.att_dropout.p == 0 or not self.training):
+            agg = ops.block_attention(b, q, k, v, negative_slope=self.att_act.negative_slope)
+        else:
+            row = b.edges()[1]
+            att = ops.edge_softmax(b, self.att_act((q[row] * k).sum(dim=2)))
+            msg = (v * self.att_dropout(att)[:, :, None]).reshape(E, -1)
+            agg = ops.block_reduce(b, torch.cat([torch.zeros((R, msg.shape[1]), device=dev), msg]))
+        agg = agg.reshape(R, -1)
+        rst = torch.cat([agg, h_dst], dim=1) if self.use_node_feat else agg
+        return self.layer_norm(F.relu(self.dropout(self.w_out(rst))))
+
+
+TransfomerAttentionLayer = TemporalAttentionLayer      # the reference's own spelling

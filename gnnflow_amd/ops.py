@@ -4,6 +4,7 @@ make on a sampled block, on HIP segment kernels (csrc/block_ops.hip) with autogr
     edge_softmax(block, logits)            dgl.ops.edge_softmax      (layers.py:153)
     block.update_all(fn.copy_src('v','m'), fn.sum('m','h'))          (layers.py:159)
     copy_u / u_mul_e messages, sum / mean reducers                   (dgl.nn.SAGEConv / GATConv)
+    block_attention(block, q, k, v)        layers.py:144-159 in one launch (csrc/block_attention.hip)
 
 A block's edges are grouped by destination (the sampler emits them that way); blocks built by
 hand with unordered edges are handled through a stable permutation.
@@ -134,6 +135,111 @@ class _BlockMax(torch.autograd.Function):
                 num_dst, _ptr(col), dim, _ptr(g), arg.data_ptr(), gs.data_ptr(), shape[0],
                 g.device.index, _stream(g.device)))
         return gs, None, None, None, None
+
+
+MAX_ATTENTION_WIDTH = 1024      # GF_BLOCK_ATTENTION_MAX_WIDTH: the limit on heads * head_dim
+
+
+class _BlockAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, offsets, num_dst, slope):
+        # q [num_dst, H, D], k / v [E, H, D] contiguous fp32, edges grouped by destination
+        E, H, D = k.shape
+        out = torch.empty((num_dst, H, D), dtype=torch.float32, device=q.device)
+        att = torch.empty((E, H), dtype=torch.float32, device=q.device)
+        with torch.cuda.device(q.device):
+            _capi.check(_capi.load().gf_block_attention(
+                offsets.data_ptr(), num_dst, E, H, D, q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                slope, out.data_ptr(), att.data_ptr(), q.device.index, _stream(q.device)))
+        ctx.save_for_backward(q, k, v, att, offsets)
+        ctx.slope = slope
+        ctx.mark_non_differentiable(att)
+        return out, att
+
+    @staticmethod
+    def backward(ctx, grad, _grad_att):
+        q, k, v, att, offsets = ctx.saved_tensors
+        g = _f32(grad)
+        E, H, D = k.shape
+        need_q, need_k, need_v = ctx.needs_input_grad[:3]
+        gq = torch.empty_like(q) if need_q else None
+        gk = torch.empty_like(k) if need_k else None
+        gv = torch.empty_like(v) if need_v else None
+        if need_q or need_k or need_v:
+            with torch.cuda.device(q.device):
+                _capi.check(_capi.load().gf_block_attention_backward(
+                    offsets.data_ptr(), q.shape[0], E, H, D, q.data_ptr(), k.data_ptr(),
+                    v.data_ptr(), att.data_ptr(), ctx.slope, g.data_ptr(), _ptr(gq), _ptr(gk),
+                    _ptr(gv), q.device.index, _stream(q.device)))
+        return gq, gk, gv, None, None, None
+
+
+class _NoEdgeAttention(torch.autograd.Function):
+    """A block without edges or without destinations: zeros, and zero gradients."""
+    @staticmethod
+    def forward(ctx, q, k, v):
+        ctx.save_for_backward(q, k, v)
+        return torch.zeros_like(q)
+
+    @staticmethod
+    def backward(ctx, grad):
+        return tuple(torch.zeros_like(t) if need else None
+                     for t, need in zip(ctx.saved_tensors, ctx.needs_input_grad))
+
+
+def block_attention(block, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                    negative_slope: float = 0.2, return_attention: bool = False, heads=None):
+    """The attention of the reference's TransfomerAttentionLayer (layers.py:144-159) with
+    per-edge keys and values, in one kernel each way:
+
+        att[e, h] = edge_softmax(leaky_relu(sum_c q[row[e], h, c] * k[e, h, c], negative_slope))
+        out[d, h] = sum over the edges e into d of att[e, h] * v[e, h]      (0 without in-edges)
+
+    q: [num_dst_nodes, H, D]; k, v: [num_edges, H, D], float32.  The inputs are 3-D; a 2-D
+    [rows, H * D] input is accepted only together with `heads=H`.  H * D is at most
+    MAX_ATTENTION_WIDTH.  Returns out [num_dst_nodes, H, D], and with return_attention=True
+    also att [num_edges, H] in the caller's edge order (not differentiable)."""
+    num_dst, E = block.num_dst_nodes(), block.num_edges()
+    q, k, v = _f32(q), _f32(k), _f32(v)
+    if q.shape[0] != num_dst:
+        raise ValueError("q must have one row per destination node")
+    if k.shape[0] != E or v.shape[0] != E:
+        raise ValueError("k and v must have one row per edge")
+    shaped = []
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.dim() == 2 and heads is not None:
+            if heads < 1 or t.shape[1] % heads or t.shape[1] == 0:
+                raise ValueError("{} has {} columns, not a multiple of heads={}".format(
+                    name, t.shape[1], heads))
+            t = t.view(t.shape[0], heads, t.shape[1] // heads)
+        elif t.dim() != 3:
+            raise ValueError("{} must be [rows, H, D] (or [rows, H * D] with heads=), got {}"
+                             .format(name, tuple(t.shape)))
+        shaped.append(t)
+    q, k, v = shaped
+    if q.shape[1:] != k.shape[1:] or k.shape[1:] != v.shape[1:]:
+        raise ValueError("q, k and v differ in [H, D]: {}, {}, {}".format(
+            tuple(q.shape[1:]), tuple(k.shape[1:]), tuple(v.shape[1:])))
+    H, D = int(q.shape[1]), int(q.shape[2])
+    if heads is not None and heads != H:
+        raise ValueError("heads={} but the inputs have {} heads".format(heads, H))
+    if H < 1 or D < 1:
+        raise ValueError("block_attention needs H >= 1 and D >= 1")
+    if H * D > MAX_ATTENTION_WIDTH:
+        raise ValueError("H * D = {} exceeds the limit of {}".format(H * D, MAX_ATTENTION_WIDTH))
+    if E == 0 or num_dst == 0:
+        out = _NoEdgeAttention.apply(q, k, v)      # nothing to launch
+        return (out, torch.zeros((E, H), dtype=torch.float32, device=q.device)) \
+            if return_attention else out
+    offsets, _, perm = block.segments()
+    if perm is not None:
+        k, v = k[perm], v[perm]
+    out, att = _BlockAttention.apply(q, k, v, offsets, num_dst, float(negative_slope))
+    if not return_attention:
+        return out
+    if perm is not None:
+        att = torch.empty_like(att).index_copy(0, perm, att)
+    return out, att
 
 
 def block_max(block, src: torch.Tensor) -> torch.Tensor:

@@ -773,6 +773,30 @@ GF_API int gf_block_reduce_max_backward(size_t num_dst, const int64_t* d_col, si
                                         float* d_grad_src, size_t num_src, int device,
                                         void* stream);
 
+/* Fused attention of the reference's TransfomerAttentionLayer (layers.py:144-159), whose keys
+ * and values are PER EDGE: q [num_dst, heads, head_dim], k / v [num_edges, heads, head_dim],
+ *   z[e,h] = sum_c q[d,h,c] k[e,h,c]   (d = destination of e, from d_offsets)
+ *   att    = edge softmax of leaky_relu(z, negative_slope)          -> d_att [num_edges, heads]
+ *   out[d,h,:] = sum over the edges e of d of att[e,h] v[e,h,:]     -> d_out [num_dst, heads, head_dim]
+ * (a destination without in-edges: 0).  k and v are read once, no atomics; d_att is what the
+ * backward pass needs besides the inputs.  heads, head_dim >= 1 with
+ * heads * head_dim <= GF_BLOCK_ATTENTION_MAX_WIDTH, else GF_ERR_INVALID_ARGUMENT. */
+#define GF_BLOCK_ATTENTION_MAX_WIDTH 1024
+GF_API int gf_block_attention(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                              size_t heads, size_t head_dim, const float* d_q, const float* d_k,
+                              const float* d_v, float negative_slope, float* d_out, float* d_att,
+                              int device, void* stream);
+/* Each of d_grad_q [num_dst, ...], d_grad_k, d_grad_v [num_edges, ...] may be NULL (not needed:
+ * its work is skipped); every element of the others is written exactly once, rows of
+ * destinations without in-edges included. */
+GF_API int gf_block_attention_backward(const int64_t* d_offsets, size_t num_dst,
+                                       size_t num_edges, size_t heads, size_t head_dim,
+                                       const float* d_q, const float* d_k, const float* d_v,
+                                       const float* d_att, float negative_slope,
+                                       const float* d_grad_out, float* d_grad_q,
+                                       float* d_grad_k, float* d_grad_v, int device,
+                                       void* stream);
+
 /* ---- measurement support (bench.py) ---------------------------------------- */
 /* Accumulated device time of a kernel family since the last reset, measured with
  * HIP events recorded around each launch on the launching stream.
