@@ -258,6 +258,10 @@ PROTOTYPES = {
                                               _p, _p, _p, _p, C.c_int, _p]),
     "gf_block_reduce_max": (C.c_int, [_p, _sz, _p, _p, _sz, _p, _p, C.c_int, _p]),
     "gf_block_reduce_max_backward": (C.c_int, [_sz, _p, _sz, _p, _p, _p, _sz, C.c_int, _p]),
+    "gf_time_encode_cat": (C.c_int, [_p, _sz, _p, _sz, _p, _p, _p, _sz, _sz, _p, C.c_int, _p]),
+    "gf_time_encode_backward_partial_rows": (C.c_int, [_sz, C.POINTER(_sz)]),
+    "gf_time_encode_backward": (C.c_int, [_p, _p, _p, _sz, _sz, _p, _sz, _sz, _p, _sz, _p, _p,
+                                          C.c_int, _p]),
     "gf_debug_part_host_us": (C.c_int, [C.POINTER(C.c_double), C.c_int]),
     "gf_debug_merge_recounts": (C.c_int, [C.POINTER(C.c_uint64)]),
     "gf_debug_part_reused_roots": (C.c_int, [C.POINTER(C.c_uint64)]),

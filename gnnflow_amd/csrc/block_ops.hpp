@@ -1,5 +1,5 @@
-// Segment operations on a sampled block (block_ops.hip, block_attention.hip): the entry points
-// other translation units call.
+// Segment operations on a sampled block (block_ops.hip, block_attention.hip) and the fused time
+// encoding in front of them (time_encode.hip): the entry points other translation units call.
 #pragma once
 
 #include <cstddef>
@@ -41,5 +41,20 @@ void block_attention_backward(const int64_t* d_offsets, size_t num_dst, size_t n
                               const float* d_v, const float* d_att, float negative_slope,
                               const float* d_grad_out, float* d_grad_q, float* d_grad_k,
                               float* d_grad_v, int device, hipStream_t stream);
+
+// time_encode.hip: out = [a | b | cosf(w * t + bias)] in one launch (a / b may be null with
+// width 0), and the gradients of w and bias from the time columns of grad_out, read in place
+// (row pitch grad_pitch floats, first time column grad_col).  The backward needs a caller-owned
+// buffer of time_encode_backward_partial_rows(n) * 2 * dim_time floats; a null d_grad_w or
+// d_grad_bias is skipped.  n == 0 launches nothing.
+constexpr size_t kTimeEncodeMaxPartialRows = 1024;
+size_t time_encode_backward_partial_rows(size_t n);
+void time_encode_cat_forward(const float* d_a, size_t width_a, const float* d_b, size_t width_b,
+                             const float* d_t, const float* d_w, const float* d_bias, size_t n,
+                             size_t dim_time, float* d_out, int device, hipStream_t stream);
+void time_encode_backward(const float* d_t, const float* d_w, const float* d_bias, size_t n,
+                          size_t dim_time, const float* d_grad_out, size_t grad_pitch,
+                          size_t grad_col, float* d_partials, size_t partial_rows,
+                          float* d_grad_w, float* d_grad_bias, int device, hipStream_t stream);
 
 }  // namespace gf

@@ -1356,6 +1356,31 @@ int gf_block_attention_backward(const int64_t* d_offsets, size_t num_dst, size_t
   });
 }
 
+int gf_time_encode_cat(const float* d_a, size_t width_a, const float* d_b, size_t width_b,
+                       const float* d_t, const float* d_w, const float* d_bias, size_t n,
+                       size_t dim_time, float* d_out, int device, void* stream) {
+  return guarded([&] {
+    gf::time_encode_cat_forward(d_a, width_a, d_b, width_b, d_t, d_w, d_bias, n, dim_time, d_out,
+                                device, static_cast<hipStream_t>(stream));
+  });
+}
+int gf_time_encode_backward_partial_rows(size_t n, size_t* rows) {
+  return guarded([&] {
+    GF_REQUIRE(rows != nullptr, "gf_time_encode_backward_partial_rows: null output");
+    *rows = gf::time_encode_backward_partial_rows(n);
+  });
+}
+int gf_time_encode_backward(const float* d_t, const float* d_w, const float* d_bias, size_t n,
+                            size_t dim_time, const float* d_grad_out, size_t grad_pitch,
+                            size_t grad_col, float* d_partials, size_t partial_rows,
+                            float* d_grad_w, float* d_grad_bias, int device, void* stream) {
+  return guarded([&] {
+    gf::time_encode_backward(d_t, d_w, d_bias, n, dim_time, d_grad_out, grad_pitch, grad_col,
+                             d_partials, partial_rows, d_grad_w, d_grad_bias, device,
+                             static_cast<hipStream_t>(stream));
+  });
+}
+
 int gf_debug_philox(const uint64_t* d_in, size_t n, uint32_t* d_out, void* stream) {
   return guarded([&] {
     GF_REQUIRE(n == 0 || (d_in != nullptr && d_out != nullptr), "gf_debug_philox: null buffer");

@@ -6,7 +6,10 @@ follow its documented layer definitions.
 
 TimeEncode / TemporalAttentionLayer are the reference's own temporal attention
 (gnnflow/models/modules/layers.py:16-168, the layer of TGN, TGAT and DySAT) with its constructor
-arguments and parameter names, on ops.block_attention."""
+arguments and parameter names, on ops.block_attention and ops.time_encode_cat.
+
+GRUMemoryUpdater is TGN's memory updater (gnnflow/models/modules/memory_updater.py, there
+spelled GRUMemeoryUpdater), the consumer of gnnflow_amd.memory.Memory.prepare_input."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -161,9 +164,17 @@ class GATConv(nn.Module):
         return rst
 
 
+# Default of `fused_time_encode` in TemporalAttentionLayer and GRUMemoryUpdater.  True only once
+# scripts/time_encode_bench.py has shown the fused op ahead of the torch chain at all three epoch
+# shapes by more than the chain's own spread (profiles/time_encode_bench.jsonl);
+# that has not been measured yet.
+FUSED_TIME_ENCODE_DEFAULT = False
+
+
 class TimeEncode(nn.Module):
     """TGAT's time encoding cos(w * dt + b): w = 1 / 10^linspace(0, 9, dim_time), b = 0 at
-    initialisation, both trainable; held as a Linear(1, dim_time) named `w`."""
+    initialisation, both trainable; held as a Linear(1, dim_time) named `w`.  float32 input on
+    the GPU takes ops.time_encode (one kernel); anything else the torch expression."""
 
     def __init__(self, dim_time: int):
         super().__init__()
@@ -173,6 +184,9 @@ class TimeEncode(nn.Module):
         self.w.bias = nn.Parameter(torch.zeros(dim_time))
 
     def forward(self, delta_time: torch.Tensor) -> torch.Tensor:
+        if delta_time.is_cuda and delta_time.dtype == torch.float32 and \
+                self.w.weight.dtype == torch.float32:
+            return ops.time_encode(delta_time.reshape(-1), self.w.weight, self.w.bias)
         return torch.cos(self.w(delta_time.reshape(-1, 1)))
 
 
@@ -189,7 +203,8 @@ class TemporalAttentionLayer(nn.Module):
     alone, or a row of ones (and w_q the identity) without a time encoding either.  With
     attention dropout inactive (p = 0 or eval mode) the attention is one ops.block_attention
     call; otherwise edge_softmax -> dropout -> block_reduce, so that dropout acts on the
-    attention weights as in the reference."""
+    attention weights as in the reference.  With `fused_time_encode` the rows [h_src | f |
+    time_enc(dt)] and [h_dst | time_enc(0)] are one ops.time_encode_cat call each."""
 
     def __init__(self, dim_node: int, dim_edge: int, dim_time: int, dim_out: int, num_head: int,
                  dropout: float, att_dropout: float):
@@ -214,11 +229,14 @@ class TemporalAttentionLayer(nn.Module):
         self.layer_norm = nn.LayerNorm(dim_out)
         # False: always the composed edge_softmax -> block_reduce chain (not part of the state)
         self.fused_attention = True
+        # False: time_enc + torch.cat instead of ops.time_encode_cat (not part of the state)
+        self.fused_time_encode = FUSED_TIME_ENCODE_DEFAULT
 
     def forward(self, b):
         E, R, dev = b.num_edges(), b.num_dst_nodes(), b.device
         if E == 0:
             return torch.zeros((R, self.dim_out), device=dev)
+        fused_te = self.fused_time_encode and self.use_time_enc
         parts_q, parts_kv = [], []
         if self.use_node_feat:
             h = b.srcdata['h']
@@ -229,12 +247,19 @@ class TemporalAttentionLayer(nn.Module):
             parts_q.append(torch.ones((R, self.dim_out), device=dev))
         if self.use_edge_feat:
             parts_kv.append(b.edata['f'])
-        if self.use_time_enc:
-            parts_q.append(self.time_enc(torch.zeros(R, dtype=torch.float32, device=dev)))
-            parts_kv.append(self.time_enc(b.edata['dt']))
-        kv = torch.cat(parts_kv, dim=1) if parts_kv else torch.zeros((E, 0), device=dev)
+        if fused_te:      # [parts | time_enc] in one launch each
+            w = self.time_enc.w
+            q_in = ops.time_encode_cat(parts_q, torch.zeros(R, dtype=torch.float32, device=dev),
+                                       w.weight, w.bias)
+            kv = ops.time_encode_cat(parts_kv, b.edata['dt'], w.weight, w.bias)
+        else:
+            if self.use_time_enc:
+                parts_q.append(self.time_enc(torch.zeros(R, dtype=torch.float32, device=dev)))
+                parts_kv.append(self.time_enc(b.edata['dt']))
+            kv = torch.cat(parts_kv, dim=1) if parts_kv else torch.zeros((E, 0), device=dev)
+            q_in = torch.cat(parts_q, dim=1)
         H = self.num_head
-        q = self.w_q(torch.cat(parts_q, dim=1)).reshape(R, H, -1)
+        q = self.w_q(q_in).reshape(R, H, -1)
         k = self.w_k(kv).reshape(E, H, -1)
         v = self.w_v(kv).reshape(E, H, -1)
         if self.fused_attention and (self.att_dropout.p == 0 or not self.training):
@@ -250,3 +275,57 @@ class TemporalAttentionLayer(nn.Module):
 
 
 TransfomerAttentionLayer = TemporalAttentionLayer      # the reference's own spelling
+
+
+class GRUMemoryUpdater(nn.Module):
+    """TGN's GRU memory updater over a block prepared by Memory.prepare_input (reads
+    b.srcdata['ts', 'mem_ts', 'mem_input', 'mem', 'ID'], and 'h' when dim_node > 0):
+
+        updated = GRUCell([mem_input | time_enc(ts - mem_ts)], mem)
+        b.srcdata['h'] = h + updated                      dim_node == dim_embed
+                         updated + node_feat_proj(h)      other dim_node > 0
+                         updated                          no node features
+
+    Returns {'last_updated_nid', 'last_updated_memory', 'last_updated_ts'} of the first
+    num_dst_nodes rows as detached clones, the arguments of Memory.update_mem_mail.  Unlike the
+    reference it leaves b.srcdata['mem_input'] as prepare_input wrote it.  With
+    `fused_time_encode` the GRU input is one ops.time_encode_cat call."""
+
+    def __init__(self, dim_node: int, dim_edge: int, dim_time: int, dim_embed: int,
+                 dim_memory: int):
+        super().__init__()
+        self.dim_message = 2 * dim_memory + dim_edge
+        self.dim_node, self.dim_time, self.dim_embed = dim_node, dim_time, dim_embed
+        self.updater = nn.GRUCell(self.dim_message + dim_time, dim_memory)
+        self.use_time_enc = dim_time > 0
+        if self.use_time_enc:
+            self.time_enc = TimeEncode(dim_time)
+        if dim_node > 0 and dim_node != dim_memory:
+            self.node_feat_proj = nn.Linear(dim_node, dim_memory)
+        # False: time_enc + torch.cat instead of ops.time_encode_cat (not part of the state)
+        self.fused_time_encode = FUSED_TIME_ENCODE_DEFAULT
+
+    def forward(self, b):
+        x = b.srcdata['mem_input']
+        if self.use_time_enc:
+            dt = b.srcdata['ts'] - b.srcdata['mem_ts']
+            if self.fused_time_encode:
+                x = ops.time_encode_cat((x,), dt, self.time_enc.w.weight, self.time_enc.w.bias)
+            else:
+                x = torch.cat([x, self.time_enc(dt)], dim=1)
+        updated = self.updater(x, b.srcdata['mem'])
+        R = b.num_dst_nodes()
+        last = {"last_updated_nid": b.srcdata['ID'][:R].detach().clone(),
+                "last_updated_memory": updated[:R].detach().clone(),
+                "last_updated_ts": b.srcdata['ts'][:R].detach().clone()}
+        if self.dim_node > 0:
+            if self.dim_node == self.dim_embed:
+                b.srcdata['h'] = b.srcdata['h'] + updated
+            else:
+                b.srcdata['h'] = updated + self.node_feat_proj(b.srcdata['h'])
+        else:
+            b.srcdata['h'] = updated
+        return last
+
+
+GRUMemeoryUpdater = GRUMemoryUpdater                   # the reference's own spelling

@@ -5,6 +5,8 @@ make on a sampled block, on HIP segment kernels (csrc/block_ops.hip) with autogr
     block.update_all(fn.copy_src('v','m'), fn.sum('m','h'))          (layers.py:159)
     copy_u / u_mul_e messages, sum / mean reducers                   (dgl.nn.SAGEConv / GATConv)
     block_attention(block, q, k, v)        layers.py:144-159 in one launch (csrc/block_attention.hip)
+    time_encode_cat(parts, t, w, b)        torch.cat([*parts, TimeEncode(t)], 1) in one launch
+                                           (layers.py:16-42, 118-137; csrc/time_encode.hip)
 
 A block's edges are grouped by destination (the sampler emits them that way); blocks built by
 hand with unordered edges are handled through a stable permutation.
@@ -240,6 +242,112 @@ def block_attention(block, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     if perm is not None:
         att = torch.empty_like(att).index_copy(0, perm, att)
     return out, att
+
+
+class _TimeEncodeCat(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, t, weight, bias, *parts):
+        # t [n], weight / bias [T], parts: contiguous [n, W] with W > 0; all fp32 on one device
+        n, T = t.shape[0], bias.shape[0]
+        widths = [p.shape[1] for p in parts]
+        out = torch.empty((n, sum(widths) + T), dtype=torch.float32, device=t.device)
+        if n:
+            a, b = (list(parts) + [None, None])[:2]
+            wa, wb = (widths + [0, 0])[:2]
+            with torch.cuda.device(t.device):
+                _capi.check(_capi.load().gf_time_encode_cat(
+                    _ptr(a), wa, _ptr(b), wb, t.data_ptr(), weight.data_ptr(), bias.data_ptr(),
+                    n, T, out.data_ptr(), t.device.index, _stream(t.device)))
+        ctx.save_for_backward(t, weight, bias)
+        ctx.widths = widths
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        t, weight, bias = ctx.saved_tensors
+        n, T = t.shape[0], bias.shape[0]
+        g = _f32(grad)
+        need_w, need_b = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        gw = gb = None
+        if need_w or need_b:
+            # n == 0: zeros, and nothing to launch
+            gw = torch.zeros_like(weight) if need_w else None
+            gb = torch.zeros_like(bias) if need_b else None
+            if n:
+                lib = _capi.load()
+                rows = C.c_size_t(0)
+                _capi.check(lib.gf_time_encode_backward_partial_rows(n, C.byref(rows)))
+                partials = torch.empty((rows.value, 2, T), dtype=torch.float32, device=t.device)
+                with torch.cuda.device(t.device):
+                    _capi.check(lib.gf_time_encode_backward(
+                        t.data_ptr(), weight.data_ptr(), bias.data_ptr(), n, T, g.data_ptr(),
+                        g.shape[1], sum(ctx.widths), partials.data_ptr(), rows.value,
+                        _ptr(gw), _ptr(gb), t.device.index, _stream(t.device)))
+        gparts, off = [], 0
+        for k, w in enumerate(ctx.widths):      # column slices of grad: views, no kernel
+            gparts.append(g[:, off:off + w] if ctx.needs_input_grad[3 + k] else None)
+            off += w
+        return (None, gw, gb) + tuple(gparts)      # no gradient flows to t
+
+
+def _time_encode_cat(parts, t, weight, bias):
+    """time_encode_cat: checks every argument, then the kernel."""
+    parts = tuple(parts)
+    if len(parts) > 2:
+        raise ValueError("time_encode_cat takes at most two parts, got {}".format(len(parts)))
+    for name, x in (("t", t), ("weight", weight), ("bias", bias)) + \
+            tuple(("parts[{}]".format(i), p) for i, p in enumerate(parts)):
+        if not isinstance(x, torch.Tensor):
+            raise TypeError("{} must be a tensor, got {}".format(name, type(x).__name__))
+        if x.dtype != torch.float32:
+            raise TypeError("time_encode_cat computes in float32, {} is {}".format(name, x.dtype))
+    if t.dim() == 2 and t.shape[1] == 1:
+        t = t.reshape(-1)
+    if t.dim() != 1:
+        raise ValueError("t must be [n] or [n, 1], got {}".format(tuple(t.shape)))
+    if bias.dim() != 1:
+        raise ValueError("bias must be [T], got {}".format(tuple(bias.shape)))
+    T = int(bias.shape[0])
+    if T == 0:
+        raise ValueError("time_encode_cat needs T >= 1")
+    if tuple(weight.shape) not in ((T, 1), (T,)):
+        raise ValueError("weight must be [T, 1] or [T] with T = {}, got {}".format(
+            T, tuple(weight.shape)))
+    n = int(t.shape[0])
+    for i, p in enumerate(parts):
+        if p.dim() != 2:
+            raise ValueError("parts[{}] must be [n, W], got {}".format(i, tuple(p.shape)))
+        if p.shape[0] != n:
+            raise ValueError("parts[{}] has {} rows, t has {}".format(i, p.shape[0], n))
+    for name, x in (("weight", weight), ("bias", bias)) + \
+            tuple(("parts[{}]".format(i), p) for i, p in enumerate(parts)):
+        if x.device != t.device:
+            raise ValueError("{} is on {}, t on {}".format(name, x.device, t.device))
+    if t.device.type != "cuda":
+        raise ValueError("time_encode_cat runs on the GPU, the inputs are on {}".format(t.device))
+    # a part without columns adds nothing to the row (and has no address to hand over)
+    parts = tuple(p.contiguous() for p in parts if p.shape[1])
+    return _TimeEncodeCat.apply(t.detach().contiguous(), weight.reshape(T).contiguous(),
+                                bias.contiguous(), *parts)
+
+
+def time_encode_cat(parts, t: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor):
+    """torch.cat([*parts, torch.cos(t[:, None] * weight.T + bias)], dim=1) in one kernel: the
+    input rows every temporal layer of the reference builds (layers.py:118-137,
+    memory_updater.py:62-65).
+
+    parts: a sequence of 0, 1 or 2 float32 tensors [n, W] (row slices such as h[R:] are taken
+    as they are; any other non-contiguous part is copied first); t: [n] or [n, 1]; weight:
+    [T, 1] or [T] (TimeEncode.w.weight); bias: [T]; all float32 on one GPU.  Returns
+    [n, sum(W) + T].  Differentiable in parts, weight and bias; t gets no gradient (the
+    reference never asks for one).  The gradients of weight and bias are summed in a fixed
+    order: bit-identical from run to run."""
+    return _time_encode_cat(parts, t, weight, bias)
+
+
+def time_encode(t: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """cos(t[:, None] * weight.T + bias): time_encode_cat without parts, [n, T]."""
+    return _time_encode_cat((), t, weight, bias)
 
 
 def block_max(block, src: torch.Tensor) -> torch.Tensor:

@@ -797,6 +797,33 @@ GF_API int gf_block_attention_backward(const int64_t* d_offsets, size_t num_dst,
                                        float* d_grad_k, float* d_grad_v, int device,
                                        void* stream);
 
+/* Fused time encoding (the reference's TimeEncode, layers.py:16-42, and the torch.cat around
+ * it): d_out [n, width_a + width_b + dim_time], row-major and contiguous,
+ *   out[i, 0:width_a]                = a[i, :]      (width_a may be 0, d_a NULL)
+ *   out[i, width_a:width_a+width_b]  = b[i, :]      (width_b may be 0, d_b NULL)
+ *   out[i, width_a+width_b+j]        = cosf(w[j] * t[i] + bias[j]),  j < dim_time
+ * in one launch, every element written exactly once; d_a / d_b are contiguous [n, width].
+ * dim_time >= 1 and fewer than 2^32 output elements, else GF_ERR_INVALID_ARGUMENT; n == 0
+ * launches nothing. */
+GF_API int gf_time_encode_cat(const float* d_a, size_t width_a, const float* d_b, size_t width_b,
+                              const float* d_t, const float* d_w, const float* d_bias, size_t n,
+                              size_t dim_time, float* d_out, int device, void* stream);
+/* Rows of the caller-owned partials buffer gf_time_encode_backward needs for n input rows
+ * (at most 1024 whatever n is): the buffer holds rows * 2 * dim_time floats. */
+GF_API int gf_time_encode_backward_partial_rows(size_t n, size_t* rows);
+/* Gradients of w and bias from the time columns g[i, j] = d_grad_out[i * grad_pitch + grad_col + j]
+ * (read in place; grad_col + dim_time <= grad_pitch):
+ *   grad_w[j]    = - sum_i g[i,j] * sinf(w[j] * t[i] + bias[j]) * t[i]
+ *   grad_bias[j] = - sum_i g[i,j] * sinf(w[j] * t[i] + bias[j])
+ * summed in a fixed order without atomics (bit-identical from run to run).  d_grad_w or
+ * d_grad_bias may be NULL (skipped).  There is no gradient for t.  The gradients of a and b
+ * are the column slices of grad_out and need no call. */
+GF_API int gf_time_encode_backward(const float* d_t, const float* d_w, const float* d_bias,
+                                   size_t n, size_t dim_time, const float* d_grad_out,
+                                   size_t grad_pitch, size_t grad_col, float* d_partials,
+                                   size_t partial_rows, float* d_grad_w, float* d_grad_bias,
+                                   int device, void* stream);
+
 /* ---- measurement support (bench.py) ---------------------------------------- */
 /* Accumulated device time of a kernel family since the last reset, measured with
  * HIP events recorded around each launch on the launching stream.
