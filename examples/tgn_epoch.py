@@ -74,11 +74,14 @@ class MemoryUpdater(nn.Module):
 class Attention(nn.Module):
     """One multi-head attention layer over a sampled block: queries from the destination
     nodes (zero time encoding), keys / values from the sampled neighbours with the time
-    encoding of the edge's age; softmax over each destination's in-edges, weighted sum."""
+    encoding of the edge's age; softmax over each destination's in-edges, weighted sum.
+    att_dropout > 0: in training the attention is one ops.block_attention call with the dropout
+    on the attention weights inside it (a seed per forward from torch's CPU generator)."""
 
-    def __init__(self, dim_node, dim_time, dim_out, heads):
+    def __init__(self, dim_node, dim_time, dim_out, heads, att_dropout=0.0):
         super().__init__()
         self.heads = heads
+        self.att_dropout = att_dropout
         self.time = TimeEncoding(dim_time)
         self.q = nn.Linear(dim_node + dim_time, dim_out)
         self.k = nn.Linear(dim_node + dim_time, dim_out)
@@ -94,10 +97,16 @@ class Attention(nn.Module):
             return torch.zeros((R, self.dim_out), device=h.device)
         dst_h, src_h = h[:R], h[R:]
         row = b.edges()[1]
-        q = self.q(torch.cat([dst_h, self.time(torch.zeros(R, device=h.device))], 1))[row]
+        q = self.q(torch.cat([dst_h, self.time(torch.zeros(R, device=h.device))], 1))
         kv_in = torch.cat([src_h, self.time(b.edata['dt'])], 1)
         k, v = self.k(kv_in), self.v(kv_in)
         H = self.heads
+        if self.att_dropout > 0 and self.training:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64))
+            agg = ops.block_attention(b, q, k, v, heads=H, dropout_p=self.att_dropout,
+                                      dropout_seed=seed).reshape(R, -1)
+            return self.norm(F.relu(self.out(torch.cat([agg, dst_h], 1))))
+        q = q[row]
         score = F.leaky_relu((q.view(E, H, -1) * k.view(E, H, -1)).sum(2), 0.2)
         att = ops.edge_softmax(b, score)                       # [E, H]
         msg = (v.view(E, H, -1) * att[:, :, None]).reshape(E, -1)
@@ -118,10 +127,11 @@ class EdgeScorer(nn.Module):
 
 
 class TGN(nn.Module):
-    def __init__(self, dim_node, dim_time=100, dim_embed=100, dim_memory=100, heads=2):
+    def __init__(self, dim_node, dim_time=100, dim_embed=100, dim_memory=100, heads=2,
+                 att_dropout=0.0):
         super().__init__()
         self.updater = MemoryUpdater(dim_node, 0, dim_time, dim_memory)
-        self.att = Attention(dim_memory, dim_time, dim_embed, heads)
+        self.att = Attention(dim_memory, dim_time, dim_embed, heads, att_dropout)
         self.score = EdgeScorer(dim_embed)
 
     def forward(self, mfgs):
@@ -137,6 +147,8 @@ def main():
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--train-frac", type=float, default=0.7)
     ap.add_argument("--max-batches", type=int, default=0)
+    ap.add_argument("--att-dropout", type=float, default=0.0,
+                    help="attention dropout, inside ops.block_attention (0: none, the default run)")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
@@ -154,7 +166,7 @@ def main():
     node_feats = torch.rand((N, args.dim_node), device=dev)
     cache = LRUCache(0.0, 0.2, N, E, dev, node_feats, None, args.dim_node, 0)
     cache.init_cache()
-    model = TGN(args.dim_node).to(dev)
+    model = TGN(args.dim_node, att_dropout=args.att_dropout).to(dev)
     memory = Memory(N, 0, 100, dev)
     opt = torch.optim.Adam(model.parameters(), lr=1e-4)
     n_train = int(E * args.train_frac)
@@ -242,7 +254,8 @@ def main():
         "stages": "host wall time per stage as scripts/offline_edge_prediction.py:403-454 "
                   "accumulates it (stages are asynchronous: GPU time shows up where the host "
                   "next waits — mostly in `model`, whose loss read-back synchronises)",
-        "graph_build_s": round(build_s, 2), "epochs": out}))
+        "graph_build_s": round(build_s, 2), "epochs": out,
+        **({"att_dropout": args.att_dropout} if args.att_dropout else {})}))
 
 
 if __name__ == "__main__":

@@ -22,8 +22,23 @@
 // Softmax: TWO PASSES over the scores, which are parked in att[] itself.  Score i of a segment
 // is written, read back and finally replaced by a[i] by the same lane (i mod G) of the same
 // group, so no fence is needed; k and v are each read exactly once by the forward.
+//
+// Attention dropout (the *_dropout kernels; the reference drops the attention weights after the
+// softmax, layers.py:153-155) needs no mask tensor: edge i of the grouped order and head h are
+//   kept  <=>  gf_philox4x32_10_first(seed, i * H + h, 0) >= T,   T = (uint32_t)(p * 2^32)
+//   w[i,h] = kept ? 1 / (1 - p) : 0          out[d,h,:] = sum_i (a[i,h] * w[i,h]) * v[i,h,:]
+// a decision per (edge, head), hence uniform over the group that owns the head.  The lane that
+// computes a[i] draws the decision, so the forward costs one Philox per (edge, head); the
+// backward draws it again the same way (G edges at a time, one per lane, handed round the group)
+// instead of reading a stored mask.  att[] keeps the PRE-dropout a -- the softmax Jacobian needs
+// it -- and a * w goes to a second, optional buffer.  A dropped edge contributes exactly 0 and
+// its v row is NOT READ, forward or backward: a non-finite v on a dropped edge does not
+// propagate, unlike 0 * inf = NaN in the composed edge_softmax -> dropout -> block_reduce chain.
+// The kernels without dropout are kept as they were and compile to the code they had before
+// dropout existed.
 #include "block_ops.hpp"
 #include "common.hpp"
+#include "../../include/gnnflow_rng.h"
 
 #include <cfloat>
 #include <cstdint>
@@ -72,6 +87,17 @@ __device__ inline void load_head(float (&a)[NC], const float* __restrict__ row, 
 }
 
 __device__ inline float leaky(float z, float slope) { return z > 0.f ? z : slope * z; }
+
+// what the dropout kernels need besides the attention's own arguments
+struct Dropout {
+  uint32_t threshold;   // T: kept <=> philox >= T
+  float scale;          // 1 / (1 - p)
+  uint64_t seed;
+};
+
+__device__ inline bool kept(const Dropout& dr, uint64_t edge, uint32_t H, uint32_t h) {
+  return gf_philox4x32_10_first(dr.seed, edge * H + h, 0) >= dr.threshold;
+}
 
 template <int G, int NC>
 __global__ void block_attention_fwd(const int64_t* __restrict__ offsets, uint64_t items,
@@ -122,6 +148,76 @@ __global__ void block_attention_fwd(const int64_t* __restrict__ offsets, uint64_
     const int n = static_cast<int>(e - base < G ? e - base : G);
     for (int t = 0; t < n; ++t) {
       const float at = group_read<G>(a, t);
+      const float* vr = v + (base + t) * width + static_cast<uint64_t>(h) * D;
+#pragma unroll
+      for (int j = 0; j < NC; ++j) {
+        const uint32_t c = lig + G * j;
+        if (c < D) acc[j] += at * vr[c];
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NC; ++j)
+    if (lig + G * j < D) out_row[lig + G * j] = acc[j];
+}
+
+// The forward with dropout: block_attention_fwd with the mask applied in pass 2b.  The lane
+// that owns a[i] replaces its copy by a * w, or by -1 for a dropped edge (a * w is never
+// negative), so still one value per edge goes round the group.  A kernel of its own rather than
+// a template flag on block_attention_fwd: a shared body changed the register allocation of the
+// NC > 1 instantiations without dropout.
+template <int G, int NC>
+__global__ void block_attention_dropout_fwd(
+    const int64_t* __restrict__ offsets, uint64_t items, uint32_t H, uint32_t D,
+    const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+    float slope, Dropout dr, float* __restrict__ out, float* att,
+    float* __restrict__ att_dropped) {
+  const uint32_t lig = threadIdx.x & (G - 1);
+  const uint64_t w = (static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / G;
+  if (w >= items) return;                     // group-uniform
+  const uint64_t d = w / H;
+  const uint32_t h = static_cast<uint32_t>(w - d * H);
+  const int64_t b = offsets[d], e = offsets[d + 1];
+  const uint64_t width = static_cast<uint64_t>(H) * D;
+  float* out_row = out + d * width + static_cast<uint64_t>(h) * D;
+  if (e <= b) {                               // no in-edges: exactly 0
+#pragma unroll
+    for (int j = 0; j < NC; ++j)
+      if (lig + G * j < D) out_row[lig + G * j] = 0.f;
+    return;
+  }
+  float qr[NC];
+  load_head<G, NC>(qr, q + d * width + static_cast<uint64_t>(h) * D, D, lig);
+
+  // pass 1 (reads k once): scores into att[], running max
+  float m = -FLT_MAX;
+  for (int64_t i = b; i < e; ++i) {
+    const float s = leaky(head_dot<G, NC>(qr, k + i * width + static_cast<uint64_t>(h) * D, D, lig),
+                          slope);
+    m = fmaxf(m, s);
+    if (static_cast<uint32_t>(i - b) % G == lig) att[i * H + h] = s;
+  }
+  // pass 2a: the lane's own scores -> sum of exponentials
+  float l = 0.f;
+  for (int64_t i = b + lig; i < e; i += G) l += __expf(att[i * H + h] - m);
+  const float inv = 1.f / group_sum<G>(l);
+  // pass 2b: as above; the lane's copy of a becomes a * w, or -1 for a dropped edge
+  float acc[NC];
+#pragma unroll
+  for (int j = 0; j < NC; ++j) acc[j] = 0.f;
+  for (int64_t base = b; base < e; base += G) {
+    const int64_t mine = base + lig;
+    float a = 0.f;
+    if (mine < e) {
+      a = __expf(att[mine * H + h] - m) * inv;
+      att[mine * H + h] = a;
+      a = kept(dr, static_cast<uint64_t>(mine), H, h) ? a * dr.scale : -1.f;
+      if (att_dropped) att_dropped[mine * H + h] = a < 0.f ? 0.f : a;
+    }
+    const int n = static_cast<int>(e - base < G ? e - base : G);
+    for (int t = 0; t < n; ++t) {
+      const float at = group_read<G>(a, t);
+      if (at < 0.f) continue;                 // dropped: exactly 0, v not read (group-uniform)
       const float* vr = v + (base + t) * width + static_cast<uint64_t>(h) * D;
 #pragma unroll
       for (int j = 0; j < NC; ++j) {
@@ -209,6 +305,113 @@ __global__ void block_attention_bwd(const int64_t* __restrict__ offsets, uint64_
   }
 }
 
+// The backward with dropout.  With ga_d = gout . v and w as in the forward:
+//   gv = (a w) gout      ga = w ga_d      dot = sum_e a ga      gs = a (ga - dot)
+// and gz, gq, gk as above.  Edges are taken G at a time: lane t of the group loads a and draws
+// w for edge base + t, and both are handed round the group, so each sweep costs one Philox per
+// (edge, head) like the forward.  A dropped edge has ga = 0: its v row is not read, its gv row
+// is written as zeros, and it still takes its share -a dot of the softmax Jacobian.
+template <int G, int NC>
+__global__ void block_attention_dropout_bwd(
+    const int64_t* __restrict__ offsets, uint64_t items, uint32_t H, uint32_t D,
+    const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+    const float* __restrict__ att, float slope, Dropout dr, const float* __restrict__ gout,
+    float* __restrict__ gq, float* __restrict__ gk, float* __restrict__ gv) {
+  const uint32_t lig = threadIdx.x & (G - 1);
+  const uint64_t w = (static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / G;
+  if (w >= items) return;
+  const uint64_t d = w / H;
+  const uint32_t h = static_cast<uint32_t>(w - d * H);
+  const int64_t b = offsets[d], e = offsets[d + 1];
+  const uint64_t width = static_cast<uint64_t>(H) * D;
+  const uint64_t head = static_cast<uint64_t>(h) * D;
+  if (e <= b) {
+    if (gq) {
+#pragma unroll
+      for (int j = 0; j < NC; ++j)
+        if (lig + G * j < D) gq[d * width + head + lig + G * j] = 0.f;
+    }
+    return;
+  }
+  float gr[NC];
+  load_head<G, NC>(gr, gout + d * width + head, D, lig);
+  const bool chain = gq || gk;
+
+  // sweep 1: gv, and dot = sum a ga over the kept edges (in edge order)
+  float dot = 0.f;
+  for (int64_t base = b; base < e; base += G) {
+    const int64_t mine = base + lig;
+    float a = 0.f, wm = 0.f;
+    if (mine < e) {
+      a = att[mine * H + h];
+      wm = kept(dr, static_cast<uint64_t>(mine), H, h) ? dr.scale : 0.f;
+    }
+    const int n = static_cast<int>(e - base < G ? e - base : G);
+    for (int t = 0; t < n; ++t) {
+      const float at = group_read<G>(a, t);
+      const float wt = group_read<G>(wm, t);   // scale >= 1, so 0 means dropped
+      const int64_t i = base + t;
+      if (wt == 0.f) {
+        if (gv) {
+#pragma unroll
+          for (int j = 0; j < NC; ++j)
+            if (lig + G * j < D) gv[i * width + head + lig + G * j] = 0.f;
+        }
+        continue;
+      }
+      if (gv) {
+        const float aw = at * wt;
+#pragma unroll
+        for (int j = 0; j < NC; ++j) {
+          const uint32_t c = lig + G * j;
+          if (c < D) gv[i * width + head + c] = aw * gr[j];
+        }
+      }
+      if (chain) dot += at * (wt * head_dot<G, NC>(gr, v + i * width + head, D, lig));
+    }
+  }
+  if (!chain) return;
+
+  // sweep 2: ga again (the same head_dot, the same bits), z by the forward's own sequence
+  float qr[NC], acc[NC];
+  load_head<G, NC>(qr, q + d * width + head, D, lig);
+#pragma unroll
+  for (int j = 0; j < NC; ++j) acc[j] = 0.f;
+  for (int64_t base = b; base < e; base += G) {
+    const int64_t mine = base + lig;
+    float a = 0.f, wm = 0.f;
+    if (mine < e) {
+      a = att[mine * H + h];
+      wm = kept(dr, static_cast<uint64_t>(mine), H, h) ? dr.scale : 0.f;
+    }
+    const int n = static_cast<int>(e - base < G ? e - base : G);
+    for (int t = 0; t < n; ++t) {
+      const float at = group_read<G>(a, t);
+      const float wt = group_read<G>(wm, t);
+      const int64_t i = base + t;
+      const float* kr = k + i * width + head;
+      float ga = 0.f;
+      if (wt != 0.f) ga = wt * head_dot<G, NC>(gr, v + i * width + head, D, lig);
+      const float z = head_dot<G, NC>(qr, kr, D, lig);
+      const float gs = at * (ga - dot);
+      const float gz = z > 0.f ? gs : gs * slope;
+#pragma unroll
+      for (int j = 0; j < NC; ++j) {
+        const uint32_t c = lig + G * j;
+        if (c < D) {
+          if (gk) gk[i * width + head + c] = gz * qr[j];
+          acc[j] += gz * kr[c];
+        }
+      }
+    }
+  }
+  if (gq) {
+#pragma unroll
+    for (int j = 0; j < NC; ++j)
+      if (lig + G * j < D) gq[d * width + head + lig + G * j] = acc[j];
+  }
+}
+
 struct Shape {
   const int64_t* offsets;
   uint64_t items;
@@ -232,6 +435,26 @@ void launch_bwd(const Shape& s, const float* q, const float* k, const float* v, 
   block_attention_bwd<G, NC><<<dim3(static_cast<unsigned>((threads + kThreads - 1) / kThreads)),
                                dim3(kThreads), 0, stream>>>(s.offsets, s.items, s.H, s.D, q, k, v,
                                                             att, slope, gout, gq, gk, gv);
+}
+
+template <int G, int NC>
+void launch_dropout_fwd(const Shape& s, const float* q, const float* k, const float* v,
+                        float slope, const Dropout& dr, float* out, float* att,
+                        float* att_dropped, hipStream_t stream) {
+  const uint64_t threads = s.items * G;
+  block_attention_dropout_fwd<G, NC>
+      <<<dim3(static_cast<unsigned>((threads + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+         stream>>>(s.offsets, s.items, s.H, s.D, q, k, v, slope, dr, out, att, att_dropped);
+}
+
+template <int G, int NC>
+void launch_dropout_bwd(const Shape& s, const float* q, const float* k, const float* v,
+                        const float* att, float slope, const Dropout& dr, const float* gout,
+                        float* gq, float* gk, float* gv, hipStream_t stream) {
+  const uint64_t threads = s.items * G;
+  block_attention_dropout_bwd<G, NC>
+      <<<dim3(static_cast<unsigned>((threads + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+         stream>>>(s.offsets, s.items, s.H, s.D, q, k, v, att, slope, dr, gout, gq, gk, gv);
 }
 
 // calls f.template operator()<G, NC>() for the group size / columns per lane of a D-column head
@@ -261,6 +484,21 @@ struct Bwd {
   }
 };
 
+struct DropoutFwd {
+  Shape s; const float *q, *k, *v; float slope; Dropout dr; float *out, *att, *att_dropped;
+  hipStream_t stream;
+  template <int G, int NC> void operator()() {
+    launch_dropout_fwd<G, NC>(s, q, k, v, slope, dr, out, att, att_dropped, stream);
+  }
+};
+struct DropoutBwd {
+  Shape s; const float *q, *k, *v, *att; float slope; Dropout dr; const float* gout;
+  float *gq, *gk, *gv; hipStream_t stream;
+  template <int G, int NC> void operator()() {
+    launch_dropout_bwd<G, NC>(s, q, k, v, att, slope, dr, gout, gq, gk, gv, stream);
+  }
+};
+
 Shape checked_shape(const int64_t* d_offsets, size_t num_dst, size_t heads, size_t head_dim) {
   GF_REQUIRE(heads >= 1 && head_dim >= 1, "block_attention: heads and head_dim must be >= 1");
   GF_REQUIRE(heads <= kBlockAttentionMaxWidth && head_dim <= kBlockAttentionMaxWidth &&
@@ -272,6 +510,13 @@ Shape checked_shape(const int64_t* d_offsets, size_t num_dst, size_t heads, size
   GF_REQUIRE(num_dst <= (size_t{1} << 32) / heads, "block_attention: too many destinations");
   return Shape{d_offsets, static_cast<uint64_t>(num_dst) * heads, static_cast<uint32_t>(heads),
                static_cast<uint32_t>(head_dim)};
+}
+
+// T and 1 / (1 - p) of the mask definition (gnnflow_hip.h); p is an fp32 value in [0, 1)
+Dropout checked_dropout(float p, uint64_t seed) {
+  GF_REQUIRE(p >= 0.f && p < 1.f, "block_attention: dropout p must be in [0, 1)");   // NaN fails
+  return Dropout{static_cast<uint32_t>(static_cast<double>(p) * 4294967296.0), 1.0f / (1.0f - p),
+                 seed};
 }
 
 }  // namespace
@@ -304,6 +549,42 @@ void block_attention_backward(const int64_t* d_offsets, size_t num_dst, size_t n
   DeviceGuard dg(device);
   dispatch(s.D, Bwd{s, d_q, d_k, d_v, d_att, negative_slope, d_grad_out, d_grad_q, d_grad_k,
                     d_grad_v, stream});
+  GF_HIP(hipGetLastError());
+}
+
+void block_attention_dropout_forward(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                                     size_t heads, size_t head_dim, const float* d_q,
+                                     const float* d_k, const float* d_v, float negative_slope,
+                                     float p, uint64_t seed, float* d_out, float* d_att,
+                                     float* d_att_dropped, int device, hipStream_t stream) {
+  const Dropout dr = checked_dropout(p, seed);
+  const Shape s = checked_shape(d_offsets, num_dst, heads, head_dim);
+  if (num_dst == 0) return;
+  GF_REQUIRE(d_q && d_out, "block_attention: null q or out");
+  GF_REQUIRE(num_edges == 0 || (d_k && d_v && d_att), "block_attention: null k, v or att");
+  DeviceGuard dg(device);
+  dispatch(s.D, DropoutFwd{s, d_q, d_k, d_v, negative_slope, dr, d_out, d_att, d_att_dropped,
+                           stream});
+  GF_HIP(hipGetLastError());
+}
+
+void block_attention_dropout_backward(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                                      size_t heads, size_t head_dim, const float* d_q,
+                                      const float* d_k, const float* d_v, const float* d_att,
+                                      float negative_slope, float p, uint64_t seed,
+                                      const float* d_grad_out, float* d_grad_q, float* d_grad_k,
+                                      float* d_grad_v, int device, hipStream_t stream) {
+  const Dropout dr = checked_dropout(p, seed);
+  const Shape s = checked_shape(d_offsets, num_dst, heads, head_dim);
+  if (num_dst == 0 || (!d_grad_q && !d_grad_k && !d_grad_v)) return;
+  GF_REQUIRE(d_grad_out != nullptr, "block_attention backward: null gradient");
+  GF_REQUIRE(num_edges == 0 || (d_att && d_v), "block_attention backward: null att or v");
+  GF_REQUIRE(num_edges == 0 || (!d_grad_q && !d_grad_k) || (d_q && d_k),
+             "block_attention backward: grad_q / grad_k need q and k");
+  if (num_edges == 0 && !d_grad_q) return;
+  DeviceGuard dg(device);
+  dispatch(s.D, DropoutBwd{s, d_q, d_k, d_v, d_att, negative_slope, dr, d_grad_out, d_grad_q,
+                           d_grad_k, d_grad_v, stream});
   GF_HIP(hipGetLastError());
 }
 

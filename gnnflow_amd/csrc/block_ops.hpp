@@ -41,6 +41,21 @@ void block_attention_backward(const int64_t* d_offsets, size_t num_dst, size_t n
                               const float* d_v, const float* d_att, float negative_slope,
                               const float* d_grad_out, float* d_grad_q, float* d_grad_k,
                               float* d_grad_v, int device, hipStream_t stream);
+// The same with attention dropout: edge i of the grouped order and head h are kept when
+// gf_philox4x32_10_first(seed, i * heads + h, 0) >= (uint32_t)(p * 2^32), and a kept weight is
+// scaled by 1 / (1 - p).  p outside [0, 1) throws GF_ERR_INVALID_ARGUMENT.  d_att is the
+// pre-dropout softmax; d_att_dropped (may be null) receives the weights that multiplied v.
+void block_attention_dropout_forward(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                                     size_t heads, size_t head_dim, const float* d_q,
+                                     const float* d_k, const float* d_v, float negative_slope,
+                                     float p, uint64_t seed, float* d_out, float* d_att,
+                                     float* d_att_dropped, int device, hipStream_t stream);
+void block_attention_dropout_backward(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                                      size_t heads, size_t head_dim, const float* d_q,
+                                      const float* d_k, const float* d_v, const float* d_att,
+                                      float negative_slope, float p, uint64_t seed,
+                                      const float* d_grad_out, float* d_grad_q, float* d_grad_k,
+                                      float* d_grad_v, int device, hipStream_t stream);
 
 // time_encode.hip: out = [a | b | cosf(w * t + bias)] in one launch (a / b may be null with
 // width 0), and the gradients of w and bias from the time columns of grad_out, read in place

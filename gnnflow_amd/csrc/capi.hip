@@ -1355,6 +1355,31 @@ int gf_block_attention_backward(const int64_t* d_offsets, size_t num_dst, size_t
                                  device, static_cast<hipStream_t>(stream));
   });
 }
+int gf_block_attention_dropout(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                               size_t heads, size_t head_dim, const float* d_q, const float* d_k,
+                               const float* d_v, float negative_slope, float p, uint64_t seed,
+                               float* d_out, float* d_att, float* d_att_dropped, int device,
+                               void* stream) {
+  return guarded([&] {
+    gf::block_attention_dropout_forward(d_offsets, num_dst, num_edges, heads, head_dim, d_q, d_k,
+                                        d_v, negative_slope, p, seed, d_out, d_att,
+                                        d_att_dropped, device, static_cast<hipStream_t>(stream));
+  });
+}
+int gf_block_attention_dropout_backward(const int64_t* d_offsets, size_t num_dst,
+                                        size_t num_edges, size_t heads, size_t head_dim,
+                                        const float* d_q, const float* d_k, const float* d_v,
+                                        const float* d_att, float negative_slope, float p,
+                                        uint64_t seed, const float* d_grad_out, float* d_grad_q,
+                                        float* d_grad_k, float* d_grad_v, int device,
+                                        void* stream) {
+  return guarded([&] {
+    gf::block_attention_dropout_backward(d_offsets, num_dst, num_edges, heads, head_dim, d_q, d_k,
+                                         d_v, d_att, negative_slope, p, seed, d_grad_out,
+                                         d_grad_q, d_grad_k, d_grad_v, device,
+                                         static_cast<hipStream_t>(stream));
+  });
+}
 
 int gf_time_encode_cat(const float* d_a, size_t width_a, const float* d_b, size_t width_b,
                        const float* d_t, const float* d_w, const float* d_bias, size_t n,

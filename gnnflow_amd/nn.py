@@ -170,6 +170,12 @@ class GATConv(nn.Module):
 # that has not been measured yet.
 FUSED_TIME_ENCODE_DEFAULT = False
 
+# Default of `fused_attention_dropout` in TemporalAttentionLayer.  True only once
+# scripts/block_attention_bench.py --dropout 0.2 has shown the fused op, forward + backward, ahead
+# of the composed chain at both of its shapes by more than the chain's own round-to-round spread
+# (profiles/block_attention_bench.jsonl).
+FUSED_ATTENTION_DROPOUT_DEFAULT = False
+
 
 class TimeEncode(nn.Module):
     """TGAT's time encoding cos(w * dt + b): w = 1 / 10^linspace(0, 9, dim_time), b = 0 at
@@ -203,7 +209,11 @@ class TemporalAttentionLayer(nn.Module):
     alone, or a row of ones (and w_q the identity) without a time encoding either.  With
     attention dropout inactive (p = 0 or eval mode) the attention is one ops.block_attention
     call; otherwise edge_softmax -> dropout -> block_reduce, so that dropout acts on the
-    attention weights as in the reference.  With `fused_time_encode` the rows [h_src | f |
+    attention weights as in the reference.  With `fused_attention_dropout` (and
+    `fused_attention`) training with 0 < att_dropout.p < 1 is one ops.block_attention call too:
+    the dropout happens inside the kernels, from the op's stateless Philox mask, with a seed
+    drawn per forward from torch's default CPU generator (no device sync; reproducible under
+    torch.manual_seed, but not the mask torch's own dropout would draw).  With `fused_time_encode` the rows [h_src | f |
     time_enc(dt)] and [h_dst | time_enc(0)] are one ops.time_encode_cat call each."""
 
     def __init__(self, dim_node: int, dim_edge: int, dim_time: int, dim_out: int, num_head: int,
@@ -229,6 +239,8 @@ class TemporalAttentionLayer(nn.Module):
         self.layer_norm = nn.LayerNorm(dim_out)
         # False: always the composed edge_softmax -> block_reduce chain (not part of the state)
         self.fused_attention = True
+        # True: attention dropout in training inside ops.block_attention (not part of the state)
+        self.fused_attention_dropout = FUSED_ATTENTION_DROPOUT_DEFAULT
         # False: time_enc + torch.cat instead of ops.time_encode_cat (not part of the state)
         self.fused_time_encode = FUSED_TIME_ENCODE_DEFAULT
 
@@ -262,8 +274,13 @@ class TemporalAttentionLayer(nn.Module):
         q = self.w_q(q_in).reshape(R, H, -1)
         k = self.w_k(kv).reshape(E, H, -1)
         v = self.w_v(kv).reshape(E, H, -1)
-        if self.fused_attention and (self.att_dropout.p == 0 or not self.training):
+        p = self.att_dropout.p
+        if self.fused_attention and (p == 0 or not self.training):
             agg = ops.block_attention(b, q, k, v, negative_slope=self.att_act.negative_slope)
+        elif self.fused_attention and self.fused_attention_dropout and 0 < p < 1:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64))
+            agg = ops.block_attention(b, q, k, v, negative_slope=self.att_act.negative_slope,
+                                      dropout_p=p, dropout_seed=seed)
         else:
             row = b.edges()[1]
             att = ops.edge_softmax(b, self.att_act((q[row] * k).sum(dim=2)))

@@ -5,6 +5,8 @@ make on a sampled block, on HIP segment kernels (csrc/block_ops.hip) with autogr
     block.update_all(fn.copy_src('v','m'), fn.sum('m','h'))          (layers.py:159)
     copy_u / u_mul_e messages, sum / mean reducers                   (dgl.nn.SAGEConv / GATConv)
     block_attention(block, q, k, v)        layers.py:144-159 in one launch (csrc/block_attention.hip)
+      ... dropout_p=, dropout_seed=        with the attention dropout of layers.py:155 inside it, from a
+                                           stateless Philox mask (no mask tensor, reproducible on the CPU)
     time_encode_cat(parts, t, w, b)        torch.cat([*parts, TimeEncode(t)], 1) in one launch
                                            (layers.py:16-42, 118-137; csrc/time_encode.hip)
 
@@ -12,6 +14,7 @@ A block's edges are grouped by destination (the sampler emits them that way); bl
 hand with unordered edges are handled through a stable permutation.
 """
 import ctypes as C
+from typing import Optional
 
 import torch
 
@@ -176,6 +179,45 @@ class _BlockAttention(torch.autograd.Function):
         return gq, gk, gv, None, None, None
 
 
+class _BlockAttentionDropout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, offsets, num_dst, slope, p, seed, want_dropped):
+        # as _BlockAttention; att is the pre-dropout softmax (saved), dropped = att * w
+        E, H, D = k.shape
+        out = torch.empty((num_dst, H, D), dtype=torch.float32, device=q.device)
+        att = torch.empty((E, H), dtype=torch.float32, device=q.device)
+        dropped = torch.empty_like(att) if want_dropped else None
+        with torch.cuda.device(q.device):
+            _capi.check(_capi.load().gf_block_attention_dropout(
+                offsets.data_ptr(), num_dst, E, H, D, q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                slope, p, seed, out.data_ptr(), att.data_ptr(), _ptr(dropped), q.device.index,
+                _stream(q.device)))
+        ctx.save_for_backward(q, k, v, att, offsets)
+        ctx.meta = (slope, p, seed)
+        if dropped is None:
+            return out, None
+        ctx.mark_non_differentiable(dropped)
+        return out, dropped
+
+    @staticmethod
+    def backward(ctx, grad, _grad_dropped):
+        q, k, v, att, offsets = ctx.saved_tensors
+        slope, p, seed = ctx.meta
+        g = _f32(grad)
+        E, H, D = k.shape
+        need_q, need_k, need_v = ctx.needs_input_grad[:3]
+        gq = torch.empty_like(q) if need_q else None
+        gk = torch.empty_like(k) if need_k else None
+        gv = torch.empty_like(v) if need_v else None
+        if need_q or need_k or need_v:
+            with torch.cuda.device(q.device):
+                _capi.check(_capi.load().gf_block_attention_dropout_backward(
+                    offsets.data_ptr(), q.shape[0], E, H, D, q.data_ptr(), k.data_ptr(),
+                    v.data_ptr(), att.data_ptr(), slope, p, seed, g.data_ptr(), _ptr(gq),
+                    _ptr(gk), _ptr(gv), q.device.index, _stream(q.device)))
+        return gq, gk, gv, None, None, None, None, None, None
+
+
 class _NoEdgeAttention(torch.autograd.Function):
     """A block without edges or without destinations: zeros, and zero gradients."""
     @staticmethod
@@ -190,7 +232,8 @@ class _NoEdgeAttention(torch.autograd.Function):
 
 
 def block_attention(block, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
-                    negative_slope: float = 0.2, return_attention: bool = False, heads=None):
+                    negative_slope: float = 0.2, return_attention: bool = False, heads=None,
+                    dropout_p: float = 0.0, dropout_seed: Optional[int] = None):
     """The attention of the reference's TransfomerAttentionLayer (layers.py:144-159) with
     per-edge keys and values, in one kernel each way:
 
@@ -200,7 +243,37 @@ def block_attention(block, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     q: [num_dst_nodes, H, D]; k, v: [num_edges, H, D], float32.  The inputs are 3-D; a 2-D
     [rows, H * D] input is accepted only together with `heads=H`.  H * D is at most
     MAX_ATTENTION_WIDTH.  Returns out [num_dst_nodes, H, D], and with return_attention=True
-    also att [num_edges, H] in the caller's edge order (not differentiable)."""
+    also att [num_edges, H] in the caller's edge order (not differentiable).
+
+    dropout_p > 0 drops attention weights after the softmax (the reference's att_dropout,
+    layers.py:155) inside the same kernels, from a stateless mask that is never stored and that
+    the backward draws again.  With p = float32(dropout_p), 0 <= p < 1, and i the position of an
+    edge in the GROUPED order the kernel sees -- the order of block.segments(): the caller's
+    order for a sampler block, the stable sort by destination (`perm`) for an unordered one --
+
+        T          = uint32(float64(p) * 2**32)
+        keep[i, h] = gf_philox4x32_10_first(dropout_seed, i * H + h, 0) >= T   (gnnflow_rng.h)
+        w[i, h]    = float32(1) / (float32(1) - p) if keep[i, h] else 0
+        out[d, h]  = sum over the edges i into d of (att[i, h] * w[i, h]) * v[i, h]
+
+    dropout_seed (0 <= seed < 2**64) is required when dropout_p > 0; the same seed gives the
+    same mask and the same bits.  return_attention=True then returns the DROPPED attention
+    att * w, the weights that multiplied v (caller's edge order, not differentiable).  A dropped
+    edge contributes exactly 0 and its v row is not read: a non-finite v on a dropped edge does
+    not propagate, unlike 0 * inf in the composed edge_softmax -> dropout -> block_reduce chain.
+    dropout_p == 0 is the call without the two arguments, bit for bit."""
+    dropout_p = float(dropout_p)
+    if not 0.0 <= dropout_p < 1.0:          # NaN fails too
+        raise ValueError("dropout_p must be in [0, 1), got {}".format(dropout_p))
+    p32 = C.c_float(dropout_p).value        # the fp32 value the kernels see
+    if p32 >= 1.0:
+        raise ValueError("dropout_p rounds to 1 in float32")
+    if dropout_seed is not None:
+        dropout_seed = int(dropout_seed)
+        if not 0 <= dropout_seed < 2 ** 64:
+            raise ValueError("dropout_seed must be in [0, 2**64), got {}".format(dropout_seed))
+    elif dropout_p > 0:
+        raise ValueError("dropout_p > 0 needs a dropout_seed")
     num_dst, E = block.num_dst_nodes(), block.num_edges()
     q, k, v = _f32(q), _f32(k), _f32(v)
     if q.shape[0] != num_dst:
@@ -236,7 +309,11 @@ def block_attention(block, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     offsets, _, perm = block.segments()
     if perm is not None:
         k, v = k[perm], v[perm]
-    out, att = _BlockAttention.apply(q, k, v, offsets, num_dst, float(negative_slope))
+    if p32 > 0:
+        out, att = _BlockAttentionDropout.apply(q, k, v, offsets, num_dst, float(negative_slope),
+                                                p32, dropout_seed, bool(return_attention))
+    else:
+        out, att = _BlockAttention.apply(q, k, v, offsets, num_dst, float(negative_slope))
     if not return_attention:
         return out
     if perm is not None:

@@ -796,6 +796,32 @@ GF_API int gf_block_attention_backward(const int64_t* d_offsets, size_t num_dst,
                                        const float* d_grad_out, float* d_grad_q,
                                        float* d_grad_k, float* d_grad_v, int device,
                                        void* stream);
+/* gf_block_attention with dropout on the attention weights (after the softmax, as the reference's
+ * att_dropout, layers.py:153-155), from a stateless mask: with i the position of an edge in the
+ * grouped order of d_offsets and p an fp32 value in [0, 1),
+ *   T         = (uint32_t)((double)p * 4294967296.0)
+ *   keep[i,h] = gf_philox4x32_10_first(seed, i * heads + h, 0) >= T        (gnnflow_rng.h)
+ *   w[i,h]    = keep ? 1.0f / (1.0f - p) : 0
+ *   out[d,h,:] = sum over the edges i of d of (att[i,h] * w[i,h]) * v[i,h,:]
+ * d_att receives the PRE-dropout softmax (what the backward needs); d_att_dropped, unless NULL,
+ * receives att * w [num_edges, heads].  A dropped edge contributes exactly 0 and its v row is not
+ * read, so a non-finite v there does not propagate.  p outside [0, 1) or NaN:
+ * GF_ERR_INVALID_ARGUMENT; p == 0 gives the bits of gf_block_attention.  The backward draws the
+ * mask again from (p, seed): nothing else is stored.  gv rows of dropped edges are exact zeros;
+ * otherwise as gf_block_attention_backward. */
+GF_API int gf_block_attention_dropout(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                                      size_t heads, size_t head_dim, const float* d_q,
+                                      const float* d_k, const float* d_v, float negative_slope,
+                                      float p, uint64_t seed, float* d_out, float* d_att,
+                                      float* d_att_dropped, int device, void* stream);
+GF_API int gf_block_attention_dropout_backward(const int64_t* d_offsets, size_t num_dst,
+                                               size_t num_edges, size_t heads, size_t head_dim,
+                                               const float* d_q, const float* d_k,
+                                               const float* d_v, const float* d_att,
+                                               float negative_slope, float p, uint64_t seed,
+                                               const float* d_grad_out, float* d_grad_q,
+                                               float* d_grad_k, float* d_grad_v, int device,
+                                               void* stream);
 
 /* Fused time encoding (the reference's TimeEncode, layers.py:16-42, and the torch.cat around
  * it): d_out [n, width_a + width_b + dim_time], row-major and contiguous,

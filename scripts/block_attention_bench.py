@@ -10,6 +10,14 @@ Each of the four variants is timed in `--rounds` rounds that alternate between t
 a round runs enough iterations for at least `--min-seconds / --rounds` of device time, so every
 variant's timed region is at least --min-seconds.  Prints one JSON line: the median round of
 each variant in microseconds per iteration, and the fused kernels' mandatory bytes / time.
+
+    python scripts/block_attention_bench.py --shape epoch --dropout 0.2
+
+With --dropout P > 0 the fused variants pass dropout_p=P and a fresh seed per call, the composed
+variants put F.dropout(att, P) between edge_softmax and the multiply, and two more variants time
+the fused op WITHOUT dropout in the same interleaved rounds, so that the line also carries the
+dropout kernels' time as a fraction of the plain kernels' time and the composed chain's own
+round-to-round spread (max - min), the margin a change of the layer's default has to beat.
 """
 import argparse
 import json
@@ -28,6 +36,8 @@ def main():
     ap.add_argument("--head-dim", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=10)
     ap.add_argument("--min-seconds", type=float, default=0.5)
+    ap.add_argument("--dropout", type=float, default=0.0,
+                    help="attention dropout probability (0: none, the original four variants)")
     a = ap.parse_args()
     import torch
     import torch.nn.functional as F
@@ -53,11 +63,21 @@ def main():
     gout = torch.randn(nd, H, D, device=dev)
     row_t = b.edges()[1]
 
+    P = a.dropout
+    seeds = iter(range(1, 1 << 62))
+
+    def plain():
+        return ops.block_attention(b, q, k, v)
+
     def fused():
+        if P > 0:
+            return ops.block_attention(b, q, k, v, dropout_p=P, dropout_seed=next(seeds))
         return ops.block_attention(b, q, k, v)
 
     def composed():
         att = ops.edge_softmax(b, F.leaky_relu((q[row_t] * k).sum(2), 0.2))
+        if P > 0:
+            att = F.dropout(att, P)
         msg = (v * att[:, :, None]).reshape(E, -1)
         pad = torch.cat([torch.zeros((nd, H * D), device=dev), msg])
         return ops.block_reduce(b, pad).view(nd, H, D)
@@ -72,6 +92,9 @@ def main():
 
     variants = {"fused_fwd": lambda: fwd(fused), "composed_fwd": lambda: fwd(composed),
                 "fused_fwd_bwd": lambda: fwd_bwd(fused), "composed_fwd_bwd": lambda: fwd_bwd(composed)}
+    if P > 0:
+        variants["plain_fwd"] = lambda: fwd(plain)
+        variants["plain_fwd_bwd"] = lambda: fwd_bwd(plain)
 
     def timed(fn, iters):
         start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -109,6 +132,16 @@ def main():
            "note": "us_per_iter includes host launch overhead of each path (wall time between "
                    "device events); GB/s = mandatory bytes / that time",
            "device": torch.cuda.get_device_name(0)}
+    if P > 0:
+        spread = (max(rounds["composed_fwd_bwd"]) - min(rounds["composed_fwd_bwd"])) * 1e6
+        out.update({
+            "dropout": P,
+            "composed_fwd_bwd_spread_us": round(spread, 2),
+            "fused_fwd_bwd_margin_us": round(us["composed_fwd_bwd"] - us["fused_fwd_bwd"], 2),
+            "fused_beats_composed_by_more_than_spread":
+                bool(us["composed_fwd_bwd"] - us["fused_fwd_bwd"] > spread),
+            "dropout_over_plain_fwd": round(us["fused_fwd"] / us["plain_fwd"], 3),
+            "dropout_over_plain_fwd_bwd": round(us["fused_fwd_bwd"] / us["plain_fwd_bwd"], 3)})
     print(json.dumps(out))
 
 
