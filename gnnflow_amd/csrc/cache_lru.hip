@@ -784,7 +784,7 @@ __global__ __launch_bounds__(kWide) void lru_list_install_kernel(Round r, uint32
 // lru_list_scan_kernel + lru_list_install_kernel as one launch: what the second launch read
 // from the first — counts per tile, the victims at the front of the list — travels between
 // workgroups of the SAME launch: counts as 8-byte granules {launch tag, count} (one relaxed
-// agent-scope store; the mechanism of merge_slots_fused_kernel, sampler.hip), the staged
+// agent-scope store; the mechanism of merge_slots_fused_kernel, sample_merge.hip), the staged
 // victims as write-through (sc1) stores that are drained (s_waitcnt vmcnt(0), workgroup
 // barrier) before the tile's granule is published, and read with sc1 loads only
 // (MI355X_MICROARCH, inter-workgroup visibility, "valid forms": row 1 of the table).

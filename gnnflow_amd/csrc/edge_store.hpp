@@ -60,7 +60,7 @@ struct alignas(32) EdgePair {
 // ts_pool[d] also writes the fences d is the last element of (fence_store below).  Any fence
 // whose position lies inside a node's live segment is a valid pivot of that (sorted) segment,
 // and 16 consecutive pivots of a level are one 64-byte line: the window search reads ONE line
-// per round instead of 16 strided 4-byte probes = 16 sectors (sampler.hip).  1/15 float per
+// per round instead of 16 strided 4-byte probes = 16 sectors (sampler_ctx.hpp).  1/15 float per
 // edge (0.27 B).  Levels sit in one buffer, level l at element offset off[l - 1].
 constexpr uint32_t kFenceMaxLevels = 8;   // 16^8 = 4.3 G elements per top-level block
 struct FenceView {

@@ -295,7 +295,7 @@ __global__ __launch_bounds__(kFusedThreads) void partition_plan_fused_kernel(
 
 // Up to four samples' plans in ONE launch (blockIdx.y picks the job): the chain of a
 // partitioned sample is bound by the host thread that issues its launches, so samples that
-// share their launches and exchanges divide that cost (sampler.hip sample_partitioned_group).
+// share their launches and exchanges divide that cost (sampler_group.hip sample_partitioned_group).
 struct PlanJobs { PlanJob j[4]; };
 __global__ __launch_bounds__(kFusedThreads) void partition_plan_jobs_kernel(
     PlanJobs jobs, OwnerDiv od, uint32_t rank, uint32_t stride) {

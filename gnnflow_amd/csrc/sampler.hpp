@@ -12,6 +12,8 @@
 
 namespace gf {
 
+struct Publish;   // sampler_ctx.hpp: where a sample's last kernel leaves its block sizes
+
 class Sampler {
  public:
   Sampler(EdgeStore* graph, const uint32_t* fanouts, size_t num_layers, int policy,
@@ -74,7 +76,7 @@ class Sampler {
   void part_merge(uint32_t layer, uint32_t snapshot, void* d_ws, size_t ws_bytes);
   void part_commit();
   void part_abort();
-  // Up to kMaxGroup samples in ONE chain (sampler.hip "SHARE their launches and exchanges"):
+  // Up to kMaxGroup samples in ONE chain (sampler_group.hip "SHARE their launches and exchanges"):
   // sample j runs through its own sampler — all over the same graph with the same arguments;
   // shared launches, exchanges and exchange workspace, separate outputs / counters / publish
   // records.
@@ -98,7 +100,7 @@ class Sampler {
   // edge_fill: compact reply slots — a slot carries at most this share of its stride x fanout
   // fixed-fanout records (0: the fixed records themselves travel).  Part of the wire format.
   bool group_ok(const size_t* R, int m) const;
-  // narrow: 12-byte reply slots (ids that fit 32 bits; sampler.hip PaddedCommon)
+  // narrow: 12-byte reply slots (ids that fit 32 bits; sampler_ctx.hpp PaddedCommon)
   // reuse_roots: layer l + 1 does not request layer l's roots again (most-recent, equal
   // fanouts) — its slots are sized for the roots it still requests.  Part of the wire format.
   bool layer_reuses_roots(bool reuse_roots, size_t layer) const {
@@ -139,7 +141,7 @@ class Sampler {
   void enqueue_layer(const int64_t* d_roots, const float* d_ts, size_t R_bound,
                      const uint64_t* d_R, uint64_t R_host, uint32_t layer, uint32_t snapshot,
                      const BlockPtrs& out, uint64_t* d_counts_slot, uint64_t* next_R,
-                     hipStream_t stream, const void* publish);
+                     hipStream_t stream, const Publish& publish);
   void reserve_workspace(size_t R_bound_max, size_t num_blocks, hipStream_t stream);
   void to_host_blocks(const gf_block* dev, gf_block* host, size_t n, hipStream_t stream);
 
@@ -158,7 +160,7 @@ class Sampler {
   void set_call_counter(uint64_t v) { calls_ = v; }
  private:
   int search_group_ = 16;   // lanes per root, layers of <= 32 768 roots
-  int large_group_ = 4;     // lanes per root, larger layers (sampler.hip: group_width_from_env)
+  int large_group_ = 4;     // lanes per root, larger layers (sample_layer.hip: group_width_from_env)
   bool hybrid_search_ = true;   // large layers: lane-per-root search, groups for the hubs
   // begun, not yet ended samples (FIFO).  begin() may run on the library's enqueue thread
   // while end() runs on the caller's: the ring bookkeeping is under ring_mu_.
@@ -189,7 +191,7 @@ class Sampler {
   bool part_own_counts(size_t root_bound) const;
   // slotted form, small layers: count + prefix + emit of the merge in ONE launch (granules)
   bool part_fused_merge(size_t root_bound, uint32_t fanout) const;
-  void part_commit_prepare(void* publish_out);   // Publish record of the sample being built
+  void part_commit_prepare(Publish& pub);   // Publish record of the sample being built
   void part_commit_finish();
   void part_roots(uint32_t layer, uint32_t snapshot, const int64_t** roots, const float** ts,
                   const uint64_t** d_R, uint64_t* R_host) const;
@@ -210,7 +212,7 @@ class Sampler {
   hipStream_t own_stream_ = nullptr;
 };
 
-// diagnostics and test hooks (sampler.hip)
+// diagnostics and test hooks (sampler.hip, sample_merge.hip, sample_layer.hip)
 void part_host_us(double out[8], bool reset);
 uint64_t merge_recounts();
 void philox_on_device(const uint64_t* d_in, size_t n, uint32_t* d_out, hipStream_t stream);

@@ -754,7 +754,7 @@ class DevicePartitionedSampler:
         C = self._C
         out = (C.c_uint64 * 4)()
         for layer, F in enumerate(self._fanouts if self._slack > 0 else []):
-            # the native layout itself (sampler.hip group_layout), not a restatement of it
+            # the native layout itself (sampler_group.hip group_layout), not a restatement of it
             self._capi.check(self._lib.gf_sampler_part_group_slot(
                 self._sampler._h, R0, layer, self._P, self._slack, self._slot_roots,
                 (1 if self._narrow else 0) |

@@ -565,7 +565,7 @@ GF_API int gf_sampler_part_layout_slotted(const gf_sampler* s, size_t num_roots,
                                           int world_size, double slack, size_t slot_roots,
                                           gf_part_layout* out);
 /* What one slot of a shared chain's exchanges takes on the wire for `layer` (the layout the
- * native chains use, sampler.hip group_layout): out[0] = rows per request slot (16 B each, header
+ * native chains use, sampler_group.hip group_layout): out[0] = rows per request slot (16 B each, header
  * row included), out[1] = bytes of one reply slot (compact: offsets + packed edges; edge_fill 0:
  * the fixed records), out[2] = edges a compact reply slot holds at most, out[3] = bytes of its
  * offsets (2 / 4).  narrow: bit 0 = 12-byte reply records, bit 1 = layer l + 1 does not request
