@@ -1,0 +1,73 @@
+// extern "C" entry points of include/gnnflow_hip.h over EdgeStore: gf_graph_*.
+#include "capi_handles.hpp"
+
+extern "C" {
+
+int gf_graph_create(gf_graph** out, size_t initial_pool_size, size_t maximum_pool_size,
+                    int mem_resource_type, size_t minium_block_size,
+                    size_t blocks_to_preallocate, int insertion_policy, int device,
+                    int adaptive_block_size) {
+  return guarded([&] {
+    GF_REQUIRE(out != nullptr, "gf_graph_create: null out");
+    *out = new gf_graph(initial_pool_size, maximum_pool_size, mem_resource_type,
+                        minium_block_size, blocks_to_preallocate, insertion_policy, device,
+                        adaptive_block_size != 0);
+  });
+}
+int gf_graph_destroy(gf_graph* g) { return destroy_handle(g); }
+int gf_graph_add_edges(gf_graph* g, const int64_t* src, const int64_t* dst, const float* ts,
+                       const int64_t* eids, size_t n) {
+  return guarded([&] { GF_G(g); g->impl.add_edges(src, dst, ts, eids, n); });
+}
+int gf_graph_offload_old_blocks(gf_graph* g, float timestamp, int to_file, size_t* num_blocks) {
+  return guarded([&] {
+    GF_G(g);
+    size_t n = g->impl.offload_old_blocks(timestamp, to_file != 0);
+    if (num_blocks) *num_blocks = n;
+  });
+}
+int gf_graph_num_vertices(const gf_graph* g, size_t* out) {
+  return guarded([&] { GF_G(g); *out = g->impl.num_nodes(); });
+}
+int gf_graph_num_source_vertices(const gf_graph* g, size_t* out) {
+  return guarded([&] { GF_G(g); *out = g->impl.num_src_nodes(); });
+}
+int gf_graph_num_edges(const gf_graph* g, size_t* out) {
+  return guarded([&] { GF_G(g); *out = g->impl.num_edges(); });
+}
+int gf_graph_max_vertex_id(const gf_graph* g, int64_t* out) {
+  return guarded([&] { GF_G(g); *out = g->impl.max_node_id(); });
+}
+int gf_graph_ids_fit_u32(const gf_graph* g, int* out) {
+  return guarded([&] { GF_G(g); *out = g->impl.ids_fit_u32() ? 1 : 0; });
+}
+int gf_graph_out_degree(const gf_graph* g, const int64_t* nodes, size_t n, size_t* out) {
+  return guarded([&] { GF_G(g); g->impl.out_degree(nodes, n, out); });
+}
+int gf_graph_nodes(const gf_graph* g, int64_t* out, size_t capacity, size_t* count) {
+  return guarded([&] { GF_G(g); *count = g->impl.nodes(out, capacity, false); });
+}
+int gf_graph_src_nodes(const gf_graph* g, int64_t* out, size_t capacity, size_t* count) {
+  return guarded([&] { GF_G(g); *count = g->impl.nodes(out, capacity, true); });
+}
+int gf_graph_edges(const gf_graph* g, int64_t* out, size_t capacity, size_t* count) {
+  return guarded([&] { GF_G(g); *count = g->impl.edges(out, capacity); });
+}
+int gf_graph_get_temporal_neighbors(const gf_graph* g, int64_t node, int64_t* dst, float* ts,
+                                    int64_t* eids, size_t capacity, size_t* count) {
+  return guarded([&] { GF_G(g); *count = g->impl.get_temporal_neighbors(node, dst, ts, eids, capacity); });
+}
+int gf_graph_avg_linked_list_length(const gf_graph* g, float* out) {
+  return guarded([&] { GF_G(g); *out = g->impl.avg_linked_list_length(); });
+}
+int gf_graph_memory_usage(const gf_graph* g, float* out) {
+  return guarded([&] { GF_G(g); *out = g->impl.graph_mem_usage(); });
+}
+int gf_graph_metadata_memory_usage(const gf_graph* g, float* out) {
+  return guarded([&] { GF_G(g); *out = g->impl.metadata_mem_usage(); });
+}
+int gf_graph_device(const gf_graph* g, int* out) {
+  return guarded([&] { GF_G(g); *out = g->impl.device(); });
+}
+
+}  // extern "C"
