@@ -261,6 +261,11 @@ PROTOTYPES = {
     "gf_block_attention_dropout_backward": (C.c_int, [_p, _sz, _sz, _sz, _sz, _p, _p, _p, _p,
                                                       C.c_float, C.c_float, C.c_uint64, _p, _p,
                                                       _p, _p, C.c_int, _p]),
+    "gf_block_gat": (C.c_int, [_p, _sz, _sz, _p, _sz, _sz, _sz, _p, _p, _p, C.c_float, C.c_float,
+                               C.c_uint64, _p, _p, _p, C.c_int, _p]),
+    "gf_block_gat_backward": (C.c_int, [_p, _sz, _sz, _p, _sz, _sz, _sz, _p, _p, _p, _p, _p,
+                                        C.c_float, C.c_float, C.c_uint64, _p, _p, _p, _p, C.c_int,
+                                        _p]),
     "gf_block_reduce_max": (C.c_int, [_p, _sz, _p, _p, _sz, _p, _p, C.c_int, _p]),
     "gf_block_reduce_max_backward": (C.c_int, [_sz, _p, _sz, _p, _p, _p, _sz, C.c_int, _p]),
     "gf_time_encode_cat": (C.c_int, [_p, _sz, _p, _sz, _p, _p, _p, _sz, _sz, _p, C.c_int, _p]),

@@ -1,4 +1,4 @@
-// Segment operations on a sampled block (block_ops.hip, block_attention.hip) and the fused time
+// Segment operations on a sampled block (block_ops.hip, block_attention.hip, block_gat.hip) and the fused time
 // encoding in front of them (time_encode.hip): the entry points other translation units call.
 #pragma once
 
@@ -56,6 +56,25 @@ void block_attention_dropout_backward(const int64_t* d_offsets, size_t num_dst, 
                                       float negative_slope, float p, uint64_t seed,
                                       const float* d_grad_out, float* d_grad_q, float* d_grad_k,
                                       float* d_grad_v, int device, hipStream_t stream);
+
+// block_gat.hip: fused GAT attention, z[e,h] = el[src(e),h] + er[d,h], the source rows both key
+// and value (feat [num_src, heads, head_dim]).  d_col null = the sampler's layout src(e) =
+// num_dst + e (then num_src must be num_dst + num_edges; the backward is free of atomics), else
+// d_grad_feat / d_grad_el accumulate with atomicAdd.  The width limit and the dropout mask
+// (p, seed; p == 0: none) are those of block_attention above.  d_att is the pre-dropout softmax
+// and d_out the forward's output: with them the backward reads each feat row once.  A null
+// d_grad_feat / d_grad_el / d_grad_er is skipped; the others are written in full.
+void block_gat_forward(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                       const int64_t* d_col, size_t num_src, size_t heads, size_t head_dim,
+                       const float* d_feat, const float* d_el, const float* d_er,
+                       float negative_slope, float p, uint64_t seed, float* d_out, float* d_att,
+                       float* d_att_dropped, int device, hipStream_t stream);
+void block_gat_backward(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                        const int64_t* d_col, size_t num_src, size_t heads, size_t head_dim,
+                        const float* d_feat, const float* d_el, const float* d_er,
+                        const float* d_att, const float* d_out, float negative_slope, float p,
+                        uint64_t seed, const float* d_grad_out, float* d_grad_feat,
+                        float* d_grad_el, float* d_grad_er, int device, hipStream_t stream);
 
 // time_encode.hip: out = [a | b | cosf(w * t + bias)] in one launch (a / b may be null with
 // width 0), and the gradients of w and bias from the time columns of grad_out, read in place

@@ -126,6 +126,30 @@ int gf_block_attention_dropout_backward(const int64_t* d_offsets, size_t num_dst
   });
 }
 
+int gf_block_gat(const int64_t* d_offsets, size_t num_dst, size_t num_edges, const int64_t* d_col,
+                 size_t num_src, size_t heads, size_t head_dim, const float* d_feat,
+                 const float* d_el, const float* d_er, float negative_slope, float p,
+                 uint64_t seed, float* d_out, float* d_att, float* d_att_dropped, int device,
+                 void* stream) {
+  return guarded([&] {
+    gf::block_gat_forward(d_offsets, num_dst, num_edges, d_col, num_src, heads, head_dim, d_feat,
+                          d_el, d_er, negative_slope, p, seed, d_out, d_att, d_att_dropped,
+                          device, as_stream(stream));
+  });
+}
+int gf_block_gat_backward(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                          const int64_t* d_col, size_t num_src, size_t heads, size_t head_dim,
+                          const float* d_feat, const float* d_el, const float* d_er,
+                          const float* d_att, const float* d_out, float negative_slope, float p,
+                          uint64_t seed, const float* d_grad_out, float* d_grad_feat,
+                          float* d_grad_el, float* d_grad_er, int device, void* stream) {
+  return guarded([&] {
+    gf::block_gat_backward(d_offsets, num_dst, num_edges, d_col, num_src, heads, head_dim, d_feat,
+                           d_el, d_er, d_att, d_out, negative_slope, p, seed, d_grad_out,
+                           d_grad_feat, d_grad_el, d_grad_er, device, as_stream(stream));
+  });
+}
+
 int gf_time_encode_cat(const float* d_a, size_t width_a, const float* d_b, size_t width_b,
                        const float* d_t, const float* d_w, const float* d_bias, size_t n,
                        size_t dim_time, float* d_out, int device, void* stream) {

@@ -93,10 +93,30 @@ class SAGEConv(nn.Module):
         return rst
 
 
+# Defaults of `fused_attention` and `fused_attention_dropout` in GATConv.  Each becomes True only
+# once scripts/block_gat_bench.py (the second with --dropout) has shown the fused op, forward +
+# backward, ahead of the composed chain at every one of its shapes by more than the chain's own
+# round-to-round spread in that run (profiles/block_gat_bench.jsonl).
+FUSED_GAT_DEFAULT = False
+FUSED_GAT_DROPOUT_DEFAULT = False
+
+
 class GATConv(nn.Module):
     """Graph attention layer: e_ij = LeakyReLU(a_l . W h_j + a_r . W h_i),
     alpha = edge_softmax(e), h_i' = sum_j alpha_ij W h_j (+ residual, bias, activation);
-    returns [num_dst, num_heads, out_feats]."""
+    returns [num_dst, num_heads, out_feats].
+
+    The attention is the chain el[col] + er[row] -> leaky_relu -> ops.edge_softmax -> attn_drop
+    -> ops.block_reduce.  With `fused_attention` set and get_attention false it is ONE
+    ops.block_gat call instead (one kernel each way, no [E, H] intermediates), whenever attention
+    dropout is inactive (attn_drop.p == 0 or eval mode).  With `fused_attention_dropout` set as
+    well, training with 0 < attn_drop.p < 1 is one ops.block_gat call too: the dropout happens
+    inside the kernels, from the op's stateless Philox mask, with a seed drawn per forward from
+    torch's default CPU generator (no device sync; reproducible under torch.manual_seed, but not
+    the mask torch's own dropout would draw).  get_attention=True always takes the composed
+    chain, where the returned attention stays differentiable.  Both attributes are plain Python
+    attributes, not part of the state dict; their defaults are FUSED_GAT_DEFAULT and
+    FUSED_GAT_DROPOUT_DEFAULT."""
 
     def __init__(self, in_feats, out_feats, num_heads, feat_drop=0., attn_drop=0.,
                  negative_slope=0.2, residual=False, activation=None,
@@ -124,6 +144,10 @@ class GATConv(nn.Module):
         else:
             self.register_buffer('res_fc', None)
         self.activation = activation
+        # True: the attention is one ops.block_gat call (not part of the state)
+        self.fused_attention = FUSED_GAT_DEFAULT
+        # True: attention dropout in training inside ops.block_gat (not part of the state)
+        self.fused_attention_dropout = FUSED_GAT_DROPOUT_DEFAULT
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -149,10 +173,23 @@ class GATConv(nn.Module):
         feat_dst = feat_src[:num_dst]
         el = (feat_src * self.attn_l).sum(dim=-1)        # [num_src, H]
         er = (feat_dst * self.attn_r).sum(dim=-1)        # [num_dst, H]
-        col, row = graph.edges()
-        e = self.leaky_relu(el[col] + er[row])           # u_add_v
-        a = self.attn_drop(ops.edge_softmax(graph, e))   # [E, H]
-        rst = ops.block_reduce(graph, feat_src, a)       # u_mul_e + sum -> [num_dst, H, D]
+        p = self.attn_drop.p
+        drop = self.training and p > 0
+        a = None
+        if self.fused_attention and not get_attention and not drop:
+            rst = ops.block_gat(graph, feat_src, el, er,
+                                negative_slope=self.leaky_relu.negative_slope)
+        elif self.fused_attention and not get_attention and self.fused_attention_dropout \
+                and p < 1:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64))
+            rst = ops.block_gat(graph, feat_src, el, er,
+                                negative_slope=self.leaky_relu.negative_slope,
+                                dropout_p=p, dropout_seed=seed)
+        else:
+            col, row = graph.edges()
+            e = self.leaky_relu(el[col] + er[row])           # u_add_v
+            a = self.attn_drop(ops.edge_softmax(graph, e))   # [E, H]
+            rst = ops.block_reduce(graph, feat_src, a)       # u_mul_e + sum -> [num_dst, H, D]
         if self.res_fc is not None:
             rst = rst + self.res_fc(h_src[:num_dst]).view(num_dst, H, D)
         if self.bias is not None:

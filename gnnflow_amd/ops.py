@@ -7,6 +7,9 @@ make on a sampled block, on HIP segment kernels (csrc/block_ops.hip) with autogr
     block_attention(block, q, k, v)        layers.py:144-159 in one launch (csrc/block_attention.hip)
       ... dropout_p=, dropout_seed=        with the attention dropout of layers.py:155 inside it, from a
                                            stateless Philox mask (no mask tensor, reproducible on the CPU)
+    block_gat(block, feat, el, er)         dgl.nn.GATConv's u_add_v -> leaky_relu -> edge_softmax ->
+                                           (attn_drop) -> u_mul_e + sum in one launch each way
+                                           (csrc/block_gat.hip), the same dropout_p= / dropout_seed=
     time_encode_cat(parts, t, w, b)        torch.cat([*parts, TimeEncode(t)], 1) in one launch
                                            (layers.py:16-42, 118-137; csrc/time_encode.hip)
 
@@ -314,6 +317,144 @@ def block_attention(block, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                                                 p32, dropout_seed, bool(return_attention))
     else:
         out, att = _BlockAttention.apply(q, k, v, offsets, num_dst, float(negative_slope))
+    if not return_attention:
+        return out
+    if perm is not None:
+        att = torch.empty_like(att).index_copy(0, perm, att)
+    return out, att
+
+
+class _BlockGat(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat, el, er, offsets, col, num_dst, E, slope, p, seed, want_dropped):
+        # feat [num_src, H, D], el [num_src, H], er [num_dst, H] contiguous fp32; col is None for
+        # the sampler's layout.  att is the pre-dropout softmax (saved, with out, for backward).
+        num_src, H, D = feat.shape
+        out = torch.empty((num_dst, H, D), dtype=torch.float32, device=feat.device)
+        att = torch.empty((E, H), dtype=torch.float32, device=feat.device)
+        dropped = torch.empty_like(att) if want_dropped and p > 0 else None
+        with torch.cuda.device(feat.device):
+            _capi.check(_capi.load().gf_block_gat(
+                offsets.data_ptr(), num_dst, E, _ptr(col), num_src, H, D, feat.data_ptr(),
+                el.data_ptr(), er.data_ptr(), slope, p, seed, out.data_ptr(), att.data_ptr(),
+                _ptr(dropped), feat.device.index, _stream(feat.device)))
+        ctx.save_for_backward(feat, el, er, att, out, offsets, col)
+        ctx.meta = (slope, p, seed)
+        shown = dropped if p > 0 else att
+        if not want_dropped:
+            return out, None
+        ctx.mark_non_differentiable(shown)
+        return out, shown
+
+    @staticmethod
+    def backward(ctx, grad, _grad_att):
+        feat, el, er, att, out, offsets, col = ctx.saved_tensors
+        slope, p, seed = ctx.meta
+        g = _f32(grad)
+        num_src, H, D = feat.shape
+        need_feat, need_el, need_er = ctx.needs_input_grad[:3]
+        gfeat = torch.empty_like(feat) if need_feat else None
+        gel = torch.empty_like(el) if need_el else None
+        ger = torch.empty_like(er) if need_er else None
+        if need_feat or need_el or need_er:
+            with torch.cuda.device(feat.device):
+                _capi.check(_capi.load().gf_block_gat_backward(
+                    offsets.data_ptr(), er.shape[0], att.shape[0], _ptr(col), num_src, H, D,
+                    feat.data_ptr(), el.data_ptr(), er.data_ptr(), att.data_ptr(),
+                    out.data_ptr(), slope, p, seed, g.data_ptr(), _ptr(gfeat), _ptr(gel),
+                    _ptr(ger), feat.device.index, _stream(feat.device)))
+        return gfeat, gel, ger, None, None, None, None, None, None, None, None
+
+
+class _NoEdgeGat(torch.autograd.Function):
+    """A block without edges or without destinations: zeros, and zero gradients."""
+    @staticmethod
+    def forward(ctx, feat, el, er):
+        ctx.save_for_backward(feat, el, er)
+        return torch.zeros((er.shape[0],) + tuple(feat.shape[1:]), dtype=torch.float32,
+                           device=feat.device)
+
+    @staticmethod
+    def backward(ctx, grad):
+        return tuple(torch.zeros_like(t) if need else None
+                     for t, need in zip(ctx.saved_tensors, ctx.needs_input_grad))
+
+
+def block_gat(block, feat: torch.Tensor, el: torch.Tensor, er: torch.Tensor,
+              negative_slope: float = 0.2, return_attention: bool = False,
+              dropout_p: float = 0.0, dropout_seed: Optional[int] = None):
+    """The message passing of dgl.nn.GATConv in one kernel each way:
+
+        att[e, h] = edge_softmax(leaky_relu(el[col[e], h] + er[row[e], h], negative_slope))
+        out[d, h] = sum over the edges e into d of att[e, h] * feat[col[e], h]   (0 without in-edges)
+
+    feat: [num_src_nodes, H, D]; el: [num_src_nodes, H]; er: [num_dst_nodes, H], float32 on one
+    GPU; H * D is at most MAX_ATTENTION_WIDTH.  Returns out [num_dst_nodes, H, D], and with
+    return_attention=True also att [num_edges, H] in the caller's edge order (not
+    differentiable).  Differentiable in feat, el and er; the forward's out is kept for the
+    backward, which then reads every feat row once.
+
+    dropout_p / dropout_seed are those of block_attention, with the same mask: p =
+    float32(dropout_p) in [0, 1), i the position of an edge in the grouped order of
+    block.segments(), keep[i, h] = gf_philox4x32_10_first(dropout_seed, i * H + h, 0) >=
+    uint32(float64(p) * 2**32), and a kept weight scaled by float32(1) / (float32(1) - p).  The
+    seed (0 <= seed < 2**64) is required when dropout_p > 0; return_attention=True then returns
+    the DROPPED attention att * w.  A dropped edge contributes exactly 0 and its feat row is not
+    read, forward or backward.  dropout_p == 0 is the call without the two arguments, bit for bit.
+
+    On a sampler block (segments()[1] is None: source of edge k = node num_dst + k) the backward
+    uses no atomics and two runs give the same bits.  On a block with an explicit col a source
+    may feed several edges; the gradients of feat and el are then accumulated with atomic adds:
+    correct within the same error bounds, rows no edge reads exact zeros, but NOT bit-identical
+    from run to run."""
+    dropout_p = float(dropout_p)
+    if not 0.0 <= dropout_p < 1.0:          # NaN fails too
+        raise ValueError("dropout_p must be in [0, 1), got {}".format(dropout_p))
+    p32 = C.c_float(dropout_p).value        # the fp32 value the kernels see
+    if p32 >= 1.0:
+        raise ValueError("dropout_p rounds to 1 in float32")
+    if dropout_seed is not None:
+        dropout_seed = int(dropout_seed)
+        if not 0 <= dropout_seed < 2 ** 64:
+            raise ValueError("dropout_seed must be in [0, 2**64), got {}".format(dropout_seed))
+    elif dropout_p > 0:
+        raise ValueError("dropout_p > 0 needs a dropout_seed")
+    for name, t in (("feat", feat), ("el", el), ("er", er)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("{} must be a tensor, got {}".format(name, type(t).__name__))
+        if t.dtype != torch.float32:
+            raise TypeError("block_gat computes in float32, {} is {}".format(name, t.dtype))
+    num_dst, num_src, E = block.num_dst_nodes(), block.num_src_nodes(), block.num_edges()
+    if feat.dim() != 3:
+        raise ValueError("feat must be [num_src, H, D], got {}".format(tuple(feat.shape)))
+    if el.dim() != 2 or er.dim() != 2:
+        raise ValueError("el and er must be [rows, H], got {} and {}".format(
+            tuple(el.shape), tuple(er.shape)))
+    if feat.shape[0] != num_src or el.shape[0] != num_src:
+        raise ValueError("feat and el must have one row per source node")
+    if er.shape[0] != num_dst:
+        raise ValueError("er must have one row per destination node")
+    H, D = int(feat.shape[1]), int(feat.shape[2])
+    if el.shape[1] != H or er.shape[1] != H:
+        raise ValueError("feat, el and er differ in H: {}, {}, {}".format(
+            H, el.shape[1], er.shape[1]))
+    if H < 1 or D < 1:
+        raise ValueError("block_gat needs H >= 1 and D >= 1")
+    if H * D > MAX_ATTENTION_WIDTH:
+        raise ValueError("H * D = {} exceeds the limit of {}".format(H * D, MAX_ATTENTION_WIDTH))
+    if el.device != feat.device or er.device != feat.device:
+        raise ValueError("feat is on {}, el on {}, er on {}".format(
+            feat.device, el.device, er.device))
+    if feat.device.type != "cuda":
+        raise ValueError("block_gat runs on the GPU, the inputs are on {}".format(feat.device))
+    feat, el, er = feat.contiguous(), el.contiguous(), er.contiguous()
+    if E == 0 or num_dst == 0:
+        out = _NoEdgeGat.apply(feat, el, er)       # nothing to launch
+        return (out, torch.zeros((E, H), dtype=torch.float32, device=feat.device)) \
+            if return_attention else out
+    offsets, col, perm = block.segments()
+    out, att = _BlockGat.apply(feat, el, er, offsets, col, num_dst, E, float(negative_slope),
+                               p32, dropout_seed if p32 > 0 else 0, bool(return_attention))
     if not return_attention:
         return out
     if perm is not None:

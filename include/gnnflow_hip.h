@@ -823,6 +823,39 @@ GF_API int gf_block_attention_dropout_backward(const int64_t* d_offsets, size_t 
                                                float* d_grad_k, float* d_grad_v, int device,
                                                void* stream);
 
+/* Fused GAT attention (dgl.nn.GATConv's message passing) over a block: feat [num_src, heads,
+ * head_dim], el [num_src, heads], er [num_dst, heads]; src(e) = d_col[e], or num_dst + e when
+ * d_col is NULL (the sampler's layout; num_src must then be num_dst + num_edges),
+ *   z[e,h] = el[src(e),h] + er[d,h]   (d = destination of e, from d_offsets)
+ *   att    = edge softmax of leaky_relu(z, negative_slope)            -> d_att [num_edges, heads]
+ *   out[d,h,:] = sum over the edges e of d of (att[e,h] * w[e,h]) * feat[src(e),h,:]
+ * (a destination without in-edges: 0).  w is the dropout mask of gf_block_attention_dropout,
+ * unchanged: p an fp32 value in [0, 1) (else GF_ERR_INVALID_ARGUMENT), i the position of an edge
+ * in the grouped order of d_offsets, keep[i,h] = gf_philox4x32_10_first(seed, i * heads + h, 0)
+ * >= (uint32_t)((double)p * 4294967296.0), w = keep ? 1.0f / (1.0f - p) : 0; p == 0 is the call
+ * without dropout (w = 1, seed unused).  d_att receives the PRE-dropout softmax; d_att_dropped,
+ * unless NULL, receives att * w.  Each feat row is read at most once and a dropped edge's row not
+ * at all.  heads * head_dim <= GF_BLOCK_ATTENTION_MAX_WIDTH, else GF_ERR_INVALID_ARGUMENT. */
+GF_API int gf_block_gat(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                        const int64_t* d_col, size_t num_src, size_t heads, size_t head_dim,
+                        const float* d_feat, const float* d_el, const float* d_er,
+                        float negative_slope, float p, uint64_t seed, float* d_out, float* d_att,
+                        float* d_att_dropped, int device, void* stream);
+/* d_att and d_out as the forward wrote them, (p, seed) as the forward got them: the mask is drawn
+ * again.  Each of d_grad_feat [num_src, heads, head_dim], d_grad_el [num_src, heads] and
+ * d_grad_er [num_dst, heads] may be NULL (skipped); every element of the others is written.
+ * d_col NULL: no atomics, each element written exactly once (the rows [0, num_dst) no edge reads
+ * are zeros), bit-identical from run to run.  Otherwise d_grad_feat and d_grad_el are zeroed and
+ * accumulated with atomic adds (a source may feed several edges): rows no edge reads are exact
+ * zeros, the rest may differ in the last bits from run to run. */
+GF_API int gf_block_gat_backward(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                                 const int64_t* d_col, size_t num_src, size_t heads,
+                                 size_t head_dim, const float* d_feat, const float* d_el,
+                                 const float* d_er, const float* d_att, const float* d_out,
+                                 float negative_slope, float p, uint64_t seed,
+                                 const float* d_grad_out, float* d_grad_feat, float* d_grad_el,
+                                 float* d_grad_er, int device, void* stream);
+
 /* Fused time encoding (the reference's TimeEncode, layers.py:16-42, and the torch.cat around
  * it): d_out [n, width_a + width_b + dim_time], row-major and contiguous,
  *   out[i, 0:width_a]                = a[i, :]      (width_a may be 0, d_a NULL)
