@@ -272,6 +272,10 @@ PROTOTYPES = {
     "gf_time_encode_backward_partial_rows": (C.c_int, [_sz, C.POINTER(_sz)]),
     "gf_time_encode_backward": (C.c_int, [_p, _p, _p, _sz, _sz, _p, _sz, _sz, _p, _sz, _p, _p,
                                           C.c_int, _p]),
+    "gf_edge_score": (C.c_int, [_p, _p, _p, _p, _sz, _sz, _sz, _p, C.c_int, _p]),
+    "gf_edge_score_backward_partial_rows": (C.c_int, [_sz, C.POINTER(_sz)]),
+    "gf_edge_score_backward": (C.c_int, [_p, _p, _p, _sz, _sz, _sz, _p, _p, _sz, _p, _p, _p, _p,
+                                         C.c_int, _p]),
     "gf_debug_part_host_us": (C.c_int, [C.POINTER(C.c_double), C.c_int]),
     "gf_debug_merge_recounts": (C.c_int, [C.POINTER(C.c_uint64)]),
     "gf_debug_part_reused_roots": (C.c_int, [C.POINTER(C.c_uint64)]),

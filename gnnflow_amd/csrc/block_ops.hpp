@@ -1,5 +1,6 @@
-// Segment operations on a sampled block (block_ops.hip, block_attention.hip, block_gat.hip) and the fused time
-// encoding in front of them (time_encode.hip): the entry points other translation units call.
+// Segment operations on a sampled block (block_ops.hip, block_attention.hip, block_gat.hip), the fused time
+// encoding in front of them (time_encode.hip) and the fused edge score behind them
+// (edge_score.hip): the entry points other translation units call.
 #pragma once
 
 #include <cstddef>
@@ -90,5 +91,20 @@ void time_encode_backward(const float* d_t, const float* d_w, const float* d_bia
                           size_t dim_time, const float* d_grad_out, size_t grad_pitch,
                           size_t grad_col, float* d_partials, size_t partial_rows,
                           float* d_grad_w, float* d_grad_bias, int device, hipStream_t stream);
+
+// edge_score.hip: out[j] = bias + sum_d w[d] * max(src[j mod num_src, d] + dst[j, d], 0) in one
+// launch (num_dst a multiple of num_src), and its gradients in at most two.  The backward needs
+// a caller-owned buffer of edge_score_backward_partial_rows(num_src) * (dim + 1) floats when
+// d_grad_w or d_grad_bias is asked for; a null d_grad_src / d_grad_dst / d_grad_w / d_grad_bias
+// is skipped.  num_dst == 0 launches nothing.
+constexpr size_t kEdgeScoreMaxPartialRows = 1024;
+size_t edge_score_backward_partial_rows(size_t num_src);
+void edge_score_forward(const float* d_src, const float* d_dst, const float* d_w,
+                        const float* d_bias, size_t num_src, size_t num_dst, size_t dim,
+                        float* d_out, int device, hipStream_t stream);
+void edge_score_backward(const float* d_src, const float* d_dst, const float* d_w, size_t num_src,
+                         size_t num_dst, size_t dim, const float* d_grad_out, float* d_partials,
+                         size_t partial_rows, float* d_grad_src, float* d_grad_dst,
+                         float* d_grad_w, float* d_grad_bias, int device, hipStream_t stream);
 
 }  // namespace gf

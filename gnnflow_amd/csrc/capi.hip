@@ -1,6 +1,6 @@
 // extern "C" entry points of include/gnnflow_hip.h: thin, exception-free shims.  Here: the error
 // slot they all report through, the pid behind foreign_process(), the shims over free functions
-// (block ops, time encoding, debug counters).  Those over a handle: capi_{graph,sampler,cache,comm}.
+// (block ops, time encoding, edge score, debug counters).  Those over a handle: capi_{graph,sampler,cache,comm}.
 #include "block_ops.hpp"
 #include "capi_handles.hpp"
 #include "partition.hpp"
@@ -171,6 +171,32 @@ int gf_time_encode_backward(const float* d_t, const float* d_w, const float* d_b
   return guarded([&] {
     gf::time_encode_backward(d_t, d_w, d_bias, n, dim_time, d_grad_out, grad_pitch, grad_col,
                              d_partials, partial_rows, d_grad_w, d_grad_bias, device, as_stream(stream));
+  });
+}
+
+int gf_edge_score(const float* d_src, const float* d_dst, const float* d_w, const float* d_bias,
+                  size_t num_src, size_t num_dst, size_t dim, float* d_out, int device,
+                  void* stream) {
+  return guarded([&] {
+    gf::edge_score_forward(d_src, d_dst, d_w, d_bias, num_src, num_dst, dim, d_out, device,
+                           as_stream(stream));
+  });
+}
+int gf_edge_score_backward_partial_rows(size_t num_src, size_t* rows) {
+  return guarded([&] {
+    GF_REQUIRE(rows != nullptr, "gf_edge_score_backward_partial_rows: null output");
+    *rows = gf::edge_score_backward_partial_rows(num_src);
+  });
+}
+int gf_edge_score_backward(const float* d_src, const float* d_dst, const float* d_w,
+                           size_t num_src, size_t num_dst, size_t dim, const float* d_grad_out,
+                           float* d_partials, size_t partial_rows, float* d_grad_src,
+                           float* d_grad_dst, float* d_grad_w, float* d_grad_bias, int device,
+                           void* stream) {
+  return guarded([&] {
+    gf::edge_score_backward(d_src, d_dst, d_w, num_src, num_dst, dim, d_grad_out, d_partials,
+                            partial_rows, d_grad_src, d_grad_dst, d_grad_w, d_grad_bias, device,
+                            as_stream(stream));
   });
 }
 

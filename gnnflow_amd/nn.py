@@ -9,7 +9,10 @@ TimeEncode / TemporalAttentionLayer are the reference's own temporal attention
 arguments and parameter names, on ops.block_attention and ops.time_encode_cat.
 
 GRUMemoryUpdater is TGN's memory updater (gnnflow/models/modules/memory_updater.py, there
-spelled GRUMemeoryUpdater), the consumer of gnnflow_amd.memory.Memory.prepare_input."""
+spelled GRUMemeoryUpdater), the consumer of gnnflow_amd.memory.Memory.prepare_input.
+
+EdgePredictor / MLP are the reference's heads (layers.py:171-214); EdgePredictor's tail can run as
+one ops.edge_score call."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -213,6 +216,12 @@ FUSED_TIME_ENCODE_DEFAULT = False
 # (profiles/block_attention_bench.jsonl).
 FUSED_ATTENTION_DROPOUT_DEFAULT = False
 
+# Default of `fused_score` in EdgePredictor.  True because scripts/bench_edge_score.py shows
+# ops.edge_score, forward + backward, ahead of the torch expression at B = 600, D = 100, as the op
+# alone (about 4x) and inside the module (about 1.65x), far beyond the rounds' spread
+# (profiles/edge_score_microbench.txt).
+FUSED_EDGE_SCORE_DEFAULT = True
+
 
 class TimeEncode(nn.Module):
     """TGAT's time encoding cos(w * dt + b): w = 1 / 10^linspace(0, 9, dim_time), b = 0 at
@@ -383,3 +392,50 @@ class GRUMemoryUpdater(nn.Module):
 
 
 GRUMemeoryUpdater = GRUMemoryUpdater                   # the reference's own spelling
+
+
+class EdgePredictor(nn.Module):
+    """The reference's link-prediction head over h = [src | pos dst | neg dst] (three equal row
+    blocks):
+
+        pos = out_fc(relu(src_fc(src) + dst_fc(pos dst)))
+        neg = out_fc(relu(src_fc(src) + dst_fc(neg dst)))        -> (pos, neg), [B, 1] each
+
+    With `fused_score`, float32 rows on the GPU take dst_fc as one GEMM over both destination
+    blocks and everything behind it as one ops.edge_score call; anything else the torch
+    expression."""
+
+    def __init__(self, dim_embed: int):
+        super().__init__()
+        self.src_fc = nn.Linear(dim_embed, dim_embed)
+        self.dst_fc = nn.Linear(dim_embed, dim_embed)
+        self.out_fc = nn.Linear(dim_embed, 1)
+        # True: the tail as one ops.edge_score call (not part of the state)
+        self.fused_score = FUSED_EDGE_SCORE_DEFAULT
+
+    def forward(self, h: torch.Tensor):
+        if h.shape[0] % 3:
+            raise ValueError("EdgePredictor takes [src | pos dst | neg dst] rows, {} is not a "
+                             "multiple of 3".format(h.shape[0]))
+        B = h.shape[0] // 3
+        if self.fused_score and h.is_cuda and h.dtype == torch.float32 and \
+                self.out_fc.weight.dtype == torch.float32:
+            out = ops.edge_score(self.src_fc(h[:B]), self.dst_fc(h[B:]), self.out_fc.weight,
+                                 self.out_fc.bias)
+            return out[:B], out[B:]
+        src_h = self.src_fc(h[:B])
+        pos_edge = F.relu(src_h + self.dst_fc(h[B:2 * B]))
+        neg_edge = F.relu(src_h + self.dst_fc(h[2 * B:]))
+        return self.out_fc(pos_edge), self.out_fc(neg_edge)
+
+
+class MLP(nn.Module):
+    """The reference's node-classification head: fc2(relu(fc1(x)))."""
+
+    def __init__(self, dim_in, dim_hid, num_class):
+        super().__init__()
+        self.fc1 = nn.Linear(dim_in, dim_hid)
+        self.fc2 = nn.Linear(dim_hid, num_class)
+
+    def forward(self, x):
+        return self.fc2(F.relu(self.fc1(x)))

@@ -12,6 +12,9 @@ make on a sampled block, on HIP segment kernels (csrc/block_ops.hip) with autogr
                                            (csrc/block_gat.hip), the same dropout_p= / dropout_seed=
     time_encode_cat(parts, t, w, b)        torch.cat([*parts, TimeEncode(t)], 1) in one launch
                                            (layers.py:16-42, 118-137; csrc/time_encode.hip)
+    edge_score(src, dst, w, b)             out_fc(relu(src + dst)) of EdgePredictor (layers.py:195-197),
+                                           every dst block against the one src block, in one launch
+                                           (csrc/edge_score.hip)
 
 A block's edges are grouped by destination (the sampler emits them that way); blocks built by
 hand with unordered edges are handled through a stable permutation.
@@ -566,6 +569,91 @@ def time_encode_cat(parts, t: torch.Tensor, weight: torch.Tensor, bias: torch.Te
 def time_encode(t: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
     """cos(t[:, None] * weight.T + bias): time_encode_cat without parts, [n, T]."""
     return _time_encode_cat((), t, weight, bias)
+
+
+class _EdgeScore(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, src, dst, weight, bias):
+        # src [B, D], dst [M, D] contiguous, weight [D], bias [1]; all fp32 on one device
+        M = dst.shape[0]
+        out = torch.empty((M, 1), dtype=torch.float32, device=dst.device)
+        if M:
+            with torch.cuda.device(dst.device):
+                _capi.check(_capi.load().gf_edge_score(
+                    src.data_ptr(), dst.data_ptr(), weight.data_ptr(), bias.data_ptr(),
+                    src.shape[0], M, dst.shape[1], out.data_ptr(), dst.device.index,
+                    _stream(dst.device)))
+        ctx.save_for_backward(src, dst, weight)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        src, dst, weight = ctx.saved_tensors
+        (B, D), M = src.shape, dst.shape[0]
+        need_src, need_dst, need_w, need_b = ctx.needs_input_grad
+        f32 = dict(dtype=torch.float32, device=dst.device)
+        if M == 0:      # zeros, and nothing to launch
+            return (torch.zeros_like(src) if need_src else None,
+                    torch.zeros_like(dst) if need_dst else None,
+                    torch.zeros_like(weight) if need_w else None,
+                    torch.zeros(1, **f32) if need_b else None)
+        if not (need_src or need_dst or need_w or need_b):
+            return None, None, None, None
+        g = _f32(grad)
+        gs = torch.empty_like(src) if need_src else None
+        gd = torch.empty_like(dst) if need_dst else None
+        gw = torch.empty_like(weight) if need_w else None
+        gb = torch.empty(1, **f32) if need_b else None
+        lib = _capi.load()
+        partials, rows = None, C.c_size_t(0)
+        if need_w or need_b:
+            _capi.check(lib.gf_edge_score_backward_partial_rows(B, C.byref(rows)))
+            partials = torch.empty((rows.value, D + 1), **f32)
+        with torch.cuda.device(dst.device):
+            _capi.check(lib.gf_edge_score_backward(
+                src.data_ptr(), dst.data_ptr(), weight.data_ptr(), B, M, D, g.data_ptr(),
+                _ptr(partials), rows.value, _ptr(gs), _ptr(gd), _ptr(gw), _ptr(gb),
+                dst.device.index, _stream(dst.device)))
+        return gs, gd, gw, gb
+
+
+def edge_score(src: torch.Tensor, dst: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor):
+    """out[j, 0] = bias + sum_d weight[d] * relu(src[j mod B, d] + dst[j, d]): the tail of the
+    reference's EdgePredictor (layers.py:195-197) for every block of dst rows in one kernel.
+
+    src: [B, D]; dst: [M, D] with M = r * B, block k of B rows paired with src (r = 2: the
+    positive and the negative half; r > 2: several negatives per positive, block after block);
+    weight: [D] or [1, D] (out_fc.weight); bias: [1]; all float32 on one GPU (row slices such as
+    h[B:] are taken as they are; any other non-contiguous input is copied first).  Returns
+    [M, 1].  Differentiable in all four; every gradient is summed in a fixed order:
+    bit-identical from run to run."""
+    for name, x in (("src", src), ("dst", dst), ("weight", weight), ("bias", bias)):
+        if not isinstance(x, torch.Tensor):
+            raise TypeError("{} must be a tensor, got {}".format(name, type(x).__name__))
+        if x.dtype != torch.float32:
+            raise TypeError("edge_score computes in float32, {} is {}".format(name, x.dtype))
+    if src.dim() != 2 or dst.dim() != 2:
+        raise ValueError("src and dst must be [B, D] and [M, D], got {} and {}".format(
+            tuple(src.shape), tuple(dst.shape)))
+    (B, D), M = (int(n) for n in src.shape), int(dst.shape[0])
+    if dst.shape[1] != D:
+        raise ValueError("src has {} columns, dst has {}".format(D, dst.shape[1]))
+    if D == 0:
+        raise ValueError("edge_score needs D >= 1")
+    if tuple(weight.shape) not in ((D,), (1, D)):
+        raise ValueError("weight must be [D] or [1, D] with D = {}, got {}".format(
+            D, tuple(weight.shape)))
+    if tuple(bias.shape) != (1,):
+        raise ValueError("bias must be [1], got {}".format(tuple(bias.shape)))
+    if M % B if B else M:
+        raise ValueError("dst has {} rows, not a multiple of the {} rows of src".format(M, B))
+    for name, x in (("src", src), ("weight", weight), ("bias", bias)):
+        if x.device != dst.device:
+            raise ValueError("{} is on {}, dst on {}".format(name, x.device, dst.device))
+    if dst.device.type != "cuda":
+        raise ValueError("edge_score runs on the GPU, the inputs are on {}".format(dst.device))
+    return _EdgeScore.apply(src.contiguous(), dst.contiguous(), weight.reshape(D).contiguous(),
+                            bias.contiguous())
 
 
 def block_max(block, src: torch.Tensor) -> torch.Tensor:

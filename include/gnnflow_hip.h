@@ -883,6 +883,34 @@ GF_API int gf_time_encode_backward(const float* d_t, const float* d_w, const flo
                                    size_t partial_rows, float* d_grad_w, float* d_grad_bias,
                                    int device, void* stream);
 
+/* Fused edge score (the tail of the reference's EdgePredictor, layers.py:186-197, after src_fc
+ * and dst_fc): d_src [num_src, dim], d_dst [num_dst, dim], d_w [dim], d_bias [1], d_out
+ * [num_dst], all fp32, row-major and contiguous; num_dst = r * num_src, row j of dst pairs with
+ * row j mod num_src of src,
+ *   out[j] = bias + sum_d w[d] * max(src[j mod num_src, d] + dst[j, d], 0)
+ * in one launch.  The order of summation depends on dim alone.  dim >= 1, num_dst a multiple of
+ * num_src >= 1 and fewer than 2^31 dst rows, else GF_ERR_INVALID_ARGUMENT; num_dst == 0
+ * launches nothing. */
+GF_API int gf_edge_score(const float* d_src, const float* d_dst, const float* d_w,
+                         const float* d_bias, size_t num_src, size_t num_dst, size_t dim,
+                         float* d_out, int device, void* stream);
+/* Rows of the caller-owned partials buffer gf_edge_score_backward needs for num_src src rows
+ * (at most 1024 whatever num_src is): the buffer holds rows * (dim + 1) floats. */
+GF_API int gf_edge_score_backward_partial_rows(size_t num_src, size_t* rows);
+/* Gradients of the edge score from g = d_grad_out [num_dst], with x[j,d] = src[j mod num_src, d]
+ * + dst[j, d]:
+ *   grad_dst[j,d] = x[j,d] > 0 ? g[j] * w[d] : 0
+ *   grad_src[i,d] = grad_dst[i,d] + grad_dst[i + num_src,d] + ...      (ascending)
+ *   grad_w[d]     = sum_j g[j] * max(x[j,d], 0)          grad_bias = sum_j g[j]
+ * in at most two launches, summed in a fixed order without atomics (bit-identical from run to
+ * run).  Any of d_grad_src, d_grad_dst, d_grad_w, d_grad_bias may be NULL (skipped); d_partials
+ * is needed only when d_grad_w or d_grad_bias is not NULL. */
+GF_API int gf_edge_score_backward(const float* d_src, const float* d_dst, const float* d_w,
+                                  size_t num_src, size_t num_dst, size_t dim,
+                                  const float* d_grad_out, float* d_partials, size_t partial_rows,
+                                  float* d_grad_src, float* d_grad_dst, float* d_grad_w,
+                                  float* d_grad_bias, int device, void* stream);
+
 /* ---- measurement support (bench.py) ---------------------------------------- */
 /* Accumulated device time of a kernel family since the last reset, measured with
  * HIP events recorded around each launch on the launching stream.
