@@ -1,6 +1,7 @@
 // Segment operations on a sampled block (block_ops.hip, block_attention.hip, block_gat.hip), the fused time
 // encoding in front of them (time_encode.hip) and the fused edge score behind them
-// (edge_score.hip): the entry points other translation units call.
+// (edge_score.hip), and the metrics of the scores it leaves (link_metrics.hip): the entry points
+// other translation units call.
 #pragma once
 
 #include <cstddef>
@@ -106,5 +107,23 @@ void edge_score_backward(const float* d_src, const float* d_dst, const float* d_
                          size_t num_dst, size_t dim, const float* d_grad_out, float* d_partials,
                          size_t partial_rows, float* d_grad_src, float* d_grad_dst,
                          float* d_grad_w, float* d_grad_bias, int device, hipStream_t stream);
+
+// link_metrics.hip: out[3] = {AP, AUC, MRR} (float64) of the scores pos[num_pos] of the true
+// edges and neg[num_neg] of the negative ones, by counting instead of sorting, in two launches
+// and without atomics.  MRR exists when num_neg is a multiple of num_pos (positive i's own
+// negatives are neg[k * num_pos + i], the layout of edge_score) and is NaN otherwise.  d_acc,
+// unless null, is the running sum of a validation pass: {sum_ap, sum_auc, sum_mrr, batches,
+// mrr_batches, nonfinite, reserved, reserved}.  A NaN or an infinity among the scores gives
+// three NaNs and adds 1 to nonfinite alone.  d_partials: link_metrics_partial_rows(num_pos)
+// rows of kLinkMetricsPartialWords 8-byte words, caller-owned.  num_pos, num_neg >= 1 and
+// num_pos + num_neg <= kLinkMetricsMaxScores, else GF_ERR_INVALID_ARGUMENT.
+constexpr size_t kLinkMetricsMaxScores = 65536;
+constexpr size_t kLinkMetricsTile = 2048;      // scores per LDS tile
+constexpr size_t kLinkMetricsMaxPartialRows = 256;
+constexpr size_t kLinkMetricsPartialWords = 4;
+size_t link_metrics_partial_rows(size_t num_pos);
+void link_metrics(const float* d_pos, const float* d_neg, size_t num_pos, size_t num_neg,
+                  void* d_partials, size_t partial_rows, double* d_out, double* d_acc, int device,
+                  hipStream_t stream);
 
 }  // namespace gf

@@ -1,6 +1,6 @@
 // extern "C" entry points of include/gnnflow_hip.h: thin, exception-free shims.  Here: the error
 // slot they all report through, the pid behind foreign_process(), the shims over free functions
-// (block ops, time encoding, edge score, debug counters).  Those over a handle: capi_{graph,sampler,cache,comm}.
+// (block ops, time encoding, edge score, link metrics, debug counters).  Those over a handle: capi_{graph,sampler,cache,comm}.
 #include "block_ops.hpp"
 #include "capi_handles.hpp"
 #include "partition.hpp"
@@ -197,6 +197,25 @@ int gf_edge_score_backward(const float* d_src, const float* d_dst, const float* 
     gf::edge_score_backward(d_src, d_dst, d_w, num_src, num_dst, dim, d_grad_out, d_partials,
                             partial_rows, d_grad_src, d_grad_dst, d_grad_w, d_grad_bias, device,
                             as_stream(stream));
+  });
+}
+
+static_assert(GF_LINK_METRICS_MAX_SCORES == gf::kLinkMetricsMaxScores &&
+                  GF_LINK_METRICS_TILE == gf::kLinkMetricsTile &&
+                  GF_LINK_METRICS_PARTIAL_WORDS == gf::kLinkMetricsPartialWords,
+              "gnnflow_hip.h and block_ops.hpp disagree on the link-metrics constants");
+int gf_link_metrics_partial_rows(size_t num_pos, size_t* rows) {
+  return guarded([&] {
+    GF_REQUIRE(rows != nullptr, "gf_link_metrics_partial_rows: null output");
+    *rows = gf::link_metrics_partial_rows(num_pos);
+  });
+}
+int gf_link_metrics(const float* d_pos, const float* d_neg, size_t num_pos, size_t num_neg,
+                    void* d_partials, size_t partial_rows, double* d_out, double* d_acc,
+                    int device, void* stream) {
+  return guarded([&] {
+    gf::link_metrics(d_pos, d_neg, num_pos, num_neg, d_partials, partial_rows, d_out, d_acc,
+                     device, as_stream(stream));
   });
 }
 

@@ -15,6 +15,10 @@ make on a sampled block, on HIP segment kernels (csrc/block_ops.hip) with autogr
     edge_score(src, dst, w, b)             out_fc(relu(src + dst)) of EdgePredictor (layers.py:195-197),
                                            every dst block against the one src block, in one launch
                                            (csrc/edge_score.hip)
+    link_metrics(pos, neg)                 average_precision_score / roc_auc_score of the reference's
+                                           evaluate() (scripts/offline_edge_prediction.py:141-146) and
+                                           the MRR, counted on the GPU without a sort, a sync or a copy
+                                           to the host (csrc/link_metrics.hip)
 
 A block's edges are grouped by destination (the sampler emits them that way); blocks built by
 hand with unordered edges are handled through a stable permutation.
@@ -654,6 +658,81 @@ def edge_score(src: torch.Tensor, dst: torch.Tensor, weight: torch.Tensor, bias:
         raise ValueError("edge_score runs on the GPU, the inputs are on {}".format(dst.device))
     return _EdgeScore.apply(src.contiguous(), dst.contiguous(), weight.reshape(D).contiguous(),
                             bias.contiguous())
+
+
+LINK_METRICS_MAX_SCORES = 65536      # GF_LINK_METRICS_MAX_SCORES: the limit on P + N
+LINK_METRICS_TILE = 2048             # GF_LINK_METRICS_TILE: scores per LDS tile of the kernel
+_LINK_METRICS_PARTIAL_WORDS = 4      # GF_LINK_METRICS_PARTIAL_WORDS
+
+
+def link_metrics(pos: torch.Tensor, neg: torch.Tensor,
+                 accumulator: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[AP, AUC, MRR] of one batch as a float64 tensor [3] on the GPU: sklearn's
+    average_precision_score and roc_auc_score of torch.cat([pos, neg]) against the labels
+    [1] * P + [0] * N, as the reference's evaluate() computes them per batch, and the mean
+    reciprocal rank of each positive among its own negatives.
+
+    pos: [P] or [P, 1], the scores of the true edges; neg: [N] or [N, 1], those of the negative
+    ones, as EdgePredictor returns them; float32 on one GPU, P >= 1, N >= 1 and
+    P + N <= LINK_METRICS_MAX_SCORES.  Both are detached; a non-contiguous input is copied.
+    MRR needs N = r * P with positive i's negatives at neg[k * P + i] (the block layout of
+    edge_score); its rank is 1 + #greater + #equal / 2, the mean of the optimistic and the
+    pessimistic rank.  When N is not a multiple of P it is NaN.
+
+    accumulator: a float64 [8] tensor on the same GPU, the running sums of a validation pass
+    (sum_ap, sum_auc, sum_mrr, batches, mrr_batches, nonfinite, 2 reserved), updated on the
+    device; metrics.LinkMetrics wraps it.  A NaN or an infinity among the scores (scikit-learn
+    raises) gives three NaNs and adds 1 to `nonfinite` alone.
+
+    Runs on the current stream and never synchronises.  Ties are counted, not broken, and the
+    sums run in a fixed order: the same inputs give the same bits.
+
+    The scores are ranked as given.  sigmoid is increasing, so ranking logits is ranking their
+    exact sigmoids; float32 torch.sigmoid saturates (to 1.0 from about 17 on, to 0 below about
+    -104) and rounds neighbouring logits to one value, so sigmoid(logits) has ties that the logits
+    do not have, and its metrics can differ from those of the logits.  Pass what you want ranked."""
+    for name, x in (("pos", pos), ("neg", neg)):
+        if not isinstance(x, torch.Tensor):
+            raise TypeError("{} must be a tensor, got {}".format(name, type(x).__name__))
+        if x.dtype != torch.float32:
+            raise TypeError("link_metrics ranks float32 scores, {} is {}".format(name, x.dtype))
+        if not (x.dim() == 1 or (x.dim() == 2 and x.shape[1] == 1)):
+            raise ValueError("{} must be [n] or [n, 1], got {}".format(name, tuple(x.shape)))
+    P, N = int(pos.shape[0]), int(neg.shape[0])
+    if P == 0 or N == 0:
+        raise ValueError("link_metrics needs at least one positive and one negative score, got "
+                         "{} and {}".format(P, N))
+    if P + N > LINK_METRICS_MAX_SCORES:
+        raise ValueError("link_metrics takes at most {} scores per call, got {} + {}".format(
+            LINK_METRICS_MAX_SCORES, P, N))
+    if neg.device != pos.device:
+        raise ValueError("neg is on {}, pos on {}".format(neg.device, pos.device))
+    if pos.device.type != "cuda":
+        raise ValueError("link_metrics runs on the GPU, the inputs are on {}".format(pos.device))
+    acc = accumulator
+    if acc is not None:
+        if not isinstance(acc, torch.Tensor):
+            raise TypeError("accumulator must be a tensor, got {}".format(type(acc).__name__))
+        if acc.dtype != torch.float64:
+            raise TypeError("accumulator must be float64, got {}".format(acc.dtype))
+        if tuple(acc.shape) != (8,) or not acc.is_contiguous():
+            raise ValueError("accumulator must be a contiguous [8] tensor, got {}".format(
+                tuple(acc.shape)))
+        if acc.device != pos.device:
+            raise ValueError("accumulator is on {}, pos on {}".format(acc.device, pos.device))
+    p = pos.detach().reshape(P).contiguous()
+    n = neg.detach().reshape(N).contiguous()
+    lib = _capi.load()
+    rows = C.c_size_t(0)
+    _capi.check(lib.gf_link_metrics_partial_rows(P, C.byref(rows)))
+    f64 = dict(dtype=torch.float64, device=p.device)
+    partials = torch.empty((rows.value, _LINK_METRICS_PARTIAL_WORDS), **f64)
+    out = torch.empty(3, **f64)
+    with torch.cuda.device(p.device):
+        _capi.check(lib.gf_link_metrics(
+            p.data_ptr(), n.data_ptr(), P, N, partials.data_ptr(), rows.value, out.data_ptr(),
+            _ptr(acc), p.device.index, _stream(p.device)))
+    return out
 
 
 def block_max(block, src: torch.Tensor) -> torch.Tensor:

@@ -911,6 +911,37 @@ GF_API int gf_edge_score_backward(const float* d_src, const float* d_dst, const 
                                   float* d_grad_src, float* d_grad_dst, float* d_grad_w,
                                   float* d_grad_bias, int device, void* stream);
 
+/* Link-prediction metrics of one validation batch from the scores d_pos [num_pos] of its true
+ * edges and d_neg [num_neg] of its negative ones (float32, compared as IEEE compares them, so
+ * -0 == +0): d_out[3] = {AP, AUC, MRR} as float64, what scikit-learn's average_precision_score
+ * and roc_auc_score give for the concatenated scores with labels 1 / 0.  Nothing is sorted; with
+ *   pge_i = #{j : pos[j] >= pos[i]}   nge_i = #{k : neg[k] >= pos[i]}
+ *   nlt_i = #{k : neg[k] <  pos[i]}   neq_i = #{k : neg[k] == pos[i]}
+ *   AP  = (1 / num_pos) sum_i pge_i / (pge_i + nge_i)
+ *   AUC = (sum_i (2 nlt_i + neq_i)) / (2 num_pos num_neg)
+ *   MRR = (1 / num_pos) sum_i 1 / (1 + gt_i + eq_i / 2)
+ * where gt_i / eq_i count positive i's OWN negatives d_neg[k * num_pos + i], k < num_neg /
+ * num_pos (the block layout of gf_edge_score), that are > / == d_pos[i]: the mean of the
+ * optimistic and the pessimistic rank.  MRR is NaN when num_neg is not a multiple of num_pos.
+ * Two launches on `stream`, no atomics, sums in a fixed order: the same inputs give the same
+ * bits, and the host never waits.
+ * d_acc (may be NULL) is a caller-owned running sum of 8 doubles: {sum_ap, sum_auc, sum_mrr,
+ * batches, mrr_batches, nonfinite, reserved, reserved}.  A call adds its AP and AUC and 1 to
+ * batches, and, when it has an MRR, the MRR and 1 to mrr_batches.  If any score is NaN or
+ * infinite the three outputs are NaN, nonfinite grows by 1 and no other field changes.
+ * d_partials: caller-owned scratch of rows * GF_LINK_METRICS_PARTIAL_WORDS 8-byte words, 8-byte
+ * aligned, rows from gf_link_metrics_partial_rows(num_pos) (at most 256).  The scores pass
+ * through LDS in tiles of GF_LINK_METRICS_TILE.  NULL d_pos, d_neg, d_partials or d_out,
+ * num_pos == 0, num_neg == 0 or num_pos + num_neg > GF_LINK_METRICS_MAX_SCORES:
+ * GF_ERR_INVALID_ARGUMENT. */
+#define GF_LINK_METRICS_MAX_SCORES 65536
+#define GF_LINK_METRICS_TILE 2048
+#define GF_LINK_METRICS_PARTIAL_WORDS 4
+GF_API int gf_link_metrics_partial_rows(size_t num_pos, size_t* rows);
+GF_API int gf_link_metrics(const float* d_pos, const float* d_neg, size_t num_pos,
+                           size_t num_neg, void* d_partials, size_t partial_rows, double* d_out,
+                           double* d_acc, int device, void* stream);
+
 /* ---- measurement support (bench.py) ---------------------------------------- */
 /* Accumulated device time of a kernel family since the last reset, measured with
  * HIP events recorded around each launch on the launching stream.
