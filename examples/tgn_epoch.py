@@ -14,6 +14,12 @@ epoch and the split sample / fetch / memory gather / memory update / model / wri
 reference's loop accumulates them (the sample time is what the prefetch does not hide).
 
     python examples/tgn_epoch.py [--nodes 1220000 --edges 13000000 --epochs 2]
+
+--fused-attention takes the attention as one ops.block_attention call also without dropout (the
+default run keeps the composed edge_softmax -> block_reduce chain of the recorded profiles).
+--amp runs the memory updater, the model and the loss under torch.autocast('cuda',
+dtype=torch.bfloat16) and implies --fused-attention: the composed chain is float32 only, while
+ops.block_attention takes the bfloat16 q, k, v of the Linear layers as they come.
 """
 import argparse
 from collections import deque
@@ -47,7 +53,10 @@ class TimeEncoding(nn.Module):
             self.lin.bias.zero_()
 
     def forward(self, dt):
-        return torch.cos(self.lin(dt.reshape(-1, 1)))
+        # float32 also under autocast, as nn.TimeEncode on ops.time_encode is: a bfloat16
+        # Linear(1, dim) would round the raw time deltas to 8 bits before the cosine
+        with torch.autocast("cuda", enabled=False):
+            return torch.cos(self.lin(dt.reshape(-1, 1).float()))
 
 
 class MemoryUpdater(nn.Module):
@@ -62,7 +71,7 @@ class MemoryUpdater(nn.Module):
 
     def forward(self, b):
         x = torch.cat([b.srcdata['mem_input'], self.time(b.srcdata['ts'] - b.srcdata['mem_ts'])], 1)
-        new_mem = self.cell(x, b.srcdata['mem'])
+        new_mem = self.cell(x, b.srcdata['mem']).float()      # bfloat16 under autocast
         R = b.num_dst_nodes()
         last = dict(last_updated_nid=b.srcdata['ID'][:R].detach(),
                     last_updated_memory=new_mem[:R].detach().clone(),
@@ -78,10 +87,11 @@ class Attention(nn.Module):
     att_dropout > 0: in training the attention is one ops.block_attention call with the dropout
     on the attention weights inside it (a seed per forward from torch's CPU generator)."""
 
-    def __init__(self, dim_node, dim_time, dim_out, heads, att_dropout=0.0):
+    def __init__(self, dim_node, dim_time, dim_out, heads, att_dropout=0.0, fused=False):
         super().__init__()
         self.heads = heads
         self.att_dropout = att_dropout
+        self.fused = fused      # one ops.block_attention call also without dropout
         self.time = TimeEncoding(dim_time)
         self.q = nn.Linear(dim_node + dim_time, dim_out)
         self.k = nn.Linear(dim_node + dim_time, dim_out)
@@ -105,7 +115,10 @@ class Attention(nn.Module):
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64))
             agg = ops.block_attention(b, q, k, v, heads=H, dropout_p=self.att_dropout,
                                       dropout_seed=seed).reshape(R, -1)
-            return self.norm(F.relu(self.out(torch.cat([agg, dst_h], 1))))
+            return self.norm(F.relu(self.out(torch.cat([agg, dst_h.to(agg.dtype)], 1))))
+        if self.fused:
+            agg = ops.block_attention(b, q, k, v, heads=H).reshape(R, -1)
+            return self.norm(F.relu(self.out(torch.cat([agg, dst_h.to(agg.dtype)], 1))))
         q = q[row]
         score = F.leaky_relu((q.view(E, H, -1) * k.view(E, H, -1)).sum(2), 0.2)
         att = ops.edge_softmax(b, score)                       # [E, H]
@@ -128,10 +141,10 @@ class EdgeScorer(nn.Module):
 
 class TGN(nn.Module):
     def __init__(self, dim_node, dim_time=100, dim_embed=100, dim_memory=100, heads=2,
-                 att_dropout=0.0):
+                 att_dropout=0.0, fused_attention=False):
         super().__init__()
         self.updater = MemoryUpdater(dim_node, 0, dim_time, dim_memory)
-        self.att = Attention(dim_memory, dim_time, dim_embed, heads, att_dropout)
+        self.att = Attention(dim_memory, dim_time, dim_embed, heads, att_dropout, fused_attention)
         self.score = EdgeScorer(dim_embed)
 
     def forward(self, mfgs):
@@ -149,7 +162,14 @@ def main():
     ap.add_argument("--max-batches", type=int, default=0)
     ap.add_argument("--att-dropout", type=float, default=0.0,
                     help="attention dropout, inside ops.block_attention (0: none, the default run)")
+    ap.add_argument("--fused-attention", action="store_true",
+                    help="the attention as one ops.block_attention call also without dropout")
+    ap.add_argument("--amp", action="store_true",
+                    help="bfloat16 autocast around updater, model and loss (implies "
+                         "--fused-attention)")
     args = ap.parse_args()
+    fused = args.fused_attention or args.amp
+    amp = torch.autocast("cuda", dtype=torch.bfloat16, enabled=args.amp)
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     N, E, B = args.nodes, args.edges, args.batch
@@ -166,7 +186,7 @@ def main():
     node_feats = torch.rand((N, args.dim_node), device=dev)
     cache = LRUCache(0.0, 0.2, N, E, dev, node_feats, None, args.dim_node, 0)
     cache.init_cache()
-    model = TGN(args.dim_node, att_dropout=args.att_dropout).to(dev)
+    model = TGN(args.dim_node, att_dropout=args.att_dropout, fused_attention=fused).to(dev)
     memory = Memory(N, 0, 100, dev)
     opt = torch.optim.Adam(model.parameters(), lr=1e-4)
     n_train = int(E * args.train_frac)
@@ -217,16 +237,19 @@ def main():
             b = mfgs[0][0]
             memory.prepare_input(b)
             t3 = time.perf_counter()
-            last = model.updater(b)
+            with amp:
+                last = model.updater(b)
             t4 = time.perf_counter()
             opt.zero_grad()
-            pos, neg = model(mfgs)
+            with amp:
+                pos, neg = model(mfgs)
             t5 = time.perf_counter()
             with torch.no_grad():
                 memory.update_mem_mail(**last, edge_feats=None, neg_sample_ratio=1)
             t6 = time.perf_counter()
-            loss = F.binary_cross_entropy_with_logits(pos, torch.ones_like(pos)) + \
-                F.binary_cross_entropy_with_logits(neg, torch.zeros_like(neg))
+            with amp:
+                loss = F.binary_cross_entropy_with_logits(pos, torch.ones_like(pos)) + \
+                    F.binary_cross_entropy_with_logits(neg, torch.zeros_like(neg))
             loss.backward()
             opt.step()
             t7 = time.perf_counter()
@@ -255,7 +278,8 @@ def main():
                   "accumulates it (stages are asynchronous: GPU time shows up where the host "
                   "next waits — mostly in `model`, whose loss read-back synchronises)",
         "graph_build_s": round(build_s, 2), "epochs": out,
-        **({"att_dropout": args.att_dropout} if args.att_dropout else {})}))
+        **({"att_dropout": args.att_dropout} if args.att_dropout else {}),
+        **({"fused_attention": True} if fused else {}), **({"amp": "bfloat16"} if args.amp else {})}))
 
 
 if __name__ == "__main__":

@@ -4,7 +4,16 @@ scripts/offline_edge_prediction.py, on this package only: batches from
 2-layer GraphSAGE (`gnnflow_amd.nn.SAGEConv`, the layer the reference's GRAPHSAGE model uses) and
 a dot-product edge scorer.  Synthetic REDDIT-shaped data; a usage example, not a benchmark.
 
-    python examples/train_edge_prediction.py [--batches 50]
+    python examples/train_edge_prediction.py [--batches 50] [--amp]
+
+--amp runs the forward and the loss under torch.autocast('cuda', dtype=torch.bfloat16).  No
+GradScaler: bfloat16 has float32's range.  SAGEConv's block ops are float32 only, so the model
+widens the first layer's output before the second.  That is enough for the widths used here
+(in_feats <= out_feats in both layers, so each layer aggregates its float32 input and applies
+fc_neigh afterwards); a SAGEConv that shrinks its rows applies fc_neigh first and would hand
+ops.block_reduce bfloat16 under autocast, which raises TypeError.  models.DGNN needs no such
+care: ops.block_attention, time_encode_cat and edge_score take the bfloat16 tensors autocast
+produces (examples/tgn_epoch.py --amp).
 """
 import argparse
 import os
@@ -37,14 +46,15 @@ class SAGE(nn.Module):
 
     def forward(self, mfgs):
         # mfgs[0] is the outer (largest) layer, mfgs[-1] the roots' layer
-        h = F.relu(self.l0(mfgs[0][0], mfgs[0][0].srcdata['h']))
+        # .float(): ops.block_reduce is float32 only (a no-op outside autocast)
+        h = F.relu(self.l0(mfgs[0][0], mfgs[0][0].srcdata['h'])).float()
         h = self.l1(mfgs[1][0], h)
         b = h.shape[0] // 3                     # roots = [src | dst | negative dst]
         src, pos, neg = h[:b], h[b:2 * b], h[2 * b:]
         return self.score(src * pos), self.score(src * neg)
 
 
-def main(num_batches=50, batch_size=600, seed=0, verbose=True):
+def main(num_batches=50, batch_size=600, seed=0, verbose=True, amp=False):
     import pandas as pd
     torch.manual_seed(seed)
     dev = torch.device("cuda", 0)
@@ -69,9 +79,10 @@ def main(num_batches=50, batch_size=600, seed=0, verbose=True):
             break
         mfgs = sampler.sample(roots, ts)
         cache.fetch_feature(mfgs, eid)
-        pos, neg = model(mfgs)
-        loss = F.binary_cross_entropy_with_logits(pos, torch.ones_like(pos)) + \
-            F.binary_cross_entropy_with_logits(neg, torch.zeros_like(neg))
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+            pos, neg = model(mfgs)
+            loss = F.binary_cross_entropy_with_logits(pos, torch.ones_like(pos)) + \
+                F.binary_cross_entropy_with_logits(neg, torch.zeros_like(neg))
         opt.zero_grad()
         loss.backward()
         opt.step()
@@ -85,4 +96,6 @@ def main(num_batches=50, batch_size=600, seed=0, verbose=True):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, default=50)
-    main(ap.parse_args().batches)
+    ap.add_argument("--amp", action="store_true", help="bfloat16 autocast around forward and loss")
+    args = ap.parse_args()
+    main(args.batches, amp=args.amp)

@@ -254,13 +254,22 @@ PROTOTYPES = {
                                            _p, C.c_int, _p]),
     "gf_block_attention": (C.c_int, [_p, _sz, _sz, _sz, _sz, _p, _p, _p, C.c_float, _p, _p,
                                      C.c_int, _p]),
+    "gf_block_attention_bf16": (C.c_int, [_p, _sz, _sz, _sz, _sz, _p, _p, _p, C.c_float, _p, _p,
+                                          C.c_int, _p]),
     "gf_block_attention_backward": (C.c_int, [_p, _sz, _sz, _sz, _sz, _p, _p, _p, _p, C.c_float,
                                               _p, _p, _p, _p, C.c_int, _p]),
+    "gf_block_attention_bf16_backward": (C.c_int, [_p, _sz, _sz, _sz, _sz, _p, _p, _p, _p, C.c_float,
+                                                   _p, _p, _p, _p, C.c_int, _p]),
     "gf_block_attention_dropout": (C.c_int, [_p, _sz, _sz, _sz, _sz, _p, _p, _p, C.c_float,
                                              C.c_float, C.c_uint64, _p, _p, _p, C.c_int, _p]),
+    "gf_block_attention_dropout_bf16": (C.c_int, [_p, _sz, _sz, _sz, _sz, _p, _p, _p, C.c_float,
+                                                  C.c_float, C.c_uint64, _p, _p, _p, C.c_int, _p]),
     "gf_block_attention_dropout_backward": (C.c_int, [_p, _sz, _sz, _sz, _sz, _p, _p, _p, _p,
                                                       C.c_float, C.c_float, C.c_uint64, _p, _p,
                                                       _p, _p, C.c_int, _p]),
+    "gf_block_attention_dropout_bf16_backward": (C.c_int, [_p, _sz, _sz, _sz, _sz, _p, _p, _p, _p,
+                                                           C.c_float, C.c_float, C.c_uint64, _p, _p,
+                                                           _p, _p, C.c_int, _p]),
     "gf_block_gat": (C.c_int, [_p, _sz, _sz, _p, _sz, _sz, _sz, _p, _p, _p, C.c_float, C.c_float,
                                C.c_uint64, _p, _p, _p, C.c_int, _p]),
     "gf_block_gat_backward": (C.c_int, [_p, _sz, _sz, _p, _sz, _sz, _sz, _p, _p, _p, _p, _p,
@@ -269,13 +278,19 @@ PROTOTYPES = {
     "gf_block_reduce_max": (C.c_int, [_p, _sz, _p, _p, _sz, _p, _p, C.c_int, _p]),
     "gf_block_reduce_max_backward": (C.c_int, [_sz, _p, _sz, _p, _p, _p, _sz, C.c_int, _p]),
     "gf_time_encode_cat": (C.c_int, [_p, _sz, _p, _sz, _p, _p, _p, _sz, _sz, _p, C.c_int, _p]),
+    "gf_time_encode_cat_bf16": (C.c_int, [_p, _sz, _p, _sz, _p, _p, _p, _sz, _sz, _p, C.c_int, _p]),
     "gf_time_encode_backward_partial_rows": (C.c_int, [_sz, C.POINTER(_sz)]),
     "gf_time_encode_backward": (C.c_int, [_p, _p, _p, _sz, _sz, _p, _sz, _sz, _p, _sz, _p, _p,
                                           C.c_int, _p]),
+    "gf_time_encode_backward_bf16": (C.c_int, [_p, _p, _p, _sz, _sz, _p, _sz, _sz, _p, _sz, _p, _p,
+                                               C.c_int, _p]),
     "gf_edge_score": (C.c_int, [_p, _p, _p, _p, _sz, _sz, _sz, _p, C.c_int, _p]),
+    "gf_edge_score_bf16": (C.c_int, [_p, _p, _p, _p, _sz, _sz, _sz, _p, C.c_int, _p]),
     "gf_edge_score_backward_partial_rows": (C.c_int, [_sz, C.POINTER(_sz)]),
     "gf_edge_score_backward": (C.c_int, [_p, _p, _p, _sz, _sz, _sz, _p, _p, _sz, _p, _p, _p, _p,
                                          C.c_int, _p]),
+    "gf_edge_score_backward_bf16": (C.c_int, [_p, _p, _p, _sz, _sz, _sz, _p, _p, _sz, _p, _p, _p, _p,
+                                              C.c_int, _p]),
     "gf_link_metrics_partial_rows": (C.c_int, [_sz, C.POINTER(_sz)]),
     "gf_link_metrics": (C.c_int, [_p, _p, _sz, _sz, _p, _sz, _p, _p, C.c_int, _p]),
     "gf_debug_part_host_us": (C.c_int, [C.POINTER(C.c_double), C.c_int]),

@@ -36,68 +36,15 @@
 // propagate, unlike 0 * inf = NaN in the composed edge_softmax -> dropout -> block_reduce chain.
 // The kernels without dropout are kept as they were and compile to the code they had before
 // dropout existed.
-#include "block_ops.hpp"
-#include "common.hpp"
-#include "../../include/gnnflow_rng.h"
-
-#include <cfloat>
-#include <cstdint>
+//
+// block_attention_bf16.hip holds these four kernels once more for bfloat16 q, k, v, out and
+// gradients: the same bodies with widen() on the loads and narrow() on the stores.  A fix to a
+// kernel here must be made there too (tests/test_gpu_block_attention_bf16.py holds the two bit
+// for bit together).  What both files share is in block_attention_common.hpp.
+#include "block_attention_common.hpp"
 
 namespace gf {
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kMaxChunks = 16;   // columns per lane of a 64-lane group: D <= 64 * 16
-
-template <int G>
-__device__ inline float group_sum(float v) {
-#pragma unroll
-  for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// value of lane `j` of the caller's group
-template <int G>
-__device__ inline float group_read(float v, int j) {
-  return __shfl(v, ((threadIdx.x & 63) & ~(G - 1)) + j, 64);
-}
-
-// sum_c a[c] * row[c] over the head's D columns; a[] holds the lane's columns of the other
-// operand (0 past D).  The same value in every lane of the group.
-template <int G, int NC>
-__device__ inline float head_dot(const float (&a)[NC], const float* __restrict__ row,
-                                 uint32_t D, uint32_t lig) {
-  float p = 0.f;
-#pragma unroll
-  for (int j = 0; j < NC; ++j) {
-    const uint32_t c = lig + G * j;
-    if (c < D) p += a[j] * row[c];
-  }
-  return group_sum<G>(p);
-}
-
-template <int G, int NC>
-__device__ inline void load_head(float (&a)[NC], const float* __restrict__ row, uint32_t D,
-                                 uint32_t lig) {
-#pragma unroll
-  for (int j = 0; j < NC; ++j) {
-    const uint32_t c = lig + G * j;
-    a[j] = c < D ? row[c] : 0.f;
-  }
-}
-
-__device__ inline float leaky(float z, float slope) { return z > 0.f ? z : slope * z; }
-
-// what the dropout kernels need besides the attention's own arguments
-struct Dropout {
-  uint32_t threshold;   // T: kept <=> philox >= T
-  float scale;          // 1 / (1 - p)
-  uint64_t seed;
-};
-
-__device__ inline bool kept(const Dropout& dr, uint64_t edge, uint32_t H, uint32_t h) {
-  return gf_philox4x32_10_first(dr.seed, edge * H + h, 0) >= dr.threshold;
-}
 
 template <int G, int NC>
 __global__ void block_attention_fwd(const int64_t* __restrict__ offsets, uint64_t items,
@@ -412,12 +359,6 @@ __global__ void block_attention_dropout_bwd(
   }
 }
 
-struct Shape {
-  const int64_t* offsets;
-  uint64_t items;
-  uint32_t H, D;
-};
-
 template <int G, int NC>
 void launch_fwd(const Shape& s, const float* q, const float* k, const float* v, float slope,
                 float* out, float* att, hipStream_t stream) {
@@ -457,19 +398,6 @@ void launch_dropout_bwd(const Shape& s, const float* q, const float* k, const fl
          stream>>>(s.offsets, s.items, s.H, s.D, q, k, v, att, slope, dr, gout, gq, gk, gv);
 }
 
-// calls f.template operator()<G, NC>() for the group size / columns per lane of a D-column head
-template <class F>
-void dispatch(uint32_t D, F&& f) {
-  if (D <= 8) f.template operator()<8, 1>();
-  else if (D <= 16) f.template operator()<16, 1>();
-  else if (D <= 32) f.template operator()<32, 1>();
-  else if (D <= 64) f.template operator()<64, 1>();
-  else if (D <= 128) f.template operator()<64, 2>();
-  else if (D <= 256) f.template operator()<64, 4>();
-  else if (D <= 512) f.template operator()<64, 8>();
-  else f.template operator()<64, kMaxChunks>();
-}
-
 struct Fwd {
   Shape s; const float *q, *k, *v; float slope; float *out, *att; hipStream_t stream;
   template <int G, int NC> void operator()() {
@@ -498,26 +426,6 @@ struct DropoutBwd {
     launch_dropout_bwd<G, NC>(s, q, k, v, att, slope, dr, gout, gq, gk, gv, stream);
   }
 };
-
-Shape checked_shape(const int64_t* d_offsets, size_t num_dst, size_t heads, size_t head_dim) {
-  GF_REQUIRE(heads >= 1 && head_dim >= 1, "block_attention: heads and head_dim must be >= 1");
-  GF_REQUIRE(heads <= kBlockAttentionMaxWidth && head_dim <= kBlockAttentionMaxWidth &&
-                 heads * head_dim <= kBlockAttentionMaxWidth,
-             "block_attention: heads * head_dim exceeds GF_BLOCK_ATTENTION_MAX_WIDTH (1024)");
-  static_assert(kBlockAttentionMaxWidth <= 64 * kMaxChunks, "a head must fit one group");
-  GF_REQUIRE(d_offsets != nullptr, "block_attention: null offsets");
-  // one group of up to 64 lanes per (destination, head): the grid stays below 2^31 blocks
-  GF_REQUIRE(num_dst <= (size_t{1} << 32) / heads, "block_attention: too many destinations");
-  return Shape{d_offsets, static_cast<uint64_t>(num_dst) * heads, static_cast<uint32_t>(heads),
-               static_cast<uint32_t>(head_dim)};
-}
-
-// T and 1 / (1 - p) of the mask definition (gnnflow_hip.h); p is an fp32 value in [0, 1)
-Dropout checked_dropout(float p, uint64_t seed) {
-  GF_REQUIRE(p >= 0.f && p < 1.f, "block_attention: dropout p must be in [0, 1)");   // NaN fails
-  return Dropout{static_cast<uint32_t>(static_cast<double>(p) * 4294967296.0), 1.0f / (1.0f - p),
-                 seed};
-}
 
 }  // namespace
 

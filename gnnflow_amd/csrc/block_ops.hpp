@@ -59,6 +59,34 @@ void block_attention_dropout_backward(const int64_t* d_offsets, size_t num_dst, 
                                       const float* d_grad_out, float* d_grad_q, float* d_grad_k,
                                       float* d_grad_v, int device, hipStream_t stream);
 
+// block_attention_bf16.hip: the four entry points above for bfloat16 q, k, v, out and gradients
+// (uint16_t; d_att and d_att_dropped stay float32): widened on load, the float32 kernels'
+// arithmetic, one rounding to nearest even on store.  The same checks.
+void block_attention_bf16_forward(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                                  size_t heads, size_t head_dim, const uint16_t* d_q,
+                                  const uint16_t* d_k, const uint16_t* d_v, float negative_slope,
+                                  uint16_t* d_out, float* d_att, int device, hipStream_t stream);
+void block_attention_bf16_backward(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                                   size_t heads, size_t head_dim, const uint16_t* d_q,
+                                   const uint16_t* d_k, const uint16_t* d_v, const float* d_att,
+                                   float negative_slope, const uint16_t* d_grad_out,
+                                   uint16_t* d_grad_q, uint16_t* d_grad_k, uint16_t* d_grad_v,
+                                   int device, hipStream_t stream);
+void block_attention_dropout_bf16_forward(const int64_t* d_offsets, size_t num_dst,
+                                          size_t num_edges, size_t heads, size_t head_dim,
+                                          const uint16_t* d_q, const uint16_t* d_k,
+                                          const uint16_t* d_v, float negative_slope, float p,
+                                          uint64_t seed, uint16_t* d_out, float* d_att,
+                                          float* d_att_dropped, int device, hipStream_t stream);
+void block_attention_dropout_bf16_backward(const int64_t* d_offsets, size_t num_dst,
+                                           size_t num_edges, size_t heads, size_t head_dim,
+                                           const uint16_t* d_q, const uint16_t* d_k,
+                                           const uint16_t* d_v, const float* d_att,
+                                           float negative_slope, float p, uint64_t seed,
+                                           const uint16_t* d_grad_out, uint16_t* d_grad_q,
+                                           uint16_t* d_grad_k, uint16_t* d_grad_v, int device,
+                                           hipStream_t stream);
+
 // block_gat.hip: fused GAT attention, z[e,h] = el[src(e),h] + er[d,h], the source rows both key
 // and value (feat [num_src, heads, head_dim]).  d_col null = the sampler's layout src(e) =
 // num_dst + e (then num_src must be num_dst + num_edges; the backward is free of atomics), else
@@ -92,6 +120,18 @@ void time_encode_backward(const float* d_t, const float* d_w, const float* d_bia
                           size_t dim_time, const float* d_grad_out, size_t grad_pitch,
                           size_t grad_col, float* d_partials, size_t partial_rows,
                           float* d_grad_w, float* d_grad_bias, int device, hipStream_t stream);
+// The same with a bfloat16 d_out (float32 parts, t, w, bias; each value rounded once on store)
+// and with a bfloat16 d_grad_out (widened on load; partials, grad_w and grad_bias float32, in
+// the float32 path's summation order).
+void time_encode_cat_bf16_forward(const float* d_a, size_t width_a, const float* d_b,
+                                  size_t width_b, const float* d_t, const float* d_w,
+                                  const float* d_bias, size_t n, size_t dim_time, uint16_t* d_out,
+                                  int device, hipStream_t stream);
+void time_encode_backward_bf16(const float* d_t, const float* d_w, const float* d_bias, size_t n,
+                               size_t dim_time, const uint16_t* d_grad_out, size_t grad_pitch,
+                               size_t grad_col, float* d_partials, size_t partial_rows,
+                               float* d_grad_w, float* d_grad_bias, int device,
+                               hipStream_t stream);
 
 // edge_score.hip: out[j] = bias + sum_d w[d] * max(src[j mod num_src, d] + dst[j, d], 0) in one
 // launch (num_dst a multiple of num_src), and its gradients in at most two.  The backward needs
@@ -107,6 +147,16 @@ void edge_score_backward(const float* d_src, const float* d_dst, const float* d_
                          size_t num_dst, size_t dim, const float* d_grad_out, float* d_partials,
                          size_t partial_rows, float* d_grad_src, float* d_grad_dst,
                          float* d_grad_w, float* d_grad_bias, int device, hipStream_t stream);
+// The same with bfloat16 src and dst rows and bfloat16 grad_src / grad_dst (widened on load,
+// rounded once on store); w, bias, out, grad_out, the partials, grad_w and grad_bias float32.
+void edge_score_bf16_forward(const uint16_t* d_src, const uint16_t* d_dst, const float* d_w,
+                             const float* d_bias, size_t num_src, size_t num_dst, size_t dim,
+                             float* d_out, int device, hipStream_t stream);
+void edge_score_bf16_backward(const uint16_t* d_src, const uint16_t* d_dst, const float* d_w,
+                              size_t num_src, size_t num_dst, size_t dim, const float* d_grad_out,
+                              float* d_partials, size_t partial_rows, uint16_t* d_grad_src,
+                              uint16_t* d_grad_dst, float* d_grad_w, float* d_grad_bias,
+                              int device, hipStream_t stream);
 
 // link_metrics.hip: out[3] = {AP, AUC, MRR} (float64) of the scores pos[num_pos] of the true
 // edges and neg[num_neg] of the negative ones, by counting instead of sorting, in two launches

@@ -126,6 +126,56 @@ int gf_block_attention_dropout_backward(const int64_t* d_offsets, size_t num_dst
   });
 }
 
+int gf_block_attention_bf16(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                            size_t heads, size_t head_dim, const uint16_t* d_q,
+                            const uint16_t* d_k, const uint16_t* d_v, float negative_slope,
+                            uint16_t* d_out, float* d_att, int device, void* stream) {
+  return guarded([&] {
+    gf::block_attention_bf16_forward(d_offsets, num_dst, num_edges, heads, head_dim, d_q, d_k,
+                                     d_v, negative_slope, d_out, d_att, device,
+                                     as_stream(stream));
+  });
+}
+int gf_block_attention_bf16_backward(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                                     size_t heads, size_t head_dim, const uint16_t* d_q,
+                                     const uint16_t* d_k, const uint16_t* d_v, const float* d_att,
+                                     float negative_slope, const uint16_t* d_grad_out,
+                                     uint16_t* d_grad_q, uint16_t* d_grad_k, uint16_t* d_grad_v,
+                                     int device, void* stream) {
+  return guarded([&] {
+    gf::block_attention_bf16_backward(d_offsets, num_dst, num_edges, heads, head_dim, d_q, d_k,
+                                      d_v, d_att, negative_slope, d_grad_out, d_grad_q, d_grad_k,
+                                      d_grad_v, device, as_stream(stream));
+  });
+}
+int gf_block_attention_dropout_bf16(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                                    size_t heads, size_t head_dim, const uint16_t* d_q,
+                                    const uint16_t* d_k, const uint16_t* d_v,
+                                    float negative_slope, float p, uint64_t seed, uint16_t* d_out,
+                                    float* d_att, float* d_att_dropped, int device,
+                                    void* stream) {
+  return guarded([&] {
+    gf::block_attention_dropout_bf16_forward(d_offsets, num_dst, num_edges, heads, head_dim, d_q,
+                                             d_k, d_v, negative_slope, p, seed, d_out, d_att,
+                                             d_att_dropped, device, as_stream(stream));
+  });
+}
+int gf_block_attention_dropout_bf16_backward(const int64_t* d_offsets, size_t num_dst,
+                                             size_t num_edges, size_t heads, size_t head_dim,
+                                             const uint16_t* d_q, const uint16_t* d_k,
+                                             const uint16_t* d_v, const float* d_att,
+                                             float negative_slope, float p, uint64_t seed,
+                                             const uint16_t* d_grad_out, uint16_t* d_grad_q,
+                                             uint16_t* d_grad_k, uint16_t* d_grad_v, int device,
+                                             void* stream) {
+  return guarded([&] {
+    gf::block_attention_dropout_bf16_backward(d_offsets, num_dst, num_edges, heads, head_dim, d_q,
+                                              d_k, d_v, d_att, negative_slope, p, seed,
+                                              d_grad_out, d_grad_q, d_grad_k, d_grad_v, device,
+                                              as_stream(stream));
+  });
+}
+
 int gf_block_gat(const int64_t* d_offsets, size_t num_dst, size_t num_edges, const int64_t* d_col,
                  size_t num_src, size_t heads, size_t head_dim, const float* d_feat,
                  const float* d_el, const float* d_er, float negative_slope, float p,
@@ -174,6 +224,26 @@ int gf_time_encode_backward(const float* d_t, const float* d_w, const float* d_b
   });
 }
 
+int gf_time_encode_cat_bf16(const float* d_a, size_t width_a, const float* d_b, size_t width_b,
+                            const float* d_t, const float* d_w, const float* d_bias, size_t n,
+                            size_t dim_time, uint16_t* d_out, int device, void* stream) {
+  return guarded([&] {
+    gf::time_encode_cat_bf16_forward(d_a, width_a, d_b, width_b, d_t, d_w, d_bias, n, dim_time,
+                                     d_out, device, as_stream(stream));
+  });
+}
+int gf_time_encode_backward_bf16(const float* d_t, const float* d_w, const float* d_bias,
+                                 size_t n, size_t dim_time, const uint16_t* d_grad_out,
+                                 size_t grad_pitch, size_t grad_col, float* d_partials,
+                                 size_t partial_rows, float* d_grad_w, float* d_grad_bias,
+                                 int device, void* stream) {
+  return guarded([&] {
+    gf::time_encode_backward_bf16(d_t, d_w, d_bias, n, dim_time, d_grad_out, grad_pitch, grad_col,
+                                  d_partials, partial_rows, d_grad_w, d_grad_bias, device,
+                                  as_stream(stream));
+  });
+}
+
 int gf_edge_score(const float* d_src, const float* d_dst, const float* d_w, const float* d_bias,
                   size_t num_src, size_t num_dst, size_t dim, float* d_out, int device,
                   void* stream) {
@@ -197,6 +267,26 @@ int gf_edge_score_backward(const float* d_src, const float* d_dst, const float* 
     gf::edge_score_backward(d_src, d_dst, d_w, num_src, num_dst, dim, d_grad_out, d_partials,
                             partial_rows, d_grad_src, d_grad_dst, d_grad_w, d_grad_bias, device,
                             as_stream(stream));
+  });
+}
+
+int gf_edge_score_bf16(const uint16_t* d_src, const uint16_t* d_dst, const float* d_w,
+                       const float* d_bias, size_t num_src, size_t num_dst, size_t dim,
+                       float* d_out, int device, void* stream) {
+  return guarded([&] {
+    gf::edge_score_bf16_forward(d_src, d_dst, d_w, d_bias, num_src, num_dst, dim, d_out, device,
+                                as_stream(stream));
+  });
+}
+int gf_edge_score_backward_bf16(const uint16_t* d_src, const uint16_t* d_dst, const float* d_w,
+                                size_t num_src, size_t num_dst, size_t dim,
+                                const float* d_grad_out, float* d_partials, size_t partial_rows,
+                                uint16_t* d_grad_src, uint16_t* d_grad_dst, float* d_grad_w,
+                                float* d_grad_bias, int device, void* stream) {
+  return guarded([&] {
+    gf::edge_score_bf16_backward(d_src, d_dst, d_w, num_src, num_dst, dim, d_grad_out, d_partials,
+                                 partial_rows, d_grad_src, d_grad_dst, d_grad_w, d_grad_bias,
+                                 device, as_stream(stream));
   });
 }
 

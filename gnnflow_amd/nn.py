@@ -260,7 +260,19 @@ class TemporalAttentionLayer(nn.Module):
     the dropout happens inside the kernels, from the op's stateless Philox mask, with a seed
     drawn per forward from torch's default CPU generator (no device sync; reproducible under
     torch.manual_seed, but not the mask torch's own dropout would draw).  With `fused_time_encode` the rows [h_src | f |
-    time_enc(dt)] and [h_dst | time_enc(0)] are one ops.time_encode_cat call each."""
+    time_enc(dt)] and [h_dst | time_enc(0)] are one ops.time_encode_cat call each.
+
+    Under torch.autocast('cuda', dtype=torch.bfloat16) every flag combination runs.  The Linear
+    layers return bfloat16, and ops.block_attention takes q, k, v as they come: float32
+    arithmetic inside, one rounding on store (ops.py).  With `fused_time_encode` the rows are
+    asked for in bfloat16 (out_dtype), the type w_q / w_k / w_v want, so autocast has nothing to
+    cast in front of them.  The bfloat16 aggregate is concatenated with h_dst.to(bfloat16): one
+    cast of the [R, dim_node] side and a bfloat16 cat, one kernel fewer than letting torch.cat
+    promote (which widens the aggregate, concatenates in float32 and leaves w_out's input to be
+    cast again).  The composed chain edge_softmax -> dropout -> block_reduce is float32 only:
+    where it is taken (`fused_attention` off, or dropout active with `fused_attention_dropout`
+    off) q, k, v are widened with .float() in front of it.  The output is float32, layer_norm's
+    type under autocast.  Outside autocast nothing differs."""
 
     def __init__(self, dim_node: int, dim_edge: int, dim_time: int, dim_out: int, num_head: int,
                  dropout: float, att_dropout: float):
@@ -295,6 +307,8 @@ class TemporalAttentionLayer(nn.Module):
         if E == 0:
             return torch.zeros((R, self.dim_out), device=dev)
         fused_te = self.fused_time_encode and self.use_time_enc
+        amp = dev.type == 'cuda' and torch.is_autocast_enabled('cuda') and \
+            torch.get_autocast_dtype('cuda') == torch.bfloat16
         parts_q, parts_kv = [], []
         if self.use_node_feat:
             h = b.srcdata['h']
@@ -307,9 +321,10 @@ class TemporalAttentionLayer(nn.Module):
             parts_kv.append(b.edata['f'])
         if fused_te:      # [parts | time_enc] in one launch each
             w = self.time_enc.w
+            rows = torch.bfloat16 if amp else None      # the GEMMs' input type under autocast
             q_in = ops.time_encode_cat(parts_q, torch.zeros(R, dtype=torch.float32, device=dev),
-                                       w.weight, w.bias)
-            kv = ops.time_encode_cat(parts_kv, b.edata['dt'], w.weight, w.bias)
+                                       w.weight, w.bias, out_dtype=rows)
+            kv = ops.time_encode_cat(parts_kv, b.edata['dt'], w.weight, w.bias, out_dtype=rows)
         else:
             if self.use_time_enc:
                 parts_q.append(self.time_enc(torch.zeros(R, dtype=torch.float32, device=dev)))
@@ -320,6 +335,8 @@ class TemporalAttentionLayer(nn.Module):
         q = self.w_q(q_in).reshape(R, H, -1)
         k = self.w_k(kv).reshape(E, H, -1)
         v = self.w_v(kv).reshape(E, H, -1)
+        if q.dtype != k.dtype:      # w_q the identity: a row of ones, exact in any float type
+            q = q.to(k.dtype)
         p = self.att_dropout.p
         if self.fused_attention and (p == 0 or not self.training):
             agg = ops.block_attention(b, q, k, v, negative_slope=self.att_act.negative_slope)
@@ -328,12 +345,14 @@ class TemporalAttentionLayer(nn.Module):
             agg = ops.block_attention(b, q, k, v, negative_slope=self.att_act.negative_slope,
                                       dropout_p=p, dropout_seed=seed)
         else:
+            if q.dtype == torch.bfloat16:      # the composed chain is float32 only
+                q, k, v = q.float(), k.float(), v.float()
             row = b.edges()[1]
             att = ops.edge_softmax(b, self.att_act((q[row] * k).sum(dim=2)))
             msg = (v * self.att_dropout(att)[:, :, None]).reshape(E, -1)
             agg = ops.block_reduce(b, torch.cat([torch.zeros((R, msg.shape[1]), device=dev), msg]))
         agg = agg.reshape(R, -1)
-        rst = torch.cat([agg, h_dst], dim=1) if self.use_node_feat else agg
+        rst = torch.cat([agg, h_dst.to(agg.dtype)], dim=1) if self.use_node_feat else agg
         return self.layer_norm(F.relu(self.dropout(self.w_out(rst))))
 
 
@@ -352,7 +371,9 @@ class GRUMemoryUpdater(nn.Module):
     Returns {'last_updated_nid', 'last_updated_memory', 'last_updated_ts'} of the first
     num_dst_nodes rows as detached clones, the arguments of Memory.update_mem_mail.  Unlike the
     reference it leaves b.srcdata['mem_input'] as prepare_input wrote it.  With
-    `fused_time_encode` the GRU input is one ops.time_encode_cat call."""
+    `fused_time_encode` the GRU input is one ops.time_encode_cat call.  Under bfloat16 autocast the
+    GRU cell returns bfloat16; it is widened once, so 'last_updated_memory' (Memory stores
+    float32) and b.srcdata['h'] come out float32 as they do outside autocast."""
 
     def __init__(self, dim_node: int, dim_edge: int, dim_time: int, dim_embed: int,
                  dim_memory: int):
@@ -377,6 +398,8 @@ class GRUMemoryUpdater(nn.Module):
             else:
                 x = torch.cat([x, self.time_enc(dt)], dim=1)
         updated = self.updater(x, b.srcdata['mem'])
+        if updated.dtype == torch.bfloat16:      # bfloat16 autocast: memory and 'h' stay float32
+            updated = updated.float()
         R = b.num_dst_nodes()
         last = {"last_updated_nid": b.srcdata['ID'][:R].detach().clone(),
                 "last_updated_memory": updated[:R].detach().clone(),
@@ -403,7 +426,9 @@ class EdgePredictor(nn.Module):
 
     With `fused_score`, float32 rows on the GPU take dst_fc as one GEMM over both destination
     blocks and everything behind it as one ops.edge_score call; anything else the torch
-    expression."""
+    expression.  The call is made when what src_fc and dst_fc return is float32 or, as under
+    bfloat16 autocast, bfloat16 (ops.edge_score: float32 arithmetic, float32 scores); any other
+    type they return (float16 autocast) takes the torch expression on the same two results."""
 
     def __init__(self, dim_embed: int):
         super().__init__()
@@ -418,11 +443,13 @@ class EdgePredictor(nn.Module):
             raise ValueError("EdgePredictor takes [src | pos dst | neg dst] rows, {} is not a "
                              "multiple of 3".format(h.shape[0]))
         B = h.shape[0] // 3
-        if self.fused_score and h.is_cuda and h.dtype == torch.float32 and \
+        if self.fused_score and h.is_cuda and h.dtype in (torch.float32, torch.bfloat16) and \
                 self.out_fc.weight.dtype == torch.float32:
-            out = ops.edge_score(self.src_fc(h[:B]), self.dst_fc(h[B:]), self.out_fc.weight,
-                                 self.out_fc.bias)
-            return out[:B], out[B:]
+            src_h, dst_h = self.src_fc(h[:B]), self.dst_fc(h[B:])
+            if src_h.dtype == dst_h.dtype and src_h.dtype in (torch.float32, torch.bfloat16):
+                out = ops.edge_score(src_h, dst_h, self.out_fc.weight, self.out_fc.bias)
+                return out[:B], out[B:]
+            return (self.out_fc(F.relu(src_h + dst_h[:B])), self.out_fc(F.relu(src_h + dst_h[B:])))
         src_h = self.src_fc(h[:B])
         pos_edge = F.relu(src_h + self.dst_fc(h[B:2 * B]))
         neg_edge = F.relu(src_h + self.dst_fc(h[2 * B:]))

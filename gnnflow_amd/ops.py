@@ -20,6 +20,14 @@ make on a sampled block, on HIP segment kernels (csrc/block_ops.hip) with autogr
                                            the MRR, counted on the GPU without a sort, a sync or a copy
                                            to the host (csrc/link_metrics.hip)
 
+block_attention, time_encode_cat and edge_score also run on bfloat16 (the tensors autocast hands
+them), by one rule: float32 arithmetic, one rounding on store.  Every bfloat16 element is widened
+to float32 where it is loaded (exact), the arithmetic is the float32 kernels' own in the same
+order, and each bfloat16 result is rounded once, to nearest even.  So
+op(x.bfloat16()) == op(x.bfloat16().float()).to(torch.bfloat16) bit for bit, forward and backward,
+and the float32 outputs (attention, scores, parameter gradients) are equal.  The ops choose by
+the dtypes they are given and behave the same inside and outside an autocast region.
+
 A block's edges are grouped by destination (the sampler emits them that way); blocks built by
 hand with unordered edges are handled through a stable permutation.
 """
@@ -43,6 +51,21 @@ def _f32(t: torch.Tensor) -> torch.Tensor:
 
 def _ptr(t):
     return t.data_ptr() if t is not None and t.numel() else None
+
+
+def _grad_as(grad: torch.Tensor, dtype) -> torch.Tensor:
+    """The incoming gradient of an output of `dtype`, contiguous."""
+    if grad.dtype != dtype:
+        raise TypeError("the gradient of a {} output is {}".format(dtype, grad.dtype))
+    return grad.contiguous()
+
+
+# The autograd Functions of the ops that take bfloat16 call no torch op that autocast would
+# recast, and custom_fwd / custom_bwd without cast_inputs keep it that way: the forward sees the
+# tensors as they are given, the backward runs under the forward's autocast state wherever
+# loss.backward() is called.
+_fwd = torch.amp.custom_fwd(device_type="cuda")
+_bwd = torch.amp.custom_bwd(device_type="cuda")
 
 
 class _EdgeSoftmax(torch.autograd.Function):
@@ -157,13 +180,17 @@ MAX_ATTENTION_WIDTH = 1024      # GF_BLOCK_ATTENTION_MAX_WIDTH: the limit on hea
 
 class _BlockAttention(torch.autograd.Function):
     @staticmethod
+    @_fwd
     def forward(ctx, q, k, v, offsets, num_dst, slope):
-        # q [num_dst, H, D], k / v [E, H, D] contiguous fp32, edges grouped by destination
+        # q [num_dst, H, D], k / v [E, H, D] contiguous, all fp32 or all bf16, edges grouped by
+        # destination; out in their dtype, att fp32
         E, H, D = k.shape
-        out = torch.empty((num_dst, H, D), dtype=torch.float32, device=q.device)
+        out = torch.empty((num_dst, H, D), dtype=q.dtype, device=q.device)
         att = torch.empty((E, H), dtype=torch.float32, device=q.device)
+        lib = _capi.load()
+        fn = lib.gf_block_attention_bf16 if q.dtype == torch.bfloat16 else lib.gf_block_attention
         with torch.cuda.device(q.device):
-            _capi.check(_capi.load().gf_block_attention(
+            _capi.check(fn(
                 offsets.data_ptr(), num_dst, E, H, D, q.data_ptr(), k.data_ptr(), v.data_ptr(),
                 slope, out.data_ptr(), att.data_ptr(), q.device.index, _stream(q.device)))
         ctx.save_for_backward(q, k, v, att, offsets)
@@ -172,17 +199,21 @@ class _BlockAttention(torch.autograd.Function):
         return out, att
 
     @staticmethod
+    @_bwd
     def backward(ctx, grad, _grad_att):
         q, k, v, att, offsets = ctx.saved_tensors
-        g = _f32(grad)
+        g = _grad_as(grad, q.dtype)
         E, H, D = k.shape
         need_q, need_k, need_v = ctx.needs_input_grad[:3]
         gq = torch.empty_like(q) if need_q else None
         gk = torch.empty_like(k) if need_k else None
         gv = torch.empty_like(v) if need_v else None
         if need_q or need_k or need_v:
+            lib = _capi.load()
+            fn = lib.gf_block_attention_bf16_backward if q.dtype == torch.bfloat16 \
+                else lib.gf_block_attention_backward
             with torch.cuda.device(q.device):
-                _capi.check(_capi.load().gf_block_attention_backward(
+                _capi.check(fn(
                     offsets.data_ptr(), q.shape[0], E, H, D, q.data_ptr(), k.data_ptr(),
                     v.data_ptr(), att.data_ptr(), ctx.slope, g.data_ptr(), _ptr(gq), _ptr(gk),
                     _ptr(gv), q.device.index, _stream(q.device)))
@@ -191,14 +222,18 @@ class _BlockAttention(torch.autograd.Function):
 
 class _BlockAttentionDropout(torch.autograd.Function):
     @staticmethod
+    @_fwd
     def forward(ctx, q, k, v, offsets, num_dst, slope, p, seed, want_dropped):
-        # as _BlockAttention; att is the pre-dropout softmax (saved), dropped = att * w
+        # as _BlockAttention; att is the pre-dropout softmax (saved), dropped = att * w, both fp32
         E, H, D = k.shape
-        out = torch.empty((num_dst, H, D), dtype=torch.float32, device=q.device)
+        out = torch.empty((num_dst, H, D), dtype=q.dtype, device=q.device)
         att = torch.empty((E, H), dtype=torch.float32, device=q.device)
         dropped = torch.empty_like(att) if want_dropped else None
+        lib = _capi.load()
+        fn = lib.gf_block_attention_dropout_bf16 if q.dtype == torch.bfloat16 \
+            else lib.gf_block_attention_dropout
         with torch.cuda.device(q.device):
-            _capi.check(_capi.load().gf_block_attention_dropout(
+            _capi.check(fn(
                 offsets.data_ptr(), num_dst, E, H, D, q.data_ptr(), k.data_ptr(), v.data_ptr(),
                 slope, p, seed, out.data_ptr(), att.data_ptr(), _ptr(dropped), q.device.index,
                 _stream(q.device)))
@@ -210,18 +245,22 @@ class _BlockAttentionDropout(torch.autograd.Function):
         return out, dropped
 
     @staticmethod
+    @_bwd
     def backward(ctx, grad, _grad_dropped):
         q, k, v, att, offsets = ctx.saved_tensors
         slope, p, seed = ctx.meta
-        g = _f32(grad)
+        g = _grad_as(grad, q.dtype)
         E, H, D = k.shape
         need_q, need_k, need_v = ctx.needs_input_grad[:3]
         gq = torch.empty_like(q) if need_q else None
         gk = torch.empty_like(k) if need_k else None
         gv = torch.empty_like(v) if need_v else None
         if need_q or need_k or need_v:
+            lib = _capi.load()
+            fn = lib.gf_block_attention_dropout_bf16_backward if q.dtype == torch.bfloat16 \
+                else lib.gf_block_attention_dropout_backward
             with torch.cuda.device(q.device):
-                _capi.check(_capi.load().gf_block_attention_dropout_backward(
+                _capi.check(fn(
                     offsets.data_ptr(), q.shape[0], E, H, D, q.data_ptr(), k.data_ptr(),
                     v.data_ptr(), att.data_ptr(), slope, p, seed, g.data_ptr(), _ptr(gq),
                     _ptr(gk), _ptr(gv), q.device.index, _stream(q.device)))
@@ -250,7 +289,12 @@ def block_attention(block, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
         att[e, h] = edge_softmax(leaky_relu(sum_c q[row[e], h, c] * k[e, h, c], negative_slope))
         out[d, h] = sum over the edges e into d of att[e, h] * v[e, h]      (0 without in-edges)
 
-    q: [num_dst_nodes, H, D]; k, v: [num_edges, H, D], float32.  The inputs are 3-D; a 2-D
+    q: [num_dst_nodes, H, D]; k, v: [num_edges, H, D], all three float32 or all three bfloat16
+    (anything else, a mixture included, raises TypeError).  bfloat16 follows the module's rule --
+    float32 arithmetic, one rounding on store --: out and the gradients are bfloat16 and equal,
+    bit for bit, the float32 op's results on q.float(), k.float(), v.float() rounded to bfloat16;
+    the attention that return_attention=True gives stays float32 and is equal to the float32
+    op's.  The inputs are 3-D; a 2-D
     [rows, H * D] input is accepted only together with `heads=H`.  H * D is at most
     MAX_ATTENTION_WIDTH.  Returns out [num_dst_nodes, H, D], and with return_attention=True
     also att [num_edges, H] in the caller's edge order (not differentiable).
@@ -285,7 +329,11 @@ def block_attention(block, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     elif dropout_p > 0:
         raise ValueError("dropout_p > 0 needs a dropout_seed")
     num_dst, E = block.num_dst_nodes(), block.num_edges()
-    q, k, v = _f32(q), _f32(k), _f32(v)
+    dtypes = (q.dtype, k.dtype, v.dtype)
+    if dtypes not in ((torch.float32,) * 3, (torch.bfloat16,) * 3):
+        raise TypeError("block_attention takes q, k and v all float32 or all bfloat16 (block ops "
+                        "compute in float32), got {}, {} and {}".format(*dtypes))
+    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
     if q.shape[0] != num_dst:
         raise ValueError("q must have one row per destination node")
     if k.shape[0] != E or v.shape[0] != E:
@@ -471,28 +519,36 @@ def block_gat(block, feat: torch.Tensor, el: torch.Tensor, er: torch.Tensor,
 
 class _TimeEncodeCat(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, t, weight, bias, *parts):
-        # t [n], weight / bias [T], parts: contiguous [n, W] with W > 0; all fp32 on one device
+    @_fwd
+    def forward(ctx, out_dtype, t, weight, bias, *parts):
+        # t [n], weight / bias [T], parts: contiguous [n, W] with W > 0; all fp32 on one device;
+        # out_dtype fp32 or bf16
         n, T = t.shape[0], bias.shape[0]
         widths = [p.shape[1] for p in parts]
-        out = torch.empty((n, sum(widths) + T), dtype=torch.float32, device=t.device)
+        out = torch.empty((n, sum(widths) + T), dtype=out_dtype, device=t.device)
         if n:
             a, b = (list(parts) + [None, None])[:2]
             wa, wb = (widths + [0, 0])[:2]
+            lib = _capi.load()
+            fn = lib.gf_time_encode_cat_bf16 if out_dtype == torch.bfloat16 \
+                else lib.gf_time_encode_cat
             with torch.cuda.device(t.device):
-                _capi.check(_capi.load().gf_time_encode_cat(
+                _capi.check(fn(
                     _ptr(a), wa, _ptr(b), wb, t.data_ptr(), weight.data_ptr(), bias.data_ptr(),
                     n, T, out.data_ptr(), t.device.index, _stream(t.device)))
         ctx.save_for_backward(t, weight, bias)
         ctx.widths = widths
+        ctx.out_dtype = out_dtype
         return out
 
     @staticmethod
+    @_bwd
     def backward(ctx, grad):
         t, weight, bias = ctx.saved_tensors
         n, T = t.shape[0], bias.shape[0]
-        g = _f32(grad)
-        need_w, need_b = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        g = _grad_as(grad, ctx.out_dtype)
+        bf16 = ctx.out_dtype == torch.bfloat16
+        need_w, need_b = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
         gw = gb = None
         if need_w or need_b:
             # n == 0: zeros, and nothing to launch
@@ -503,20 +559,28 @@ class _TimeEncodeCat(torch.autograd.Function):
                 rows = C.c_size_t(0)
                 _capi.check(lib.gf_time_encode_backward_partial_rows(n, C.byref(rows)))
                 partials = torch.empty((rows.value, 2, T), dtype=torch.float32, device=t.device)
+                fn = lib.gf_time_encode_backward_bf16 if bf16 else lib.gf_time_encode_backward
                 with torch.cuda.device(t.device):
-                    _capi.check(lib.gf_time_encode_backward(
+                    _capi.check(fn(
                         t.data_ptr(), weight.data_ptr(), bias.data_ptr(), n, T, g.data_ptr(),
                         g.shape[1], sum(ctx.widths), partials.data_ptr(), rows.value,
                         _ptr(gw), _ptr(gb), t.device.index, _stream(t.device)))
         gparts, off = [], 0
         for k, w in enumerate(ctx.widths):      # column slices of grad: views, no kernel
-            gparts.append(g[:, off:off + w] if ctx.needs_input_grad[3 + k] else None)
+            gp = g[:, off:off + w] if ctx.needs_input_grad[4 + k] else None
+            # the parts are fp32: a bf16 slice is widened once (exact)
+            gparts.append(gp.float() if gp is not None and bf16 else gp)
             off += w
-        return (None, gw, gb) + tuple(gparts)      # no gradient flows to t
+        return (None, None, gw, gb) + tuple(gparts)      # no gradient flows to t
 
 
-def _time_encode_cat(parts, t, weight, bias):
+def _time_encode_cat(parts, t, weight, bias, out_dtype=None):
     """time_encode_cat: checks every argument, then the kernel."""
+    if out_dtype is None:
+        out_dtype = torch.float32
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("out_dtype must be None, torch.float32 or torch.bfloat16, got {}".format(
+            out_dtype))
     parts = tuple(parts)
     if len(parts) > 2:
         raise ValueError("time_encode_cat takes at most two parts, got {}".format(len(parts)))
@@ -552,11 +616,12 @@ def _time_encode_cat(parts, t, weight, bias):
         raise ValueError("time_encode_cat runs on the GPU, the inputs are on {}".format(t.device))
     # a part without columns adds nothing to the row (and has no address to hand over)
     parts = tuple(p.contiguous() for p in parts if p.shape[1])
-    return _TimeEncodeCat.apply(t.detach().contiguous(), weight.reshape(T).contiguous(),
-                                bias.contiguous(), *parts)
+    return _TimeEncodeCat.apply(out_dtype, t.detach().contiguous(),
+                                weight.reshape(T).contiguous(), bias.contiguous(), *parts)
 
 
-def time_encode_cat(parts, t: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor):
+def time_encode_cat(parts, t: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
+                    out_dtype=None):
     """torch.cat([*parts, torch.cos(t[:, None] * weight.T + bias)], dim=1) in one kernel: the
     input rows every temporal layer of the reference builds (layers.py:118-137,
     memory_updater.py:62-65).
@@ -566,24 +631,36 @@ def time_encode_cat(parts, t: torch.Tensor, weight: torch.Tensor, bias: torch.Te
     [T, 1] or [T] (TimeEncode.w.weight); bias: [T]; all float32 on one GPU.  Returns
     [n, sum(W) + T].  Differentiable in parts, weight and bias; t gets no gradient (the
     reference never asks for one).  The gradients of weight and bias are summed in a fixed
-    order: bit-identical from run to run."""
-    return _time_encode_cat(parts, t, weight, bias)
+    order: bit-identical from run to run.
+
+    out_dtype: None or torch.float32 (the call without it, bit for bit) or torch.bfloat16; any
+    other value raises ValueError.  The inputs stay float32 either way.  bfloat16 follows the
+    module's rule -- float32 arithmetic, one rounding on store --: the rows are what the float32
+    call returns, converted with .to(torch.bfloat16), written by the kernel itself.  The backward
+    then takes a bfloat16 gradient: the gradients of weight and bias are float32 and equal, bit
+    for bit, the float32 op's on the widened gradient, and those of the parts are its column
+    slices widened to float32."""
+    return _time_encode_cat(parts, t, weight, bias, out_dtype)
 
 
-def time_encode(t: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+def time_encode(t: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
+                out_dtype=None) -> torch.Tensor:
     """cos(t[:, None] * weight.T + bias): time_encode_cat without parts, [n, T]."""
-    return _time_encode_cat((), t, weight, bias)
+    return _time_encode_cat((), t, weight, bias, out_dtype)
 
 
 class _EdgeScore(torch.autograd.Function):
     @staticmethod
+    @_fwd
     def forward(ctx, src, dst, weight, bias):
-        # src [B, D], dst [M, D] contiguous, weight [D], bias [1]; all fp32 on one device
+        # src [B, D], dst [M, D] contiguous, both fp32 or both bf16; weight [D], bias [1] fp32
         M = dst.shape[0]
         out = torch.empty((M, 1), dtype=torch.float32, device=dst.device)
         if M:
+            lib = _capi.load()
+            fn = lib.gf_edge_score_bf16 if dst.dtype == torch.bfloat16 else lib.gf_edge_score
             with torch.cuda.device(dst.device):
-                _capi.check(_capi.load().gf_edge_score(
+                _capi.check(fn(
                     src.data_ptr(), dst.data_ptr(), weight.data_ptr(), bias.data_ptr(),
                     src.shape[0], M, dst.shape[1], out.data_ptr(), dst.device.index,
                     _stream(dst.device)))
@@ -591,6 +668,7 @@ class _EdgeScore(torch.autograd.Function):
         return out
 
     @staticmethod
+    @_bwd
     def backward(ctx, grad):
         src, dst, weight = ctx.saved_tensors
         (B, D), M = src.shape, dst.shape[0]
@@ -613,8 +691,10 @@ class _EdgeScore(torch.autograd.Function):
         if need_w or need_b:
             _capi.check(lib.gf_edge_score_backward_partial_rows(B, C.byref(rows)))
             partials = torch.empty((rows.value, D + 1), **f32)
+        fn = lib.gf_edge_score_backward_bf16 if dst.dtype == torch.bfloat16 \
+            else lib.gf_edge_score_backward
         with torch.cuda.device(dst.device):
-            _capi.check(lib.gf_edge_score_backward(
+            _capi.check(fn(
                 src.data_ptr(), dst.data_ptr(), weight.data_ptr(), B, M, D, g.data_ptr(),
                 _ptr(partials), rows.value, _ptr(gs), _ptr(gd), _ptr(gw), _ptr(gb),
                 dst.device.index, _stream(dst.device)))
@@ -630,10 +710,20 @@ def edge_score(src: torch.Tensor, dst: torch.Tensor, weight: torch.Tensor, bias:
     weight: [D] or [1, D] (out_fc.weight); bias: [1]; all float32 on one GPU (row slices such as
     h[B:] are taken as they are; any other non-contiguous input is copied first).  Returns
     [M, 1].  Differentiable in all four; every gradient is summed in a fixed order:
-    bit-identical from run to run."""
+    bit-identical from run to run.
+
+    src and dst may instead both be bfloat16 (the Linear outputs under autocast) with weight and
+    bias float32; any other dtype or a mixture raises TypeError.  The module's rule -- float32
+    arithmetic, one rounding on store -- applies: the scores and the gradients of weight and bias
+    are float32 and equal, bit for bit, the float32 op's on src.float() and dst.float(); the
+    gradients of src and dst are bfloat16, its float32 gradients rounded once."""
     for name, x in (("src", src), ("dst", dst), ("weight", weight), ("bias", bias)):
         if not isinstance(x, torch.Tensor):
             raise TypeError("{} must be a tensor, got {}".format(name, type(x).__name__))
+    if (src.dtype, dst.dtype) not in ((torch.float32,) * 2, (torch.bfloat16,) * 2):
+        raise TypeError("edge_score computes in float32 and takes src and dst both float32 or "
+                        "both bfloat16, src is {} and dst is {}".format(src.dtype, dst.dtype))
+    for name, x in (("weight", weight), ("bias", bias)):
         if x.dtype != torch.float32:
             raise TypeError("edge_score computes in float32, {} is {}".format(name, x.dtype))
     if src.dim() != 2 or dst.dim() != 2:

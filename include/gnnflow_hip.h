@@ -823,6 +823,42 @@ GF_API int gf_block_attention_dropout_backward(const int64_t* d_offsets, size_t 
                                                float* d_grad_k, float* d_grad_v, int device,
                                                void* stream);
 
+/* The four entry points above for bfloat16 q, k, v, out and gradients, carried as uint16_t (the
+ * upper half of a float32); d_att and d_att_dropped stay float32.  Every element is widened to
+ * float32 when it is loaded (exact), the arithmetic is that of the float32 entry points in the
+ * same order, and each result is rounded once, to nearest even, when it is stored (NaN -> 0x7FC0,
+ * overflow -> infinity).  So d_out, d_grad_q, d_grad_k and d_grad_v hold, bit for bit, the
+ * float32 entry point's results on the widened inputs, rounded to bfloat16; d_att and
+ * d_att_dropped are equal to its outputs.  Arguments, order, checks and limits are the float32
+ * siblings'. */
+GF_API int gf_block_attention_bf16(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                                   size_t heads, size_t head_dim, const uint16_t* d_q,
+                                   const uint16_t* d_k, const uint16_t* d_v, float negative_slope,
+                                   uint16_t* d_out, float* d_att, int device, void* stream);
+GF_API int gf_block_attention_bf16_backward(const int64_t* d_offsets, size_t num_dst,
+                                            size_t num_edges, size_t heads, size_t head_dim,
+                                            const uint16_t* d_q, const uint16_t* d_k,
+                                            const uint16_t* d_v, const float* d_att,
+                                            float negative_slope, const uint16_t* d_grad_out,
+                                            uint16_t* d_grad_q, uint16_t* d_grad_k,
+                                            uint16_t* d_grad_v, int device, void* stream);
+GF_API int gf_block_attention_dropout_bf16(const int64_t* d_offsets, size_t num_dst,
+                                           size_t num_edges, size_t heads, size_t head_dim,
+                                           const uint16_t* d_q, const uint16_t* d_k,
+                                           const uint16_t* d_v, float negative_slope, float p,
+                                           uint64_t seed, uint16_t* d_out, float* d_att,
+                                           float* d_att_dropped, int device, void* stream);
+GF_API int gf_block_attention_dropout_bf16_backward(const int64_t* d_offsets, size_t num_dst,
+                                                    size_t num_edges, size_t heads,
+                                                    size_t head_dim, const uint16_t* d_q,
+                                                    const uint16_t* d_k, const uint16_t* d_v,
+                                                    const float* d_att, float negative_slope,
+                                                    float p, uint64_t seed,
+                                                    const uint16_t* d_grad_out,
+                                                    uint16_t* d_grad_q, uint16_t* d_grad_k,
+                                                    uint16_t* d_grad_v, int device,
+                                                    void* stream);
+
 /* Fused GAT attention (dgl.nn.GATConv's message passing) over a block: feat [num_src, heads,
  * head_dim], el [num_src, heads], er [num_dst, heads]; src(e) = d_col[e], or num_dst + e when
  * d_col is NULL (the sampler's layout; num_src must then be num_dst + num_edges),
@@ -883,6 +919,22 @@ GF_API int gf_time_encode_backward(const float* d_t, const float* d_w, const flo
                                    size_t partial_rows, float* d_grad_w, float* d_grad_bias,
                                    int device, void* stream);
 
+/* gf_time_encode_cat with a bfloat16 d_out (uint16_t as above; parts, t, w and bias float32):
+ * every column is the float32 entry point's value rounded once to nearest even, so a copied
+ * column is a plain float32 -> bfloat16 conversion.  gf_time_encode_backward_bf16 reads a
+ * bfloat16 d_grad_out (grad_pitch and grad_col in elements), widened on load; the partials
+ * (gf_time_encode_backward_partial_rows as before), grad_w and grad_bias stay float32 and are the
+ * float32 entry point's on the widened gradient, bit for bit.  The same checks. */
+GF_API int gf_time_encode_cat_bf16(const float* d_a, size_t width_a, const float* d_b,
+                                   size_t width_b, const float* d_t, const float* d_w,
+                                   const float* d_bias, size_t n, size_t dim_time,
+                                   uint16_t* d_out, int device, void* stream);
+GF_API int gf_time_encode_backward_bf16(const float* d_t, const float* d_w, const float* d_bias,
+                                        size_t n, size_t dim_time, const uint16_t* d_grad_out,
+                                        size_t grad_pitch, size_t grad_col, float* d_partials,
+                                        size_t partial_rows, float* d_grad_w, float* d_grad_bias,
+                                        int device, void* stream);
+
 /* Fused edge score (the tail of the reference's EdgePredictor, layers.py:186-197, after src_fc
  * and dst_fc): d_src [num_src, dim], d_dst [num_dst, dim], d_w [dim], d_bias [1], d_out
  * [num_dst], all fp32, row-major and contiguous; num_dst = r * num_src, row j of dst pairs with
@@ -910,6 +962,22 @@ GF_API int gf_edge_score_backward(const float* d_src, const float* d_dst, const 
                                   const float* d_grad_out, float* d_partials, size_t partial_rows,
                                   float* d_grad_src, float* d_grad_dst, float* d_grad_w,
                                   float* d_grad_bias, int device, void* stream);
+
+/* gf_edge_score and gf_edge_score_backward for bfloat16 d_src and d_dst rows (uint16_t as above)
+ * and bfloat16 d_grad_src / d_grad_dst; d_w, d_bias, d_out, d_grad_out, the partials
+ * (gf_edge_score_backward_partial_rows as before), d_grad_w and d_grad_bias stay float32.  Rows
+ * are widened on load, the arithmetic and its order are the float32 entry points', and grad_src
+ * and grad_dst are rounded once on store: every output equals the float32 entry point's on the
+ * widened rows (grad_src, grad_dst: rounded to bfloat16), bit for bit.  The same checks. */
+GF_API int gf_edge_score_bf16(const uint16_t* d_src, const uint16_t* d_dst, const float* d_w,
+                              const float* d_bias, size_t num_src, size_t num_dst, size_t dim,
+                              float* d_out, int device, void* stream);
+GF_API int gf_edge_score_backward_bf16(const uint16_t* d_src, const uint16_t* d_dst,
+                                       const float* d_w, size_t num_src, size_t num_dst,
+                                       size_t dim, const float* d_grad_out, float* d_partials,
+                                       size_t partial_rows, uint16_t* d_grad_src,
+                                       uint16_t* d_grad_dst, float* d_grad_w, float* d_grad_bias,
+                                       int device, void* stream);
 
 /* Link-prediction metrics of one validation batch from the scores d_pos [num_pos] of its true
  * edges and d_neg [num_neg] of its negative ones (float32, compared as IEEE compares them, so

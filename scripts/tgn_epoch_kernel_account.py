@@ -19,6 +19,7 @@ FAMILIES = [
     ("TGN memory ops", r"memory_\w+_kernel"),
     ("block ops: edge_softmax", r"edge_softmax_\w+"),
     ("block ops: segment reduce", r"segment_(reduce|max)_\w+|segment_offsets"),
+    ("block ops: attention", r"block_attention_\w+"),
     ("time encoding", r"time_encode_\w+"),
     ("edge store / ingest", r"move_segments|scatter_\w+|ingest|rocprim|node_table|publish"),
 ]
