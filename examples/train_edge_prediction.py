@@ -1,19 +1,14 @@
 """Minimal offline edge-prediction loop in the shape of the reference's
 scripts/offline_edge_prediction.py, on this package only: batches from
-`gnnflow_amd.data`, neighbourhoods from `TemporalSampler`, features through `LRUCache`, a
-2-layer GraphSAGE (`gnnflow_amd.nn.SAGEConv`, the layer the reference's GRAPHSAGE model uses) and
-a dot-product edge scorer.  Synthetic REDDIT-shaped data; a usage example, not a benchmark.
+`gnnflow_amd.data`, neighbourhoods from `TemporalSampler`, features through `LRUCache`, and one
+of the reference's static models, the 2-layer `gnnflow_amd.models.SAGE` (GraphSAGE) or
+`gnnflow_amd.models.GAT`.  Synthetic REDDIT-shaped data; a usage example, not a benchmark.
 
-    python examples/train_edge_prediction.py [--batches 50] [--amp]
+    python examples/train_edge_prediction.py [--batches 50] [--model {sage,gat}] [--amp]
 
 --amp runs the forward and the loss under torch.autocast('cuda', dtype=torch.bfloat16).  No
-GradScaler: bfloat16 has float32's range.  SAGEConv's block ops are float32 only, so the model
-widens the first layer's output before the second.  That is enough for the widths used here
-(in_feats <= out_feats in both layers, so each layer aggregates its float32 input and applies
-fc_neigh afterwards); a SAGEConv that shrinks its rows applies fc_neigh first and would hand
-ops.block_reduce bfloat16 under autocast, which raises TypeError.  models.DGNN needs no such
-care: ops.block_attention, time_encode_cat and edge_score take the bfloat16 tensors autocast
-produces (examples/tgn_epoch.py --amp).
+GradScaler: bfloat16 has float32's range.  The models need no cast for it: the block ops take
+the bfloat16 rows autocast produces (as models.DGNN does, examples/tgn_epoch.py --amp).
 """
 import argparse
 import os
@@ -23,38 +18,26 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import numpy as np
 import torch
-import torch.nn as nn
 import torch.nn.functional as F
 from torch.utils.data import DataLoader, SequentialSampler
 
 import gnnflow_amd
-from gnnflow_amd import nn as gnn
-from gnnflow_amd import synthetic
+from gnnflow_amd import models, synthetic
 from gnnflow_amd.cache import LRUCache
 from gnnflow_amd.data import (EdgePredictionDataset, RandomStartBatchSampler,
                               default_collate_ndarray)
 from gnnflow_amd.utils import DstRandEdgeSampler, build_dynamic_graph
 
 
-class SAGE(nn.Module):
-    def __init__(self, dim_in, dim_hidden):
-        super().__init__()
-        self.l0 = gnn.SAGEConv(dim_in, dim_hidden, 'mean')
-        self.l1 = gnn.SAGEConv(dim_hidden, dim_hidden, 'mean')
-        self.score = nn.Sequential(nn.Linear(dim_hidden, dim_hidden), nn.ReLU(),
-                                   nn.Linear(dim_hidden, 1))
-
-    def forward(self, mfgs):
-        # mfgs[0] is the outer (largest) layer, mfgs[-1] the roots' layer
-        # .float(): ops.block_reduce is float32 only (a no-op outside autocast)
-        h = F.relu(self.l0(mfgs[0][0], mfgs[0][0].srcdata['h'])).float()
-        h = self.l1(mfgs[1][0], h)
-        b = h.shape[0] // 3                     # roots = [src | dst | negative dst]
-        src, pos, neg = h[:b], h[b:2 * b], h[2 * b:]
-        return self.score(src * pos), self.score(src * neg)
+def build_model(name, dim_in, dim_hidden):
+    if name == 'sage':
+        return models.SAGE(dim_in, dim_hidden, num_layers=2, aggregator='mean')
+    if name == 'gat':
+        return models.GAT(dim_in, dim_hidden, num_layers=2, attn_head=[2, 1])
+    raise ValueError("model must be 'sage' or 'gat', got {!r}".format(name))
 
 
-def main(num_batches=50, batch_size=600, seed=0, verbose=True, amp=False):
+def main(num_batches=50, batch_size=600, seed=0, verbose=True, amp=False, model='sage'):
     import pandas as pd
     torch.manual_seed(seed)
     dev = torch.device("cuda", 0)
@@ -71,7 +54,7 @@ def main(num_batches=50, batch_size=600, seed=0, verbose=True, amp=False):
     ds = EdgePredictionDataset(df, DstRandEdgeSampler(df["dst"].to_numpy(), seed=seed))
     loader = DataLoader(ds, sampler=RandomStartBatchSampler(SequentialSampler(ds), batch_size, False),
                         collate_fn=default_collate_ndarray, num_workers=0)
-    model = SAGE(d, 64).to(dev)
+    model = build_model(model, d, 64).to(dev)
     opt = torch.optim.Adam(model.parameters(), lr=1e-3)
     losses = []
     for i, (roots, ts, eid) in enumerate(loader):
@@ -97,5 +80,6 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, default=50)
     ap.add_argument("--amp", action="store_true", help="bfloat16 autocast around forward and loss")
+    ap.add_argument("--model", choices=["sage", "gat"], default="sage")
     args = ap.parse_args()
-    main(args.batches, amp=args.amp)
+    main(args.batches, amp=args.amp, model=args.model)

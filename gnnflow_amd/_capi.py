@@ -277,6 +277,18 @@ PROTOTYPES = {
                                         _p]),
     "gf_block_reduce_max": (C.c_int, [_p, _sz, _p, _p, _sz, _p, _p, C.c_int, _p]),
     "gf_block_reduce_max_backward": (C.c_int, [_sz, _p, _sz, _p, _p, _p, _sz, C.c_int, _p]),
+    # the bfloat16 siblings: the float32 prototype, then the scratch / float32 out pointer
+    "gf_block_reduce_bf16": (C.c_int, [_p, _sz, _p, _p, _sz, _p, _sz, C.c_int, _p, C.c_int, _p]),
+    "gf_block_reduce_backward_bf16": (C.c_int, [_p, _sz, _p, _p, _sz, _p, _sz, C.c_int, _p, _p,
+                                                _sz, _p, C.c_int, _p, _p]),
+    "gf_block_reduce_max_bf16": (C.c_int, [_p, _sz, _p, _p, _sz, _p, _p, C.c_int, _p]),
+    "gf_block_reduce_max_backward_bf16": (C.c_int, [_sz, _p, _sz, _p, _p, _p, _sz, C.c_int, _p,
+                                                    _p]),
+    "gf_block_gat_bf16": (C.c_int, [_p, _sz, _sz, _p, _sz, _sz, _sz, _p, _p, _p, C.c_float,
+                                    C.c_float, C.c_uint64, _p, _p, _p, C.c_int, _p, _p]),
+    "gf_block_gat_backward_bf16": (C.c_int, [_p, _sz, _sz, _p, _sz, _sz, _sz, _p, _p, _p, _p, _p,
+                                             C.c_float, C.c_float, C.c_uint64, _p, _p, _p, _p,
+                                             C.c_int, _p, _p]),
     "gf_time_encode_cat": (C.c_int, [_p, _sz, _p, _sz, _p, _p, _p, _sz, _sz, _p, C.c_int, _p]),
     "gf_time_encode_cat_bf16": (C.c_int, [_p, _sz, _p, _sz, _p, _p, _p, _sz, _sz, _p, C.c_int, _p]),
     "gf_time_encode_backward_partial_rows": (C.c_int, [_sz, C.POINTER(_sz)]),

@@ -1,4 +1,5 @@
-// Segment operations on a sampled block (block_ops.hip, block_attention.hip, block_gat.hip), the fused time
+// Segment operations on a sampled block (block_ops.hip, block_attention.hip, block_gat.hip and their
+// bfloat16 siblings block_ops_bf16.hip, block_attention_bf16.hip, block_gat_bf16.hip), the fused time
 // encoding in front of them (time_encode.hip) and the fused edge score behind them
 // (edge_score.hip), and the metrics of the scores it leaves (link_metrics.hip): the entry points
 // other translation units call.
@@ -29,6 +30,31 @@ void segment_max_forward(const int64_t* d_offsets, size_t num_dst, const int64_t
 void segment_max_backward(size_t num_dst, const int64_t* d_col, size_t dim,
                           const float* d_grad_out, const int64_t* d_arg, float* d_grad_src,
                           size_t num_src, int device, hipStream_t stream);
+
+// block_ops_bf16.hip: the reductions above for bfloat16 src, out, grad_out and grad_src
+// (uint16_t; edge weights, their gradient and arg stay as they are): widened on load, the float32
+// kernels' arithmetic, one rounding to nearest even on store.  The same checks.  d_scratch is a
+// caller-owned float32 [num_src, dim] the gradient of the source rows is accumulated in when d_col
+// is given (then rounded into d_grad_src by narrow_rows); it may be null when d_col is null, or
+// when d_grad_src is.
+void segment_reduce_bf16_forward(const int64_t* d_offsets, size_t num_dst, const int64_t* d_col,
+                                 const uint16_t* d_src, size_t dim, const float* d_w,
+                                 size_t heads, bool mean, uint16_t* d_out, int device,
+                                 hipStream_t stream);
+void segment_reduce_bf16_backward(const int64_t* d_offsets, size_t num_dst, const int64_t* d_col,
+                                  const uint16_t* d_src, size_t dim, const float* d_w,
+                                  size_t heads, bool mean, const uint16_t* d_grad_out,
+                                  uint16_t* d_grad_src, size_t num_src, float* d_grad_w,
+                                  float* d_scratch, int device, hipStream_t stream);
+void segment_max_bf16_forward(const int64_t* d_offsets, size_t num_dst, const int64_t* d_col,
+                              const uint16_t* d_src, size_t dim, uint16_t* d_out, int64_t* d_arg,
+                              int device, hipStream_t stream);
+void segment_max_bf16_backward(size_t num_dst, const int64_t* d_col, size_t dim,
+                               const uint16_t* d_grad_out, const int64_t* d_arg,
+                               uint16_t* d_grad_src, size_t num_src, float* d_scratch, int device,
+                               hipStream_t stream);
+// d_out[i] = d_in[i] rounded to bfloat16, i < n, on `stream` of the current device
+void narrow_rows(const float* d_in, uint16_t* d_out, size_t n, hipStream_t stream);
 
 // block_attention.hip: fused attention with per-edge K / V.  heads * head_dim is limited to
 // kBlockAttentionMaxWidth (GF_BLOCK_ATTENTION_MAX_WIDTH of the C ABI); beyond it both throw
@@ -105,6 +131,25 @@ void block_gat_backward(const int64_t* d_offsets, size_t num_dst, size_t num_edg
                         const float* d_att, const float* d_out, float negative_slope, float p,
                         uint64_t seed, const float* d_grad_out, float* d_grad_feat,
                         float* d_grad_el, float* d_grad_er, int device, hipStream_t stream);
+
+// block_gat_bf16.hip: the two entry points above for bfloat16 feat, out, grad_out and grad_feat
+// (el, er, att, the dropped attention, grad_el and grad_er float32).  d_out_f32 [num_dst, heads,
+// head_dim] receives the forward's sums before they are rounded: it is the `out` the backward
+// reads (null in the forward: not written).  d_scratch: float32 [num_src, heads, head_dim] that
+// grad_feat is accumulated in when d_col is given; may be null when d_col or d_grad_feat is.
+void block_gat_bf16_forward(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                            const int64_t* d_col, size_t num_src, size_t heads, size_t head_dim,
+                            const uint16_t* d_feat, const float* d_el, const float* d_er,
+                            float negative_slope, float p, uint64_t seed, uint16_t* d_out,
+                            float* d_att, float* d_att_dropped, float* d_out_f32, int device,
+                            hipStream_t stream);
+void block_gat_bf16_backward(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                             const int64_t* d_col, size_t num_src, size_t heads, size_t head_dim,
+                             const uint16_t* d_feat, const float* d_el, const float* d_er,
+                             const float* d_att, const float* d_out_f32, float negative_slope,
+                             float p, uint64_t seed, const uint16_t* d_grad_out,
+                             uint16_t* d_grad_feat, float* d_grad_el, float* d_grad_er,
+                             float* d_scratch, int device, hipStream_t stream);
 
 // time_encode.hip: out = [a | b | cosf(w * t + bias)] in one launch (a / b may be null with
 // width 0), and the gradients of w and bias from the time columns of grad_out, read in place

@@ -200,6 +200,70 @@ int gf_block_gat_backward(const int64_t* d_offsets, size_t num_dst, size_t num_e
   });
 }
 
+int gf_block_reduce_bf16(const int64_t* d_offsets, size_t num_dst, const int64_t* d_col,
+                         const uint16_t* d_src, size_t dim, const float* d_edge_weight,
+                         size_t heads, int mean, uint16_t* d_out, int device, void* stream) {
+  return guarded([&] {
+    gf::segment_reduce_bf16_forward(d_offsets, num_dst, d_col, d_src, dim, d_edge_weight, heads,
+                                    mean != 0, d_out, device, as_stream(stream));
+  });
+}
+int gf_block_reduce_backward_bf16(const int64_t* d_offsets, size_t num_dst, const int64_t* d_col,
+                                  const uint16_t* d_src, size_t dim, const float* d_edge_weight,
+                                  size_t heads, int mean, const uint16_t* d_grad_out,
+                                  uint16_t* d_grad_src, size_t num_src,
+                                  float* d_grad_edge_weight, int device, void* stream,
+                                  float* d_scratch) {
+  return guarded([&] {
+    gf::segment_reduce_bf16_backward(d_offsets, num_dst, d_col, d_src, dim, d_edge_weight, heads,
+                                     mean != 0, d_grad_out, d_grad_src, num_src,
+                                     d_grad_edge_weight, d_scratch, device, as_stream(stream));
+  });
+}
+int gf_block_reduce_max_bf16(const int64_t* d_offsets, size_t num_dst, const int64_t* d_col,
+                             const uint16_t* d_src, size_t dim, uint16_t* d_out, int64_t* d_arg,
+                             int device, void* stream) {
+  return guarded([&] {
+    gf::segment_max_bf16_forward(d_offsets, num_dst, d_col, d_src, dim, d_out, d_arg, device,
+                                 as_stream(stream));
+  });
+}
+int gf_block_reduce_max_backward_bf16(size_t num_dst, const int64_t* d_col, size_t dim,
+                                      const uint16_t* d_grad_out, const int64_t* d_arg,
+                                      uint16_t* d_grad_src, size_t num_src, int device,
+                                      void* stream, float* d_scratch) {
+  return guarded([&] {
+    gf::segment_max_bf16_backward(num_dst, d_col, dim, d_grad_out, d_arg, d_grad_src, num_src,
+                                  d_scratch, device, as_stream(stream));
+  });
+}
+int gf_block_gat_bf16(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                      const int64_t* d_col, size_t num_src, size_t heads, size_t head_dim,
+                      const uint16_t* d_feat, const float* d_el, const float* d_er,
+                      float negative_slope, float p, uint64_t seed, uint16_t* d_out, float* d_att,
+                      float* d_att_dropped, int device, void* stream, float* d_out_f32) {
+  return guarded([&] {
+    gf::block_gat_bf16_forward(d_offsets, num_dst, num_edges, d_col, num_src, heads, head_dim,
+                               d_feat, d_el, d_er, negative_slope, p, seed, d_out, d_att,
+                               d_att_dropped, d_out_f32, device, as_stream(stream));
+  });
+}
+int gf_block_gat_backward_bf16(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                               const int64_t* d_col, size_t num_src, size_t heads,
+                               size_t head_dim, const uint16_t* d_feat, const float* d_el,
+                               const float* d_er, const float* d_att, const float* d_out_f32,
+                               float negative_slope, float p, uint64_t seed,
+                               const uint16_t* d_grad_out, uint16_t* d_grad_feat,
+                               float* d_grad_el, float* d_grad_er, int device, void* stream,
+                               float* d_scratch) {
+  return guarded([&] {
+    gf::block_gat_bf16_backward(d_offsets, num_dst, num_edges, d_col, num_src, heads, head_dim,
+                                d_feat, d_el, d_er, d_att, d_out_f32, negative_slope, p, seed,
+                                d_grad_out, d_grad_feat, d_grad_el, d_grad_er, d_scratch, device,
+                                as_stream(stream));
+  });
+}
+
 int gf_time_encode_cat(const float* d_a, size_t width_a, const float* d_b, size_t width_b,
                        const float* d_t, const float* d_w, const float* d_bias, size_t n,
                        size_t dim_time, float* d_out, int device, void* stream) {

@@ -1,6 +1,9 @@
-"""The reference's model package (gnnflow/models): `from gnnflow_amd.models.dgnn import DGNN` and
-the `models.modules.{layers,memory,memory_updater}` import lines work with the package name
+"""The reference's model package (gnnflow/models): `from gnnflow_amd.models.dgnn import DGNN`,
+`from gnnflow_amd.models.graphsage import SAGE`, `from gnnflow_amd.models.gat import GAT` and the
+`models.modules.{layers,memory,memory_updater}` import lines work with the package name
 swapped."""
 from .dgnn import DGNN
+from .gat import GAT
+from .graphsage import SAGE
 
-__all__ = ["DGNN"]
+__all__ = ["DGNN", "GAT", "SAGE"]

@@ -2,7 +2,9 @@
 reference's static models instantiate (gnnflow/models/graphsage.py:27-31, gat.py:28-46), with
 dgl's constructor arguments, parameter names and formulas, on the block ops of
 gnnflow_amd.ops.  dgl (requirements.txt: dgl >= 0.7) is not vendored in the reference; these
-follow its documented layer definitions.
+follow its documented layer definitions.  Both run under torch.autocast('cuda',
+dtype=torch.bfloat16) with no cast by the caller: ops.block_reduce, block_max and block_gat take
+the bfloat16 rows the Linear layers return (models.SAGE and models.GAT are built from them).
 
 TimeEncode / TemporalAttentionLayer are the reference's own temporal attention
 (gnnflow/models/modules/layers.py:16-168, the layer of TGN, TGAT and DySAT) with its constructor
@@ -23,7 +25,18 @@ from . import ops
 
 class SAGEConv(nn.Module):
     """GraphSAGE layer: h_i' = W_self h_i + W_neigh * AGG_{j in N(i)} h_j + b.
-    aggregator_type 'mean', 'gcn' or 'pool' ('lstm' is not built)."""
+    aggregator_type 'mean', 'gcn' or 'pool' ('lstm' is not built).
+
+    Under torch.autocast('cuda', dtype=torch.bfloat16) every aggregator runs on either side of
+    `lin_before_mp`, with and without edge weights.  fc_neigh / fc_pool return bfloat16, and
+    ops.block_reduce / ops.block_max take the rows as they come, float32 features or bfloat16
+    Linear outputs: float32 arithmetic inside, one rounding on store (ops.py).  Edge weights stay
+    float32.  Two small operands are brought to the large one's dtype so that torch's promotion
+    does not widen a [num_dst, out_feats] tensor only for the next Linear to narrow it again (the
+    h_dst.to(agg.dtype) of TemporalAttentionLayer): the bias, and in 'gcn' the degrees, where
+    degree + 1 is added as integers first so that bfloat16 rounds it once.  The output has the
+    dtype of the Linear outputs, bfloat16.  Outside autocast these are no-ops and nothing
+    differs."""
 
     def __init__(self, in_feats, out_feats, aggregator_type, feat_drop=0., bias=True, norm=None,
                  activation=None):
@@ -82,13 +95,15 @@ class SAGEConv(nn.Module):
                 src = self.fc_neigh(feat_src) if lin_before_mp else feat_src
                 dst = src[:graph.num_dst_nodes()]
                 total = ops.block_reduce(graph, src, w, mean=False)
-                degs = graph.in_degrees().to(total.dtype)
-                h_neigh = (total + dst) / (degs.unsqueeze(-1) + 1)
+                # degree + 1 in integers, then one cast: exact in float32 as before, and rounded
+                # once where total is bfloat16
+                degs1 = (graph.in_degrees() + 1).to(total.dtype)
+                h_neigh = (total + dst) / degs1.unsqueeze(-1)
                 if not lin_before_mp:
                     h_neigh = self.fc_neigh(h_neigh)
         rst = h_neigh if self._aggre_type == 'gcn' else self.fc_self(h_self) + h_neigh
         if self.bias is not None:
-            rst = rst + self.bias
+            rst = rst + self.bias.to(rst.dtype)      # a no-op unless rst is bfloat16 (autocast)
         if self.activation is not None:
             rst = self.activation(rst)
         if self.norm is not None:
@@ -119,7 +134,18 @@ class GATConv(nn.Module):
     the mask torch's own dropout would draw).  get_attention=True always takes the composed
     chain, where the returned attention stays differentiable.  Both attributes are plain Python
     attributes, not part of the state dict; their defaults are FUSED_GAT_DEFAULT and
-    FUSED_GAT_DROPOUT_DEFAULT."""
+    FUSED_GAT_DROPOUT_DEFAULT.
+
+    Under torch.autocast('cuda', dtype=torch.bfloat16) every one of these paths runs.  fc
+    returns bfloat16; el and er come out float32 (bfloat16 * float32 parameter promotes, and sum
+    is on autocast's float32 list), so ops.edge_softmax sees float32 as always, and
+    ops.block_reduce / ops.block_gat take the bfloat16 rows with the float32 attention: float32
+    arithmetic inside, one rounding on store (ops.py).  The bias and the residual (float32 when
+    res_fc is the identity) are brought to the aggregate's dtype, as TemporalAttentionLayer does
+    with h_dst.to(agg.dtype), so that promotion does not widen the [num_dst, H, D] result only for
+    the next Linear to narrow it again; the output is bfloat16, and the attention
+    get_attention=True returns float32.  Outside autocast the casts are no-ops and nothing
+    differs."""
 
     def __init__(self, in_feats, out_feats, num_heads, feat_drop=0., attn_drop=0.,
                  negative_slope=0.2, residual=False, activation=None,
@@ -194,9 +220,10 @@ class GATConv(nn.Module):
             a = self.attn_drop(ops.edge_softmax(graph, e))   # [E, H]
             rst = ops.block_reduce(graph, feat_src, a)       # u_mul_e + sum -> [num_dst, H, D]
         if self.res_fc is not None:
-            rst = rst + self.res_fc(h_src[:num_dst]).view(num_dst, H, D)
+            # an identity res_fc hands on the float32 input: one cast of the [num_dst, H * D] side
+            rst = rst + self.res_fc(h_src[:num_dst]).view(num_dst, H, D).to(rst.dtype)
         if self.bias is not None:
-            rst = rst + self.bias.view(1, H, D)
+            rst = rst + self.bias.to(rst.dtype).view(1, H, D)      # a no-op outside autocast
         if self.activation:
             rst = self.activation(rst)
         if get_attention:

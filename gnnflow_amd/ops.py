@@ -20,13 +20,18 @@ make on a sampled block, on HIP segment kernels (csrc/block_ops.hip) with autogr
                                            the MRR, counted on the GPU without a sort, a sync or a copy
                                            to the host (csrc/link_metrics.hip)
 
-block_attention, time_encode_cat and edge_score also run on bfloat16 (the tensors autocast hands
-them), by one rule: float32 arithmetic, one rounding on store.  Every bfloat16 element is widened
-to float32 where it is loaded (exact), the arithmetic is the float32 kernels' own in the same
-order, and each bfloat16 result is rounded once, to nearest even.  So
-op(x.bfloat16()) == op(x.bfloat16().float()).to(torch.bfloat16) bit for bit, forward and backward,
-and the float32 outputs (attention, scores, parameter gradients) are equal.  The ops choose by
-the dtypes they are given and behave the same inside and outside an autocast region.
+block_attention, block_reduce, block_max, block_gat, time_encode_cat and edge_score also run on
+bfloat16 (the tensors autocast hands them), by one rule: float32 arithmetic, one rounding on
+store.  Every bfloat16 element is widened to float32 where it is loaded (exact), the arithmetic is
+the float32 kernels' own in the same order, and each bfloat16 result is rounded once, to nearest
+even.  So op(x.bfloat16()) == op(x.bfloat16().float()).to(torch.bfloat16) bit for bit, forward and
+backward, and the float32 outputs (attention, scores, parameter gradients) are equal.  The ops
+choose by the dtypes they are given and behave the same inside and outside an autocast region.
+What may be bfloat16 is what autocast makes bfloat16, the rows a Linear returns: q / k / v, the
+source rows of block_reduce and block_max, feat of block_gat.  What autocast leaves float32 stays
+float32 only: edge weights (a softmax output), el and er (a float32 sum), and edge_softmax
+altogether.  A gradient of a source may meet several edges (an explicit col): it is summed in a
+float32 scratch and rounded once, never once per edge.
 
 A block's edges are grouped by destination (the sampler emits them that way); blocks built by
 hand with unordered edges are handled through a stable permutation.
@@ -98,11 +103,21 @@ class _EdgeSoftmax(torch.autograd.Function):
         return gx, None, None
 
 
+def _scratch(t, col, wanted=True):
+    """The float32 buffer a bfloat16 gradient of `t`'s shape is summed in when the block has an
+    explicit col; None for float32, for the sampler's layout, or when it is not wanted."""
+    if t.dtype != torch.bfloat16 or col is None or not wanted:
+        return None
+    return torch.empty(t.shape, dtype=torch.float32, device=t.device)
+
+
 class _BlockReduce(torch.autograd.Function):
     @staticmethod
+    @_fwd
     def forward(ctx, src, weight, offsets, col, num_dst, mean, num_edges):
-        # col is None for the sampler's layout (source of edge k = row num_dst + k)
-        s = _f32(src)
+        # col is None for the sampler's layout (source of edge k = row num_dst + k); src fp32 or
+        # bf16 (checked by block_reduce), weight fp32; out in src's dtype
+        s = src.contiguous()
         num_src = s.shape[0]
         dim = s.numel() // num_src if num_src else 0
         w, heads = None, 1
@@ -113,10 +128,12 @@ class _BlockReduce(torch.autograd.Function):
             if dim % max(heads, 1):
                 raise ValueError("feature size {} is not a multiple of the {} edge-weight heads"
                                  .format(dim, heads))
-        out = torch.zeros((num_dst,) + tuple(s.shape[1:]), dtype=torch.float32, device=s.device)
+        out = torch.zeros((num_dst,) + tuple(s.shape[1:]), dtype=s.dtype, device=s.device)
         if num_dst and dim and num_edges:
+            lib = _capi.load()
+            fn = lib.gf_block_reduce_bf16 if s.dtype == torch.bfloat16 else lib.gf_block_reduce
             with torch.cuda.device(s.device):
-                _capi.check(_capi.load().gf_block_reduce(
+                _capi.check(fn(
                     offsets.data_ptr(), num_dst, _ptr(col), s.data_ptr(), dim, _ptr(w), heads,
                     1 if mean else 0, out.data_ptr(), s.device.index, _stream(s.device)))
         ctx.save_for_backward(s, w, offsets, col)
@@ -124,10 +141,11 @@ class _BlockReduce(torch.autograd.Function):
         return out
 
     @staticmethod
+    @_bwd
     def backward(ctx, grad):
         s, w, offsets, col = ctx.saved_tensors
         num_dst, mean, heads, dim, num_edges = ctx.meta
-        g = _f32(grad)
+        g = _grad_as(grad, s.dtype)
         need_src, need_w = ctx.needs_input_grad[0], w is not None and ctx.needs_input_grad[1]
         gs = torch.empty_like(s) if need_src else None
         gw = torch.zeros_like(w) if need_w else None
@@ -136,42 +154,56 @@ class _BlockReduce(torch.autograd.Function):
                 if gs is not None:
                     gs.zero_()
             else:
-                with torch.cuda.device(s.device):
-                    _capi.check(_capi.load().gf_block_reduce_backward(
-                        offsets.data_ptr(), num_dst, _ptr(col), s.data_ptr(), dim, _ptr(w),
+                lib = _capi.load()
+                args = (offsets.data_ptr(), num_dst, _ptr(col), s.data_ptr(), dim, _ptr(w),
                         heads, 1 if mean else 0, g.data_ptr(), _ptr(gs), s.shape[0], _ptr(gw),
-                        s.device.index, _stream(s.device)))
+                        s.device.index, _stream(s.device))
+                with torch.cuda.device(s.device):
+                    if s.dtype == torch.bfloat16:
+                        _capi.check(lib.gf_block_reduce_backward_bf16(
+                            *args, _ptr(_scratch(s, col, need_src))))
+                    else:
+                        _capi.check(lib.gf_block_reduce_backward(*args))
         return gs, gw, None, None, None, None, None
 
 
 class _BlockMax(torch.autograd.Function):
     @staticmethod
+    @_fwd
     def forward(ctx, src, offsets, col, num_dst, num_edges):
-        s = _f32(src)
+        s = src.contiguous()      # fp32 or bf16 (checked by block_max); out in its dtype
         num_src = s.shape[0]
         dim = s.numel() // num_src if num_src else 0
-        out = torch.zeros((num_dst,) + tuple(s.shape[1:]), dtype=torch.float32, device=s.device)
+        out = torch.zeros((num_dst,) + tuple(s.shape[1:]), dtype=s.dtype, device=s.device)
         arg = torch.full((num_dst, max(dim, 1)), -1, dtype=torch.int64, device=s.device)
         if num_dst and dim and num_edges:
+            lib = _capi.load()
+            fn = lib.gf_block_reduce_max_bf16 if s.dtype == torch.bfloat16 \
+                else lib.gf_block_reduce_max
             with torch.cuda.device(s.device):
-                _capi.check(_capi.load().gf_block_reduce_max(
+                _capi.check(fn(
                     offsets.data_ptr(), num_dst, _ptr(col), s.data_ptr(), dim, out.data_ptr(),
                     arg.data_ptr(), s.device.index, _stream(s.device)))
         ctx.save_for_backward(arg, col)
-        ctx.meta = (num_dst, dim, tuple(s.shape))
+        ctx.meta = (num_dst, dim, tuple(s.shape), s.dtype)
         ctx.mark_non_differentiable(arg)
         return out
 
     @staticmethod
+    @_bwd
     def backward(ctx, grad):
         arg, col = ctx.saved_tensors
-        num_dst, dim, shape = ctx.meta
-        g = _f32(grad)
-        gs = torch.empty(shape, dtype=torch.float32, device=g.device)
+        num_dst, dim, shape, dtype = ctx.meta
+        g = _grad_as(grad, dtype)
+        gs = torch.empty(shape, dtype=dtype, device=g.device)
+        lib = _capi.load()
+        args = (num_dst, _ptr(col), dim, _ptr(g), arg.data_ptr(), gs.data_ptr(), shape[0],
+                g.device.index, _stream(g.device))
         with torch.cuda.device(g.device):
-            _capi.check(_capi.load().gf_block_reduce_max_backward(
-                num_dst, _ptr(col), dim, _ptr(g), arg.data_ptr(), gs.data_ptr(), shape[0],
-                g.device.index, _stream(g.device)))
+            if dtype == torch.bfloat16:
+                _capi.check(lib.gf_block_reduce_max_backward_bf16(*args, _ptr(_scratch(gs, col))))
+            else:
+                _capi.check(lib.gf_block_reduce_max_backward(*args))
         return gs, None, None, None, None
 
 
@@ -381,19 +413,29 @@ def block_attention(block, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
 
 class _BlockGat(torch.autograd.Function):
     @staticmethod
+    @_fwd
     def forward(ctx, feat, el, er, offsets, col, num_dst, E, slope, p, seed, want_dropped):
-        # feat [num_src, H, D], el [num_src, H], er [num_dst, H] contiguous fp32; col is None for
-        # the sampler's layout.  att is the pre-dropout softmax (saved, with out, for backward).
+        # feat [num_src, H, D] fp32 or bf16, el [num_src, H], er [num_dst, H] fp32, contiguous;
+        # col is None for the sampler's layout.  att is the pre-dropout softmax (saved, with the
+        # float32 out, for backward).  bf16: the kernel writes out twice, rounded (returned) and
+        # as summed ([num_dst, H, D] float32, saved).
         num_src, H, D = feat.shape
-        out = torch.empty((num_dst, H, D), dtype=torch.float32, device=feat.device)
+        bf16 = feat.dtype == torch.bfloat16
+        out = torch.empty((num_dst, H, D), dtype=feat.dtype, device=feat.device)
+        out32 = torch.empty((num_dst, H, D), dtype=torch.float32, device=feat.device) \
+            if bf16 else out
         att = torch.empty((E, H), dtype=torch.float32, device=feat.device)
         dropped = torch.empty_like(att) if want_dropped and p > 0 else None
-        with torch.cuda.device(feat.device):
-            _capi.check(_capi.load().gf_block_gat(
-                offsets.data_ptr(), num_dst, E, _ptr(col), num_src, H, D, feat.data_ptr(),
+        lib = _capi.load()
+        args = (offsets.data_ptr(), num_dst, E, _ptr(col), num_src, H, D, feat.data_ptr(),
                 el.data_ptr(), er.data_ptr(), slope, p, seed, out.data_ptr(), att.data_ptr(),
-                _ptr(dropped), feat.device.index, _stream(feat.device)))
-        ctx.save_for_backward(feat, el, er, att, out, offsets, col)
+                _ptr(dropped), feat.device.index, _stream(feat.device))
+        with torch.cuda.device(feat.device):
+            if bf16:
+                _capi.check(lib.gf_block_gat_bf16(*args, out32.data_ptr()))
+            else:
+                _capi.check(lib.gf_block_gat(*args))
+        ctx.save_for_backward(feat, el, er, att, out32, offsets, col)
         ctx.meta = (slope, p, seed)
         shown = dropped if p > 0 else att
         if not want_dropped:
@@ -402,22 +444,28 @@ class _BlockGat(torch.autograd.Function):
         return out, shown
 
     @staticmethod
+    @_bwd
     def backward(ctx, grad, _grad_att):
-        feat, el, er, att, out, offsets, col = ctx.saved_tensors
+        feat, el, er, att, out32, offsets, col = ctx.saved_tensors
         slope, p, seed = ctx.meta
-        g = _f32(grad)
+        g = _grad_as(grad, feat.dtype)
         num_src, H, D = feat.shape
         need_feat, need_el, need_er = ctx.needs_input_grad[:3]
         gfeat = torch.empty_like(feat) if need_feat else None
         gel = torch.empty_like(el) if need_el else None
         ger = torch.empty_like(er) if need_er else None
         if need_feat or need_el or need_er:
-            with torch.cuda.device(feat.device):
-                _capi.check(_capi.load().gf_block_gat_backward(
-                    offsets.data_ptr(), er.shape[0], att.shape[0], _ptr(col), num_src, H, D,
+            lib = _capi.load()
+            args = (offsets.data_ptr(), er.shape[0], att.shape[0], _ptr(col), num_src, H, D,
                     feat.data_ptr(), el.data_ptr(), er.data_ptr(), att.data_ptr(),
-                    out.data_ptr(), slope, p, seed, g.data_ptr(), _ptr(gfeat), _ptr(gel),
-                    _ptr(ger), feat.device.index, _stream(feat.device)))
+                    out32.data_ptr(), slope, p, seed, g.data_ptr(), _ptr(gfeat), _ptr(gel),
+                    _ptr(ger), feat.device.index, _stream(feat.device))
+            with torch.cuda.device(feat.device):
+                if feat.dtype == torch.bfloat16:
+                    _capi.check(lib.gf_block_gat_backward_bf16(
+                        *args, _ptr(_scratch(feat, col, need_feat))))
+                else:
+                    _capi.check(lib.gf_block_gat_backward(*args))
         return gfeat, gel, ger, None, None, None, None, None, None, None, None
 
 
@@ -426,7 +474,7 @@ class _NoEdgeGat(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feat, el, er):
         ctx.save_for_backward(feat, el, er)
-        return torch.zeros((er.shape[0],) + tuple(feat.shape[1:]), dtype=torch.float32,
+        return torch.zeros((er.shape[0],) + tuple(feat.shape[1:]), dtype=feat.dtype,
                            device=feat.device)
 
     @staticmethod
@@ -449,6 +497,12 @@ def block_gat(block, feat: torch.Tensor, el: torch.Tensor, er: torch.Tensor,
     differentiable).  Differentiable in feat, el and er; the forward's out is kept for the
     backward, which then reads every feat row once.
 
+    feat may instead be bfloat16 (fc(h) under autocast) with el and er float32 (there a float32
+    sum); anything else raises TypeError.  The module's rule -- float32 arithmetic, one rounding
+    on store -- applies: out and the gradient of feat are bfloat16 and equal, bit for bit, the
+    float32 op's on feat.float() rounded once; the attention and the gradients of el and er are
+    float32 and equal to its.  The out kept for the backward is the float32 one, before rounding.
+
     dropout_p / dropout_seed are those of block_attention, with the same mask: p =
     float32(dropout_p) in [0, 1), i the position of an edge in the grouped order of
     block.segments(), keep[i, h] = gf_philox4x32_10_first(dropout_seed, i * H + h, 0) >=
@@ -459,7 +513,8 @@ def block_gat(block, feat: torch.Tensor, el: torch.Tensor, er: torch.Tensor,
 
     On a sampler block (segments()[1] is None: source of edge k = node num_dst + k) the backward
     uses no atomics and two runs give the same bits.  On a block with an explicit col a source
-    may feed several edges; the gradients of feat and el are then accumulated with atomic adds:
+    may feed several edges; the gradients of feat and el are then accumulated with atomic adds
+    (float32 ones also for a bfloat16 feat: in a float32 scratch, rounded once afterwards):
     correct within the same error bounds, rows no edge reads exact zeros, but NOT bit-identical
     from run to run."""
     dropout_p = float(dropout_p)
@@ -477,8 +532,11 @@ def block_gat(block, feat: torch.Tensor, el: torch.Tensor, er: torch.Tensor,
     for name, t in (("feat", feat), ("el", el), ("er", er)):
         if not isinstance(t, torch.Tensor):
             raise TypeError("{} must be a tensor, got {}".format(name, type(t).__name__))
-        if t.dtype != torch.float32:
-            raise TypeError("block_gat computes in float32, {} is {}".format(name, t.dtype))
+    if feat.dtype not in (torch.float32, torch.bfloat16) or el.dtype != torch.float32 or \
+            er.dtype != torch.float32:
+        raise TypeError("block_gat computes in float32 and takes feat float32 or bfloat16 with "
+                        "el and er float32, feat is {}, el is {} and er is {}".format(
+                            feat.dtype, el.dtype, er.dtype))
     num_dst, num_src, E = block.num_dst_nodes(), block.num_src_nodes(), block.num_edges()
     if feat.dim() != 3:
         raise ValueError("feat must be [num_src, H, D], got {}".format(tuple(feat.shape)))
@@ -825,9 +883,21 @@ def link_metrics(pos: torch.Tensor, neg: torch.Tensor,
     return out
 
 
+def _src_dtype(op, src):
+    if not isinstance(src, torch.Tensor):
+        raise TypeError("src must be a tensor, got {}".format(type(src).__name__))
+    if src.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("{} computes in float32 and takes src float32 or bfloat16, src is {}"
+                        .format(op, src.dtype))
+
+
 def block_max(block, src: torch.Tensor) -> torch.Tensor:
     """out[d] = element-wise max over the edges into d of src[source(k)] (0 without in-edges):
-    update_all(copy_src, max)."""
+    update_all(copy_src, max).  src float32 or bfloat16 (anything else raises TypeError); out and
+    the gradient of src have its dtype.  A maximum is one of the inputs, so the bfloat16 op
+    returns exactly what the float32 op returns on src.float(), and routes the gradient to the
+    same edge (the lowest on ties)."""
+    _src_dtype("block_max", src)
     if src.shape[0] != block.num_src_nodes():
         raise ValueError("src must have one row per source node")
     offsets, col, _ = block.segments()
@@ -849,7 +919,23 @@ def edge_softmax(block, logits: torch.Tensor) -> torch.Tensor:
 def block_reduce(block, src: torch.Tensor, edge_weight=None, mean: bool = False) -> torch.Tensor:
     """out[d] = sum (mean) over the edges k into d of edge_weight[k] * src[source(k)].
     src: [num_src_nodes, ...]; edge_weight: None or [num_edges, heads(, 1)], each head
-    scaling `feature_size / heads` consecutive values."""
+    scaling `feature_size / heads` consecutive values.
+
+    src is float32 or bfloat16, edge_weight float32 (under autocast a softmax output); anything
+    else raises TypeError.  With a bfloat16 src the module's rule applies -- float32 arithmetic,
+    one rounding on store --: out and the gradient of src are bfloat16 and equal, bit for bit,
+    the float32 op's on src.float() rounded once (on a block with an explicit col, where a source
+    may feed several edges, that gradient is summed in float32 and rounded once at the end); the
+    gradient of edge_weight is float32 and equal to its."""
+    _src_dtype("block_reduce", src)
+    if edge_weight is not None:
+        if not isinstance(edge_weight, torch.Tensor):
+            raise TypeError("edge_weight must be a tensor or None, got {}".format(
+                type(edge_weight).__name__))
+        if edge_weight.dtype != torch.float32:
+            raise TypeError("block_reduce computes in float32 and takes edge_weight float32 "
+                            "(src float32 or bfloat16), src is {} and edge_weight is {}".format(
+                                src.dtype, edge_weight.dtype))
     if src.shape[0] != block.num_src_nodes():
         raise ValueError("src must have one row per source node")
     offsets, col, perm = block.segments()

@@ -892,6 +892,58 @@ GF_API int gf_block_gat_backward(const int64_t* d_offsets, size_t num_dst, size_
                                  const float* d_grad_out, float* d_grad_feat, float* d_grad_el,
                                  float* d_grad_er, int device, void* stream);
 
+/* gf_block_reduce, gf_block_reduce_max, gf_block_gat and their backward passes for bfloat16
+ * source rows (d_src, d_feat), outputs (d_out) and their gradients (d_grad_out, d_grad_src,
+ * d_grad_feat), carried as uint16_t.  What autocast leaves float32 stays float32: the edge
+ * weights and their gradient, d_arg, d_el, d_er, d_att, d_att_dropped, d_grad_el, d_grad_er.
+ * Every bfloat16 element is widened where it is loaded (exact), the arithmetic is that of the
+ * float32 entry point in the same order, and each bfloat16 result is rounded once, to nearest
+ * even, where it is stored: the bfloat16 results hold, bit for bit, the float32 entry point's
+ * results on the widened inputs rounded to bfloat16, and the float32 results are equal to its.
+ * Arguments, order, checks and limits are the float32 siblings'; what a bfloat16 entry point
+ * needs besides comes LAST, after `stream`:
+ *   d_scratch   float32 [num_src, dim] (gf_block_gat_backward_bf16: [num_src, heads, head_dim]),
+ *               caller-owned, contents irrelevant.  With d_col the gradient of the source rows is
+ *               accumulated there with float32 atomic adds -- a bfloat16 add would round once per
+ *               edge -- and rounded into d_grad_src / d_grad_feat by one more launch.  May be
+ *               NULL when d_col is NULL (each element is then stored once, directly in bfloat16,
+ *               without atomics) or when that gradient is not asked for.
+ *   d_out_f32   float32 [num_dst, heads, head_dim]: gf_block_gat_bf16 writes the sums there
+ *               before it rounds them into d_out, and gf_block_gat_backward_bf16 takes it where
+ *               gf_block_gat_backward takes d_out (the rounded d_out would give another
+ *               gout . out than the float32 op's).  NULL in the forward: not written. */
+GF_API int gf_block_reduce_bf16(const int64_t* d_offsets, size_t num_dst, const int64_t* d_col,
+                                const uint16_t* d_src, size_t dim, const float* d_edge_weight,
+                                size_t heads, int mean, uint16_t* d_out, int device,
+                                void* stream);
+GF_API int gf_block_reduce_backward_bf16(const int64_t* d_offsets, size_t num_dst,
+                                         const int64_t* d_col, const uint16_t* d_src, size_t dim,
+                                         const float* d_edge_weight, size_t heads, int mean,
+                                         const uint16_t* d_grad_out, uint16_t* d_grad_src,
+                                         size_t num_src, float* d_grad_edge_weight, int device,
+                                         void* stream, float* d_scratch);
+GF_API int gf_block_reduce_max_bf16(const int64_t* d_offsets, size_t num_dst,
+                                    const int64_t* d_col, const uint16_t* d_src, size_t dim,
+                                    uint16_t* d_out, int64_t* d_arg, int device, void* stream);
+GF_API int gf_block_reduce_max_backward_bf16(size_t num_dst, const int64_t* d_col, size_t dim,
+                                             const uint16_t* d_grad_out, const int64_t* d_arg,
+                                             uint16_t* d_grad_src, size_t num_src, int device,
+                                             void* stream, float* d_scratch);
+GF_API int gf_block_gat_bf16(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                             const int64_t* d_col, size_t num_src, size_t heads, size_t head_dim,
+                             const uint16_t* d_feat, const float* d_el, const float* d_er,
+                             float negative_slope, float p, uint64_t seed, uint16_t* d_out,
+                             float* d_att, float* d_att_dropped, int device, void* stream,
+                             float* d_out_f32);
+GF_API int gf_block_gat_backward_bf16(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                                      const int64_t* d_col, size_t num_src, size_t heads,
+                                      size_t head_dim, const uint16_t* d_feat, const float* d_el,
+                                      const float* d_er, const float* d_att,
+                                      const float* d_out_f32, float negative_slope, float p,
+                                      uint64_t seed, const uint16_t* d_grad_out,
+                                      uint16_t* d_grad_feat, float* d_grad_el, float* d_grad_er,
+                                      int device, void* stream, float* d_scratch);
+
 /* Fused time encoding (the reference's TimeEncode, layers.py:16-42, and the torch.cat around
  * it): d_out [n, width_a + width_b + dim_time], row-major and contiguous,
  *   out[i, 0:width_a]                = a[i, :]      (width_a may be 0, d_a NULL)
