@@ -303,6 +303,15 @@ PROTOTYPES = {
                                          C.c_int, _p]),
     "gf_edge_score_backward_bf16": (C.c_int, [_p, _p, _p, _sz, _sz, _sz, _p, _p, _sz, _p, _p, _p, _p,
                                               C.c_int, _p]),
+    "gf_layer_epilogue": (C.c_int, [_p, _p, _p, _sz, _sz, C.c_float, C.c_float, C.c_uint64, _p, _p,
+                                    _p, C.c_int, _p]),
+    "gf_layer_epilogue_bf16": (C.c_int, [_p, _p, _p, _sz, _sz, C.c_float, C.c_float, C.c_uint64,
+                                         _p, _p, _p, C.c_int, _p]),
+    "gf_layer_epilogue_backward_partial_rows": (C.c_int, [_sz, C.POINTER(_sz)]),
+    "gf_layer_epilogue_backward": (C.c_int, [_p, _p, _p, _p, _sz, _sz, C.c_float, C.c_uint64, _p,
+                                             _p, _sz, _p, _p, _p, C.c_int, _p]),
+    "gf_layer_epilogue_backward_bf16": (C.c_int, [_p, _p, _p, _p, _sz, _sz, C.c_float, C.c_uint64,
+                                                  _p, _p, _sz, _p, _p, _p, C.c_int, _p]),
     "gf_link_metrics_partial_rows": (C.c_int, [_sz, C.POINTER(_sz)]),
     "gf_link_metrics": (C.c_int, [_p, _p, _sz, _sz, _p, _sz, _p, _p, C.c_int, _p]),
     "gf_debug_part_host_us": (C.c_int, [C.POINTER(C.c_double), C.c_int]),

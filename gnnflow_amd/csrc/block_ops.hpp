@@ -203,6 +203,36 @@ void edge_score_bf16_backward(const uint16_t* d_src, const uint16_t* d_dst, cons
                               uint16_t* d_grad_dst, float* d_grad_w, float* d_grad_bias,
                               int device, hipStream_t stream);
 
+// layer_epilogue.hip: out = layer_norm(relu(dropout(x))) over the rows of x [num_rows, dim] in one
+// launch, with mean and rstd [num_rows] kept for the backward and the dropout mask drawn from
+// (p, seed) in both directions, and its gradients in at most two launches.  The backward needs a
+// caller-owned buffer of layer_epilogue_backward_partial_rows(num_rows) * 2 * dim floats when
+// d_grad_gamma or d_grad_beta is asked for; a null d_grad_x / d_grad_gamma / d_grad_beta is
+// skipped.  num_rows == 0 launches nothing (the backward zeroes the parameter gradients given).
+constexpr size_t kLayerEpilogueMaxWidth = 1024;
+constexpr size_t kLayerEpilogueMaxPartialRows = 1024;
+size_t layer_epilogue_backward_partial_rows(size_t num_rows);
+void layer_epilogue_forward(const float* d_x, const float* d_gamma, const float* d_beta,
+                            size_t num_rows, size_t dim, float eps, float p, uint64_t seed,
+                            float* d_out, float* d_mean, float* d_rstd, int device,
+                            hipStream_t stream);
+void layer_epilogue_backward(const float* d_x, const float* d_gamma, const float* d_mean,
+                             const float* d_rstd, size_t num_rows, size_t dim, float p,
+                             uint64_t seed, const float* d_grad_out, float* d_partials,
+                             size_t partial_rows, float* d_grad_x, float* d_grad_gamma,
+                             float* d_grad_beta, int device, hipStream_t stream);
+// The same with bfloat16 x rows and a bfloat16 grad_x (widened on load, rounded once on store);
+// everything else float32.
+void layer_epilogue_bf16_forward(const uint16_t* d_x, const float* d_gamma, const float* d_beta,
+                                 size_t num_rows, size_t dim, float eps, float p, uint64_t seed,
+                                 float* d_out, float* d_mean, float* d_rstd, int device,
+                                 hipStream_t stream);
+void layer_epilogue_bf16_backward(const uint16_t* d_x, const float* d_gamma, const float* d_mean,
+                                  const float* d_rstd, size_t num_rows, size_t dim, float p,
+                                  uint64_t seed, const float* d_grad_out, float* d_partials,
+                                  size_t partial_rows, uint16_t* d_grad_x, float* d_grad_gamma,
+                                  float* d_grad_beta, int device, hipStream_t stream);
+
 // link_metrics.hip: out[3] = {AP, AUC, MRR} (float64) of the scores pos[num_pos] of the true
 // edges and neg[num_neg] of the negative ones, by counting instead of sorting, in two launches
 // and without atomics.  MRR exists when num_neg is a multiple of num_pos (positive i's own

@@ -354,6 +354,55 @@ int gf_edge_score_backward_bf16(const uint16_t* d_src, const uint16_t* d_dst, co
   });
 }
 
+static_assert(GF_LAYER_EPILOGUE_MAX_WIDTH == gf::kLayerEpilogueMaxWidth,
+              "gnnflow_hip.h and block_ops.hpp disagree on the layer-epilogue width");
+int gf_layer_epilogue(const float* d_x, const float* d_gamma, const float* d_beta,
+                      size_t num_rows, size_t dim, float eps, float p, uint64_t seed,
+                      float* d_out, float* d_mean, float* d_rstd, int device, void* stream) {
+  return guarded([&] {
+    gf::layer_epilogue_forward(d_x, d_gamma, d_beta, num_rows, dim, eps, p, seed, d_out, d_mean,
+                               d_rstd, device, as_stream(stream));
+  });
+}
+int gf_layer_epilogue_backward_partial_rows(size_t num_rows, size_t* rows) {
+  return guarded([&] {
+    GF_REQUIRE(rows != nullptr, "gf_layer_epilogue_backward_partial_rows: null output");
+    *rows = gf::layer_epilogue_backward_partial_rows(num_rows);
+  });
+}
+int gf_layer_epilogue_backward(const float* d_x, const float* d_gamma, const float* d_mean,
+                               const float* d_rstd, size_t num_rows, size_t dim, float p,
+                               uint64_t seed, const float* d_grad_out, float* d_partials,
+                               size_t partial_rows, float* d_grad_x, float* d_grad_gamma,
+                               float* d_grad_beta, int device, void* stream) {
+  return guarded([&] {
+    gf::layer_epilogue_backward(d_x, d_gamma, d_mean, d_rstd, num_rows, dim, p, seed, d_grad_out,
+                                d_partials, partial_rows, d_grad_x, d_grad_gamma, d_grad_beta,
+                                device, as_stream(stream));
+  });
+}
+int gf_layer_epilogue_bf16(const uint16_t* d_x, const float* d_gamma, const float* d_beta,
+                           size_t num_rows, size_t dim, float eps, float p, uint64_t seed,
+                           float* d_out, float* d_mean, float* d_rstd, int device,
+                           void* stream) {
+  return guarded([&] {
+    gf::layer_epilogue_bf16_forward(d_x, d_gamma, d_beta, num_rows, dim, eps, p, seed, d_out,
+                                    d_mean, d_rstd, device, as_stream(stream));
+  });
+}
+int gf_layer_epilogue_backward_bf16(const uint16_t* d_x, const float* d_gamma,
+                                    const float* d_mean, const float* d_rstd, size_t num_rows,
+                                    size_t dim, float p, uint64_t seed, const float* d_grad_out,
+                                    float* d_partials, size_t partial_rows, uint16_t* d_grad_x,
+                                    float* d_grad_gamma, float* d_grad_beta, int device,
+                                    void* stream) {
+  return guarded([&] {
+    gf::layer_epilogue_bf16_backward(d_x, d_gamma, d_mean, d_rstd, num_rows, dim, p, seed,
+                                     d_grad_out, d_partials, partial_rows, d_grad_x, d_grad_gamma,
+                                     d_grad_beta, device, as_stream(stream));
+  });
+}
+
 static_assert(GF_LINK_METRICS_MAX_SCORES == gf::kLinkMetricsMaxScores &&
                   GF_LINK_METRICS_TILE == gf::kLinkMetricsTile &&
                   GF_LINK_METRICS_PARTIAL_WORDS == gf::kLinkMetricsPartialWords,

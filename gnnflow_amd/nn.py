@@ -249,6 +249,18 @@ FUSED_ATTENTION_DROPOUT_DEFAULT = False
 # (profiles/edge_score_microbench.txt).
 FUSED_EDGE_SCORE_DEFAULT = True
 
+# Default of `fused_epilogue` in TemporalAttentionLayer.  True only once
+# scripts/layer_epilogue_bench.py has shown ops.dropout_relu_layer_norm, forward + backward, ahead
+# of the torch line at every one of its shapes by more than the torch chain's own round-to-round
+# spread (profiles/layer_epilogue_bench.jsonl).  It did not hold on the run
+# recorded there.  Medians per iteration: the op 62.3-92.8 us (62-67 us in its quietest rounds at
+# every shape: the pace at which the host enqueues its three launches), torch 53.5-128.9 us.  The
+# op is ahead by more than torch's spread on 6 of the 12 lines (R = 19 800: float32 p = 0 and
+# bfloat16 at both p; D = 172: float32 p = 0.1 and bfloat16 at both p), ahead by less than the
+# spread on 4, and behind at float32 without dropout at R = 1 800 (0.71x at D = 100, 0.86x at
+# D = 172).  So the default stays False.
+FUSED_EPILOGUE_DEFAULT = False
+
 
 class TimeEncode(nn.Module):
     """TGAT's time encoding cos(w * dt + b): w = 1 / 10^linspace(0, 9, dim_time), b = 0 at
@@ -299,7 +311,18 @@ class TemporalAttentionLayer(nn.Module):
     cast again).  The composed chain edge_softmax -> dropout -> block_reduce is float32 only:
     where it is taken (`fused_attention` off, or dropout active with `fused_attention_dropout`
     off) q, k, v are widened with .float() in front of it.  The output is float32, layer_norm's
-    type under autocast.  Outside autocast nothing differs."""
+    type under autocast.  Outside autocast nothing differs.
+
+    With `fused_epilogue` the last line after w_out, layer_norm(relu(dropout(.))), is one
+    ops.dropout_relu_layer_norm call each way instead of torch's dropout, relu, cast and
+    layer_norm kernels: it takes w_out's rows as they come (float32, or bfloat16 under autocast),
+    returns float32 and writes no mask.  In training with 0 < dropout.p < 1 the dropout happens
+    inside the kernel, from the op's stateless Philox mask with a seed drawn per forward from
+    torch's default CPU generator, after the attention's when both are drawn: reproducible under
+    torch.manual_seed, but not the mask nn.Dropout would draw.  With the flag off no seed is
+    drawn.  dropout.p == 1, a layer_norm without affine parameters, rows that are not on the GPU
+    or not float32 / bfloat16, and dim_out above ops.LAYER_EPILOGUE_MAX_WIDTH take the torch
+    line."""
 
     def __init__(self, dim_node: int, dim_edge: int, dim_time: int, dim_out: int, num_head: int,
                  dropout: float, att_dropout: float):
@@ -328,6 +351,9 @@ class TemporalAttentionLayer(nn.Module):
         self.fused_attention_dropout = FUSED_ATTENTION_DROPOUT_DEFAULT
         # False: time_enc + torch.cat instead of ops.time_encode_cat (not part of the state)
         self.fused_time_encode = FUSED_TIME_ENCODE_DEFAULT
+        # True: dropout, relu and layer_norm after w_out as one ops.dropout_relu_layer_norm call
+        # (not part of the state)
+        self.fused_epilogue = FUSED_EPILOGUE_DEFAULT
 
     def forward(self, b):
         E, R, dev = b.num_edges(), b.num_dst_nodes(), b.device
@@ -380,7 +406,18 @@ class TemporalAttentionLayer(nn.Module):
             agg = ops.block_reduce(b, torch.cat([torch.zeros((R, msg.shape[1]), device=dev), msg]))
         agg = agg.reshape(R, -1)
         rst = torch.cat([agg, h_dst.to(agg.dtype)], dim=1) if self.use_node_feat else agg
-        return self.layer_norm(F.relu(self.dropout(self.w_out(rst))))
+        z = self.w_out(rst)
+        ln, p = self.layer_norm, self.dropout.p
+        if self.fused_epilogue and z.is_cuda and z.dtype in (torch.float32, torch.bfloat16) and \
+                self.dim_out <= ops.LAYER_EPILOGUE_MAX_WIDTH and ln.weight is not None and \
+                ln.bias is not None and ln.weight.dtype == torch.float32 and \
+                (0 <= p < 1 or not self.training):
+            if p == 0 or not self.training:
+                return ops.dropout_relu_layer_norm(z, ln.weight, ln.bias, ln.eps)
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64))
+            return ops.dropout_relu_layer_norm(z, ln.weight, ln.bias, ln.eps, dropout_p=p,
+                                               dropout_seed=seed)
+        return ln(F.relu(self.dropout(z)))
 
 
 TransfomerAttentionLayer = TemporalAttentionLayer      # the reference's own spelling

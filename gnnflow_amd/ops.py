@@ -15,13 +15,17 @@ make on a sampled block, on HIP segment kernels (csrc/block_ops.hip) with autogr
     edge_score(src, dst, w, b)             out_fc(relu(src + dst)) of EdgePredictor (layers.py:195-197),
                                            every dst block against the one src block, in one launch
                                            (csrc/edge_score.hip)
+    dropout_relu_layer_norm(x, w, b)       layer_norm(relu(dropout(x))), the last line of
+                                           TemporalAttentionLayer.forward after w_out, in one launch
+                                           with the Philox mask of block_attention, redrawn in the
+                                           backward (csrc/layer_epilogue.hip)
     link_metrics(pos, neg)                 average_precision_score / roc_auc_score of the reference's
                                            evaluate() (scripts/offline_edge_prediction.py:141-146) and
                                            the MRR, counted on the GPU without a sort, a sync or a copy
                                            to the host (csrc/link_metrics.hip)
 
-block_attention, block_reduce, block_max, block_gat, time_encode_cat and edge_score also run on
-bfloat16 (the tensors autocast hands them), by one rule: float32 arithmetic, one rounding on
+block_attention, block_reduce, block_max, block_gat, time_encode_cat, edge_score and
+dropout_relu_layer_norm also run on bfloat16 (the tensors autocast hands them), by one rule: float32 arithmetic, one rounding on
 store.  Every bfloat16 element is widened to float32 where it is loaded (exact), the arithmetic is
 the float32 kernels' own in the same order, and each bfloat16 result is rounded once, to nearest
 even.  So op(x.bfloat16()) == op(x.bfloat16().float()).to(torch.bfloat16) bit for bit, forward and
@@ -806,6 +810,129 @@ def edge_score(src: torch.Tensor, dst: torch.Tensor, weight: torch.Tensor, bias:
         raise ValueError("edge_score runs on the GPU, the inputs are on {}".format(dst.device))
     return _EdgeScore.apply(src.contiguous(), dst.contiguous(), weight.reshape(D).contiguous(),
                             bias.contiguous())
+
+
+LAYER_EPILOGUE_MAX_WIDTH = 1024      # GF_LAYER_EPILOGUE_MAX_WIDTH: the limit on D
+
+
+class _DropoutReluLayerNorm(torch.autograd.Function):
+    @staticmethod
+    @_fwd
+    def forward(ctx, x, weight, bias, eps, p32, seed):
+        # x [R, D] contiguous, fp32 or bf16; weight, bias [D] fp32 contiguous; out fp32
+        R, D = x.shape
+        f32 = dict(dtype=torch.float32, device=x.device)
+        out = torch.empty((R, D), **f32)
+        mean, rstd = torch.empty(R, **f32), torch.empty(R, **f32)
+        if R:
+            lib = _capi.load()
+            fn = lib.gf_layer_epilogue_bf16 if x.dtype == torch.bfloat16 else lib.gf_layer_epilogue
+            with torch.cuda.device(x.device):
+                _capi.check(fn(
+                    x.data_ptr(), weight.data_ptr(), bias.data_ptr(), R, D, eps, p32, seed,
+                    out.data_ptr(), mean.data_ptr(), rstd.data_ptr(), x.device.index,
+                    _stream(x.device)))
+        ctx.save_for_backward(x, weight, mean, rstd)      # neither out nor a mask
+        ctx.p32, ctx.seed = p32, seed
+        return out
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, grad):
+        x, weight, mean, rstd = ctx.saved_tensors
+        R, D = x.shape
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        if R == 0:      # zeros, and nothing to launch
+            return (torch.zeros_like(x) if need_x else None,
+                    torch.zeros_like(weight) if need_w else None,
+                    torch.zeros_like(weight) if need_b else None, None, None, None)
+        if not (need_x or need_w or need_b):
+            return None, None, None, None, None, None
+        g = _grad_as(grad, torch.float32)
+        gx = torch.empty_like(x) if need_x else None
+        gw = torch.empty_like(weight) if need_w else None
+        gb = torch.empty_like(weight) if need_b else None
+        lib = _capi.load()
+        partials, rows = None, C.c_size_t(0)
+        if need_w or need_b:
+            _capi.check(lib.gf_layer_epilogue_backward_partial_rows(R, C.byref(rows)))
+            partials = torch.empty((rows.value, 2 * D), dtype=torch.float32, device=x.device)
+        fn = lib.gf_layer_epilogue_backward_bf16 if x.dtype == torch.bfloat16 \
+            else lib.gf_layer_epilogue_backward
+        with torch.cuda.device(x.device):
+            _capi.check(fn(
+                x.data_ptr(), weight.data_ptr(), mean.data_ptr(), rstd.data_ptr(), R, D, ctx.p32,
+                ctx.seed, g.data_ptr(), _ptr(partials), rows.value, _ptr(gx), _ptr(gw), _ptr(gb),
+                x.device.index, _stream(x.device)))
+        return gx, gw, gb, None, None, None
+
+
+def dropout_relu_layer_norm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
+                            eps: float = 1e-5, dropout_p: float = 0.0, dropout_seed: int = 0):
+    """layer_norm(relu(dropout(x)), (D,), weight, bias, eps) over the rows of x [R, D]: the last
+    line of the reference's TemporalAttentionLayer after w_out, in one kernel each way
+    (csrc/layer_epilogue.hip).  Returns float32 [R, D].
+
+    x: [R, D], float32 or bfloat16 (what w_out returns under autocast), D <=
+    LAYER_EPILOGUE_MAX_WIDTH; weight, bias: float32 [D]; all on one GPU (a non-contiguous x is
+    copied first).  Any other dtype raises TypeError.  With p = float32(dropout_p), 0 <= p < 1:
+
+        T          = uint32(float64(p) * 2**32)
+        keep[r, d] = gf_philox4x32_10_first(dropout_seed, r * D + d, 0) >= T      (gnnflow_rng.h)
+        y          = relu(keep ? x * fl32(1 / (1 - p)) : 0)
+        out        = (y - mean) * rstd * weight + bias      mean, var over the row, rstd = 1 / sqrt(var + eps)
+
+    dropout_p == 0 keeps everything and ignores dropout_seed (0 <= seed < 2**64).  The mask is not
+    stored: the backward draws it again from the seed, and saves x, weight and the rows' mean and
+    rstd, neither the output nor a mask.  tests/attention_dropout_ref.py restates the generator in
+    numpy.  Differentiable in x, weight and bias; a gradient that is not asked for is None and is
+    not computed, and the gradients of weight and bias are summed in a fixed order: bit-identical
+    from run to run.
+
+    The module's rule for bfloat16 applies -- float32 arithmetic, one rounding on store --: the
+    output and the gradients of weight and bias equal, bit for bit, the float32 op's on
+    x.float(); the gradient of x is bfloat16, its float32 gradient rounded once."""
+    for name, t in (("x", x), ("weight", weight), ("bias", bias)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("{} must be a tensor, got {}".format(name, type(t).__name__))
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("dropout_relu_layer_norm computes in float32 and takes x float32 or "
+                        "bfloat16, x is {}".format(x.dtype))
+    for name, t in (("weight", weight), ("bias", bias)):
+        if t.dtype != torch.float32:
+            raise TypeError("dropout_relu_layer_norm computes in float32, {} is {}".format(
+                name, t.dtype))
+    if x.dim() != 2:
+        raise ValueError("x must be [R, D], got {}".format(tuple(x.shape)))
+    D = int(x.shape[1])
+    if D == 0:
+        raise ValueError("dropout_relu_layer_norm needs D >= 1")
+    if D > LAYER_EPILOGUE_MAX_WIDTH:
+        raise ValueError("D = {} exceeds LAYER_EPILOGUE_MAX_WIDTH ({})".format(
+            D, LAYER_EPILOGUE_MAX_WIDTH))
+    for name, t in (("weight", weight), ("bias", bias)):
+        if tuple(t.shape) != (D,):
+            raise ValueError("{} must be [D] with D = {}, got {}".format(name, D, tuple(t.shape)))
+    eps = float(eps)
+    if not eps > 0.0 or not C.c_float(eps).value > 0.0:      # NaN fails too
+        raise ValueError("eps must be > 0 in float32, got {}".format(eps))
+    dropout_p = float(dropout_p)
+    if not 0.0 <= dropout_p < 1.0:          # NaN fails too
+        raise ValueError("dropout_p must be in [0, 1), got {}".format(dropout_p))
+    p32 = C.c_float(dropout_p).value        # the fp32 value the kernels see
+    if not p32 < 1.0:
+        raise ValueError("dropout_p rounds to 1 in float32")
+    dropout_seed = int(dropout_seed)
+    if not 0 <= dropout_seed < 2 ** 64:
+        raise ValueError("dropout_seed must be in [0, 2**64), got {}".format(dropout_seed))
+    for name, t in (("weight", weight), ("bias", bias)):
+        if t.device != x.device:
+            raise ValueError("{} is on {}, x on {}".format(name, t.device, x.device))
+    if x.device.type != "cuda":
+        raise ValueError("dropout_relu_layer_norm runs on the GPU, the inputs are on {}".format(
+            x.device))
+    return _DropoutReluLayerNorm.apply(x.contiguous(), weight.contiguous(), bias.contiguous(),
+                                       eps, p32, dropout_seed if p32 > 0 else 0)
 
 
 LINK_METRICS_MAX_SCORES = 65536      # GF_LINK_METRICS_MAX_SCORES: the limit on P + N

@@ -1031,6 +1031,63 @@ GF_API int gf_edge_score_backward_bf16(const uint16_t* d_src, const uint16_t* d_
                                        uint16_t* d_grad_dst, float* d_grad_w, float* d_grad_bias,
                                        int device, void* stream);
 
+/* Fused epilogue of the reference's TemporalAttentionLayer (layers.py: layer_norm(relu(dropout(
+ * w_out(rst)))), after the GEMM): d_x [num_rows, dim], d_gamma and d_beta [dim], d_out
+ * [num_rows, dim], d_mean and d_rstd [num_rows], all fp32, row-major and contiguous.  With p an
+ * fp32 value in [0, 1), T = (uint32_t)((double)p * 4294967296.0) and sc = 1.0f / (1.0f - p):
+ *   keep[r,d] = gf_philox4x32_10_first(seed, r * dim + d, 0) >= T        (gnnflow_rng.h)
+ *   y[r,d]    = max(keep ? x[r,d] * sc : 0, 0)            p == 0: y = max(x, 0), seed unused
+ *   mean[r]   = sum_d y / dim      var[r] = sum_d (y - mean)^2 / dim
+ *   rstd[r]   = 1 / sqrtf(var + eps)
+ *   out[r,d]  = (y - mean) * rstd * gamma[d] + beta[d]
+ * in one launch: one wave per row, the row read once, the variance taken from the deviations.  No
+ * mask is written; d_mean and d_rstd are what the backward needs besides x.  The bits depend on
+ * dim alone, not on num_rows, the grid or the alignment of the pointers.  dim == 0, dim >
+ * GF_LAYER_EPILOGUE_MAX_WIDTH, p outside [0, 1) or NaN, eps not > 0, 2^31 rows or more, or a NULL
+ * pointer when num_rows > 0: GF_ERR_INVALID_ARGUMENT; num_rows == 0 launches nothing. */
+#define GF_LAYER_EPILOGUE_MAX_WIDTH 1024
+GF_API int gf_layer_epilogue(const float* d_x, const float* d_gamma, const float* d_beta,
+                             size_t num_rows, size_t dim, float eps, float p, uint64_t seed,
+                             float* d_out, float* d_mean, float* d_rstd, int device,
+                             void* stream);
+/* Rows of the caller-owned partials buffer gf_layer_epilogue_backward needs for num_rows rows (at
+ * most 1024 whatever num_rows is): the buffer holds rows * 2 * dim floats. */
+GF_API int gf_layer_epilogue_backward_partial_rows(size_t num_rows, size_t* rows);
+/* Gradients of gf_layer_epilogue from d_grad_out [num_rows, dim], with y and keep recomputed from
+ * x, p and seed, and d_mean / d_rstd as the forward wrote them:
+ *   xhat = (y - mean) * rstd          g = grad_out * gamma
+ *   dy   = rstd * (g - sum_d(g) / dim - xhat * (sum_d(g * xhat) / dim))
+ *   grad_x[r,d]   = (keep && x[r,d] * sc > 0) ? dy * sc : 0
+ *   grad_gamma[d] = sum_r grad_out * xhat          grad_beta[d] = sum_r grad_out
+ * in at most two launches, summed in a fixed order without atomics (bit-identical from run to
+ * run).  Any of d_grad_x, d_grad_gamma, d_grad_beta may be NULL (skipped); d_partials is needed,
+ * with at least the rows gf_layer_epilogue_backward_partial_rows gives, only when d_grad_gamma or
+ * d_grad_beta is not NULL, and without them there is one launch.  num_rows == 0 zeroes the
+ * parameter gradients given and launches nothing.  The checks of gf_layer_epilogue otherwise. */
+GF_API int gf_layer_epilogue_backward(const float* d_x, const float* d_gamma,
+                                      const float* d_mean, const float* d_rstd, size_t num_rows,
+                                      size_t dim, float p, uint64_t seed,
+                                      const float* d_grad_out, float* d_partials,
+                                      size_t partial_rows, float* d_grad_x, float* d_grad_gamma,
+                                      float* d_grad_beta, int device, void* stream);
+/* gf_layer_epilogue and gf_layer_epilogue_backward for a bfloat16 d_x (uint16_t as above) and a
+ * bfloat16 d_grad_x; d_gamma, d_beta, d_out, d_mean, d_rstd, d_grad_out, the partials, d_grad_gamma
+ * and d_grad_beta stay float32.  Rows are widened on load, the arithmetic and its order are the
+ * float32 entry points', and grad_x is rounded once to nearest even on store: every output equals
+ * the float32 entry point's on the widened rows (grad_x: rounded to bfloat16), bit for bit.  The
+ * same checks. */
+GF_API int gf_layer_epilogue_bf16(const uint16_t* d_x, const float* d_gamma, const float* d_beta,
+                                  size_t num_rows, size_t dim, float eps, float p, uint64_t seed,
+                                  float* d_out, float* d_mean, float* d_rstd, int device,
+                                  void* stream);
+GF_API int gf_layer_epilogue_backward_bf16(const uint16_t* d_x, const float* d_gamma,
+                                           const float* d_mean, const float* d_rstd,
+                                           size_t num_rows, size_t dim, float p, uint64_t seed,
+                                           const float* d_grad_out, float* d_partials,
+                                           size_t partial_rows, uint16_t* d_grad_x,
+                                           float* d_grad_gamma, float* d_grad_beta, int device,
+                                           void* stream);
+
 /* Link-prediction metrics of one validation batch from the scores d_pos [num_pos] of its true
  * edges and d_neg [num_neg] of its negative ones (float32, compared as IEEE compares them, so
  * -0 == +0): d_out[3] = {AP, AUC, MRR} as float64, what scikit-learn's average_precision_score
