@@ -20,6 +20,8 @@ default run keeps the composed edge_softmax -> block_reduce chain of the recorde
 --amp runs the memory updater, the model and the loss under torch.autocast('cuda',
 dtype=torch.bfloat16) and implies --fused-attention: the composed chain is float32 only, while
 ops.block_attention takes the bfloat16 q, k, v of the Linear layers as they come.
+--fused-loss takes gnnflow_amd.nn.LinkLoss as the criterion (one ops.link_loss launch each way)
+and reports the epoch's mean loss from its device-side sums, read once after the epoch.
 """
 import argparse
 from collections import deque
@@ -167,8 +169,11 @@ def main():
     ap.add_argument("--amp", action="store_true",
                     help="bfloat16 autocast around updater, model and loss (implies "
                          "--fused-attention)")
+    ap.add_argument("--fused-loss", action="store_true",
+                    help="nn.LinkLoss as the criterion; the epoch's mean loss from its sums")
     args = ap.parse_args()
     fused = args.fused_attention or args.amp
+    criterion = gnnflow_amd.nn.LinkLoss() if args.fused_loss else None
     amp = torch.autocast("cuda", dtype=torch.bfloat16, enabled=args.amp)
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
@@ -214,6 +219,8 @@ def main():
     for epoch in range(args.epochs):
         memory.reset()
         cache.init_cache()
+        if criterion is not None:
+            criterion.reset()
         T = dict(sample=0.0, fetch=0.0, mem_gather=0.0, mem_update=0.0, model=0.0, write_back=0.0)
         edges = 0
         torch.cuda.synchronize()
@@ -248,8 +255,11 @@ def main():
                 memory.update_mem_mail(**last, edge_feats=None, neg_sample_ratio=1)
             t6 = time.perf_counter()
             with amp:
-                loss = F.binary_cross_entropy_with_logits(pos, torch.ones_like(pos)) + \
-                    F.binary_cross_entropy_with_logits(neg, torch.zeros_like(neg))
+                if criterion is not None:
+                    loss = criterion(pos, neg)
+                else:
+                    loss = F.binary_cross_entropy_with_logits(pos, torch.ones_like(pos)) + \
+                        F.binary_cross_entropy_with_logits(neg, torch.zeros_like(neg))
             loss.backward()
             opt.step()
             t7 = time.perf_counter()
@@ -262,8 +272,13 @@ def main():
             edges += b.num_edges()
         torch.cuda.synchronize()
         total = time.perf_counter() - e0
+        if criterion is not None:
+            sums = criterion.compute()
+            print("epoch {}: mean loss {:.4f} over {} batches ({} non-finite)".format(
+                epoch, sums["mean_loss"], sums["batches"], sums["nonfinite"]), file=sys.stderr)
         out.append(dict(epoch=epoch, seconds=total, batches=nb, ms_per_batch=1e3 * total / nb,
                         sampled_edges=edges, loss=float(loss.detach()),
+                        **({"mean_loss": sums["mean_loss"]} if criterion is not None else {}),
                         node_cache_hit_ratio=float(cache.cache_node_ratio),
                         host_seconds_by_stage={k: round(v, 3) for k, v in T.items()}))
     print(json.dumps({
@@ -279,7 +294,8 @@ def main():
                   "next waits — mostly in `model`, whose loss read-back synchronises)",
         "graph_build_s": round(build_s, 2), "epochs": out,
         **({"att_dropout": args.att_dropout} if args.att_dropout else {}),
-        **({"fused_attention": True} if fused else {}), **({"amp": "bfloat16"} if args.amp else {})}))
+        **({"fused_attention": True} if fused else {}),
+        **({"fused_loss": True} if args.fused_loss else {}), **({"amp": "bfloat16"} if args.amp else {})}))
 
 
 if __name__ == "__main__":

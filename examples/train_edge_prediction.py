@@ -5,10 +5,15 @@ of the reference's static models, the 2-layer `gnnflow_amd.models.SAGE` (GraphSA
 `gnnflow_amd.models.GAT`.  Synthetic REDDIT-shaped data; a usage example, not a benchmark.
 
     python examples/train_edge_prediction.py [--batches 50] [--model {sage,gat}] [--amp]
+                                             [--fused-loss]
 
 --amp runs the forward and the loss under torch.autocast('cuda', dtype=torch.bfloat16).  No
 GradScaler: bfloat16 has float32's range.  The models need no cast for it: the block ops take
 the bfloat16 rows autocast produces (as models.DGNN does, examples/tgn_epoch.py --amp).
+
+--fused-loss takes gnnflow_amd.nn.LinkLoss as the criterion: one ops.link_loss launch each way
+instead of torch's two BCE-with-logits expressions, the epoch's sums kept on the device, and no
+float(loss) per batch -- the losses are read once, after the loop.
 """
 import argparse
 import os
@@ -37,7 +42,8 @@ def build_model(name, dim_in, dim_hidden):
     raise ValueError("model must be 'sage' or 'gat', got {!r}".format(name))
 
 
-def main(num_batches=50, batch_size=600, seed=0, verbose=True, amp=False, model='sage'):
+def main(num_batches=50, batch_size=600, seed=0, verbose=True, amp=False, model='sage',
+         fused_loss=False):
     import pandas as pd
     torch.manual_seed(seed)
     dev = torch.device("cuda", 0)
@@ -56,7 +62,8 @@ def main(num_batches=50, batch_size=600, seed=0, verbose=True, amp=False, model=
                         collate_fn=default_collate_ndarray, num_workers=0)
     model = build_model(model, d, 64).to(dev)
     opt = torch.optim.Adam(model.parameters(), lr=1e-3)
-    losses = []
+    criterion = gnnflow_amd.nn.LinkLoss() if fused_loss else None
+    losses = []      # floats; with fused_loss detached device scalars, read once after the loop
     for i, (roots, ts, eid) in enumerate(loader):
         if i >= num_batches:
             break
@@ -64,15 +71,28 @@ def main(num_batches=50, batch_size=600, seed=0, verbose=True, amp=False, model=
         cache.fetch_feature(mfgs, eid)
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
             pos, neg = model(mfgs)
-            loss = F.binary_cross_entropy_with_logits(pos, torch.ones_like(pos)) + \
-                F.binary_cross_entropy_with_logits(neg, torch.zeros_like(neg))
+            if fused_loss:
+                loss = criterion(pos, neg)
+            else:
+                loss = F.binary_cross_entropy_with_logits(pos, torch.ones_like(pos)) + \
+                    F.binary_cross_entropy_with_logits(neg, torch.zeros_like(neg))
         opt.zero_grad()
         loss.backward()
         opt.step()
+        if fused_loss:
+            losses.append(loss.detach())      # no sync
+            continue
         losses.append(float(loss.detach()))
         if verbose and i % 10 == 0:
             print("batch {:4d} loss {:.4f} node-cache hit ratio {:.3f}".format(
                 i, losses[-1], float(cache.cache_node_ratio)))
+    if fused_loss and losses:
+        epoch = criterion.compute()      # the loop's one sync for the loss
+        losses = torch.stack(losses).tolist()
+        if verbose:
+            print("{} batches: mean loss {:.4f}, edge-weighted {:.4f}, {} non-finite".format(
+                epoch["batches"], epoch["mean_loss"], epoch["edge_weighted_loss"],
+                epoch["nonfinite"]))
     return losses
 
 
@@ -81,5 +101,7 @@ if __name__ == "__main__":
     ap.add_argument("--batches", type=int, default=50)
     ap.add_argument("--amp", action="store_true", help="bfloat16 autocast around forward and loss")
     ap.add_argument("--model", choices=["sage", "gat"], default="sage")
+    ap.add_argument("--fused-loss", action="store_true",
+                    help="nn.LinkLoss as the criterion, the losses read once after the loop")
     args = ap.parse_args()
-    main(args.batches, amp=args.amp, model=args.model)
+    main(args.batches, amp=args.amp, model=args.model, fused_loss=args.fused_loss)

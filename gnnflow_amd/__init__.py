@@ -7,10 +7,10 @@ kernels (gfx950) behind the C ABI of include/gnnflow_hip.h.
 from .dynamic_graph import DynamicGraph
 from .metrics import LinkMetrics
 from .mfg import MFGBlock
-from .nn import (MLP, EdgePredictor, GATConv, GRUMemeoryUpdater, GRUMemoryUpdater, SAGEConv,
-                 TemporalAttentionLayer, TimeEncode, TransfomerAttentionLayer)
+from .nn import (MLP, EdgePredictor, GATConv, GRUMemeoryUpdater, GRUMemoryUpdater, LinkLoss,
+                 SAGEConv, TemporalAttentionLayer, TimeEncode, TransfomerAttentionLayer)
 from .temporal_sampler import SamplingResult, TemporalSampler
 
 __all__ = ["DynamicGraph", "TemporalSampler", "SamplingResult", "MFGBlock", "SAGEConv", "GATConv",
            "TimeEncode", "TemporalAttentionLayer", "TransfomerAttentionLayer", "GRUMemoryUpdater",
-           "GRUMemeoryUpdater", "EdgePredictor", "MLP", "LinkMetrics"]
+           "GRUMemeoryUpdater", "EdgePredictor", "MLP", "LinkMetrics", "LinkLoss"]

@@ -314,6 +314,11 @@ PROTOTYPES = {
                                                   _p, _p, _sz, _p, _p, _p, C.c_int, _p]),
     "gf_link_metrics_partial_rows": (C.c_int, [_sz, C.POINTER(_sz)]),
     "gf_link_metrics": (C.c_int, [_p, _p, _sz, _sz, _p, _sz, _p, _p, C.c_int, _p]),
+    "gf_link_loss_partial_rows": (C.c_int, [_sz, _sz, C.POINTER(_sz)]),
+    "gf_link_loss": (C.c_int, [_p, _p, _sz, _sz, _p, _sz, _p, _p, C.c_int, _p]),
+    "gf_link_loss_bf16": (C.c_int, [_p, _p, _sz, _sz, _p, _sz, _p, _p, C.c_int, _p]),
+    "gf_link_loss_backward": (C.c_int, [_p, _p, _sz, _sz, _p, _p, _p, C.c_int, _p]),
+    "gf_link_loss_backward_bf16": (C.c_int, [_p, _p, _sz, _sz, _p, _p, _p, C.c_int, _p]),
     "gf_debug_part_host_us": (C.c_int, [C.POINTER(C.c_double), C.c_int]),
     "gf_debug_merge_recounts": (C.c_int, [C.POINTER(C.c_uint64)]),
     "gf_debug_part_reused_roots": (C.c_int, [C.POINTER(C.c_uint64)]),

@@ -251,4 +251,34 @@ void link_metrics(const float* d_pos, const float* d_neg, size_t num_pos, size_t
                   void* d_partials, size_t partial_rows, double* d_out, double* d_acc, int device,
                   hipStream_t stream);
 
+// link_loss.hip: out[1] (float32) = mean softplus(-pos) + mean softplus(neg), the reference's
+// BCEWithLogitsLoss of the positive logits against 1 plus that of the negative ones against 0,
+// float32 terms summed in float64 in a fixed order, in one launch up to kLinkLossSingleTiles
+// tiles of kLinkLossTile logits in all and in two beyond; no atomics.  d_acc, unless null, is
+// the running sum of a training epoch: {sum_loss, sum_loss_times_num_pos, batches, nonfinite,
+// sum_num_pos}; a loss that is not finite adds 1 to nonfinite alone.  d_partials:
+// link_loss_partial_rows(num_pos, num_neg) float64 words, caller-owned (0 rows: may be null).
+// The backward writes grad_pos [num_pos] and grad_neg [num_neg] (a null one is skipped) times
+// the scalar d_grad_out[0] in one launch.  num_pos, num_neg >= 1 and < 2^31, else
+// GF_ERR_INVALID_ARGUMENT.
+constexpr size_t kLinkLossTile = 1024;      // logits per workgroup pass
+constexpr size_t kLinkLossSingleTiles = 8;
+constexpr size_t kLinkLossMaxPartialRows = 256;
+constexpr size_t kLinkLossAccFields = 5;
+size_t link_loss_partial_rows(size_t num_pos, size_t num_neg);
+void link_loss_forward(const float* d_pos, const float* d_neg, size_t num_pos, size_t num_neg,
+                       double* d_partials, size_t partial_rows, float* d_out, double* d_acc,
+                       int device, hipStream_t stream);
+void link_loss_backward(const float* d_pos, const float* d_neg, size_t num_pos, size_t num_neg,
+                        const float* d_grad_out, float* d_grad_pos, float* d_grad_neg, int device,
+                        hipStream_t stream);
+// The same with bfloat16 logits (widened on load) and bfloat16 gradients (rounded once on store);
+// the loss, the partials and the accumulator are as above.
+void link_loss_bf16_forward(const uint16_t* d_pos, const uint16_t* d_neg, size_t num_pos,
+                            size_t num_neg, double* d_partials, size_t partial_rows, float* d_out,
+                            double* d_acc, int device, hipStream_t stream);
+void link_loss_bf16_backward(const uint16_t* d_pos, const uint16_t* d_neg, size_t num_pos,
+                             size_t num_neg, const float* d_grad_out, uint16_t* d_grad_pos,
+                             uint16_t* d_grad_neg, int device, hipStream_t stream);
+
 }  // namespace gf

@@ -422,6 +422,50 @@ int gf_link_metrics(const float* d_pos, const float* d_neg, size_t num_pos, size
   });
 }
 
+static_assert(GF_LINK_LOSS_TILE == gf::kLinkLossTile &&
+                  GF_LINK_LOSS_SINGLE_TILES == gf::kLinkLossSingleTiles &&
+                  GF_LINK_LOSS_MAX_PARTIAL_ROWS == gf::kLinkLossMaxPartialRows &&
+                  GF_LINK_LOSS_ACC_FIELDS == gf::kLinkLossAccFields,
+              "gnnflow_hip.h and block_ops.hpp disagree on the link-loss constants");
+int gf_link_loss_partial_rows(size_t num_pos, size_t num_neg, size_t* rows) {
+  return guarded([&] {
+    GF_REQUIRE(rows != nullptr, "gf_link_loss_partial_rows: null output");
+    *rows = gf::link_loss_partial_rows(num_pos, num_neg);
+  });
+}
+int gf_link_loss(const float* d_pos, const float* d_neg, size_t num_pos, size_t num_neg,
+                 double* d_partials, size_t partial_rows, float* d_out, double* d_acc, int device,
+                 void* stream) {
+  return guarded([&] {
+    gf::link_loss_forward(d_pos, d_neg, num_pos, num_neg, d_partials, partial_rows, d_out, d_acc,
+                          device, as_stream(stream));
+  });
+}
+int gf_link_loss_backward(const float* d_pos, const float* d_neg, size_t num_pos, size_t num_neg,
+                          const float* d_grad_out, float* d_grad_pos, float* d_grad_neg,
+                          int device, void* stream) {
+  return guarded([&] {
+    gf::link_loss_backward(d_pos, d_neg, num_pos, num_neg, d_grad_out, d_grad_pos, d_grad_neg,
+                           device, as_stream(stream));
+  });
+}
+int gf_link_loss_bf16(const uint16_t* d_pos, const uint16_t* d_neg, size_t num_pos,
+                      size_t num_neg, double* d_partials, size_t partial_rows, float* d_out,
+                      double* d_acc, int device, void* stream) {
+  return guarded([&] {
+    gf::link_loss_bf16_forward(d_pos, d_neg, num_pos, num_neg, d_partials, partial_rows, d_out,
+                               d_acc, device, as_stream(stream));
+  });
+}
+int gf_link_loss_backward_bf16(const uint16_t* d_pos, const uint16_t* d_neg, size_t num_pos,
+                               size_t num_neg, const float* d_grad_out, uint16_t* d_grad_pos,
+                               uint16_t* d_grad_neg, int device, void* stream) {
+  return guarded([&] {
+    gf::link_loss_bf16_backward(d_pos, d_neg, num_pos, num_neg, d_grad_out, d_grad_pos,
+                                d_grad_neg, device, as_stream(stream));
+  });
+}
+
 int gf_debug_philox(const uint64_t* d_in, size_t n, uint32_t* d_out, void* stream) {
   return guarded([&] {
     GF_REQUIRE(n == 0 || (d_in != nullptr && d_out != nullptr), "gf_debug_philox: null buffer");

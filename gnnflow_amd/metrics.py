@@ -15,6 +15,7 @@ kept on the device, one synchronisation per pass in compute().
 import torch
 
 from . import ops
+from .nn import LinkLoss  # noqa: F401  (the training loss kept the same way: nn.LinkLoss)
 
 _FIELDS = ("sum_ap", "sum_auc", "sum_mrr", "batches", "mrr_batches", "nonfinite")
 

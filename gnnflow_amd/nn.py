@@ -14,7 +14,7 @@ GRUMemoryUpdater is TGN's memory updater (gnnflow/models/modules/memory_updater.
 spelled GRUMemeoryUpdater), the consumer of gnnflow_amd.memory.Memory.prepare_input.
 
 EdgePredictor / MLP are the reference's heads (layers.py:171-214); EdgePredictor's tail can run as
-one ops.edge_score call."""
+one ops.edge_score call.  LinkLoss is the training criterion that follows them, on ops.link_loss."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -518,6 +518,61 @@ class EdgePredictor(nn.Module):
         pos_edge = F.relu(src_h + self.dst_fc(h[B:2 * B]))
         neg_edge = F.relu(src_h + self.dst_fc(h[2 * B:]))
         return self.out_fc(pos_edge), self.out_fc(neg_edge)
+
+
+class LinkLoss(nn.Module):
+    """The reference's training criterion for link prediction,
+
+        criterion(pred_pos, ones_like(pred_pos)) + criterion(pred_neg, zeros_like(pred_neg))
+
+    with BCEWithLogitsLoss, as one ops.link_loss call that also keeps the epoch's running sums
+    on the device, so that a training epoch reads its loss with one synchronisation:
+
+        criterion = LinkLoss()
+        for ...:                                   # the training batches
+            loss = criterion(pred_pos, pred_neg)   # float32 scalar, no sync
+            loss.backward()
+        result = criterion.compute()               # {'mean_loss', ...}, one sync
+
+    The accumulator is a float64 [5] buffer (sum_loss, sum_loss_times_P, batches, nonfinite,
+    sum_P; P the number of positives of a batch), created on the device of the first GPU inputs.
+    It is not persistent: state_dict() does not hold it.
+
+    Inputs that are not float32 or bfloat16 on the GPU (CPU tensors, float64, float16) take the
+    torch expression, F.binary_cross_entropy_with_logits twice, and are NOT accumulated."""
+
+    _FIELDS = ("sum_loss", "sum_loss_times_P", "batches", "nonfinite", "sum_P")
+
+    def __init__(self):
+        super().__init__()
+        self.register_buffer("state", None, persistent=False)
+
+    def forward(self, pred_pos: torch.Tensor, pred_neg: torch.Tensor) -> torch.Tensor:
+        if not (pred_pos.is_cuda and pred_neg.is_cuda and pred_pos.dtype == pred_neg.dtype and
+                pred_pos.dtype in (torch.float32, torch.bfloat16)):
+            return F.binary_cross_entropy_with_logits(pred_pos, torch.ones_like(pred_pos)) + \
+                F.binary_cross_entropy_with_logits(pred_neg, torch.zeros_like(pred_neg))
+        if self.state is None or self.state.device != pred_pos.device:
+            self.state = torch.zeros(ops.LINK_LOSS_ACC_FIELDS, dtype=torch.float64,
+                                     device=pred_pos.device)
+        return ops.link_loss(pred_pos, pred_neg, accumulator=self.state)
+
+    def compute(self) -> dict:
+        """The epoch so far (one device-to-host copy, which waits for the batches issued):
+        'mean_loss' = sum_loss / batches, what the mean of float(loss) over the batches gives;
+        'edge_weighted_loss' = sum_loss_times_P / sum_P, each batch weighted by its positives;
+        NaN where the count is 0; 'batches'; 'nonfinite' counts the batches left out because
+        their loss was NaN or infinite."""
+        s = dict(zip(self._FIELDS, self.state.tolist() if self.state is not None else [0.0] * 5))
+        nan = float("nan")
+        b = int(s["batches"])
+        return {"mean_loss": s["sum_loss"] / b if b else nan,
+                "edge_weighted_loss": s["sum_loss_times_P"] / s["sum_P"] if s["sum_P"] else nan,
+                "batches": b, "nonfinite": int(s["nonfinite"])}
+
+    def reset(self) -> None:
+        if self.state is not None:
+            self.state.zero_()
 
 
 class MLP(nn.Module):

@@ -23,8 +23,12 @@ make on a sampled block, on HIP segment kernels (csrc/block_ops.hip) with autogr
                                            evaluate() (scripts/offline_edge_prediction.py:141-146) and
                                            the MRR, counted on the GPU without a sort, a sync or a copy
                                            to the host (csrc/link_metrics.hip)
+    link_loss(pos, neg)                    criterion(pred_pos, ones) + criterion(pred_neg, zeros) of the
+                                           reference's training step (BCEWithLogitsLoss), one launch
+                                           each way, with a running epoch sum on the device
+                                           (csrc/link_loss.hip)
 
-block_attention, block_reduce, block_max, block_gat, time_encode_cat, edge_score and
+block_attention, block_reduce, block_max, block_gat, time_encode_cat, edge_score, link_loss and
 dropout_relu_layer_norm also run on bfloat16 (the tensors autocast hands them), by one rule: float32 arithmetic, one rounding on
 store.  Every bfloat16 element is widened to float32 where it is loaded (exact), the arithmetic is
 the float32 kernels' own in the same order, and each bfloat16 result is rounded once, to nearest
@@ -1008,6 +1012,111 @@ def link_metrics(pos: torch.Tensor, neg: torch.Tensor,
             p.data_ptr(), n.data_ptr(), P, N, partials.data_ptr(), rows.value, out.data_ptr(),
             _ptr(acc), p.device.index, _stream(p.device)))
     return out
+
+
+LINK_LOSS_TILE = 1024                # GF_LINK_LOSS_TILE: logits per workgroup pass of the kernel
+LINK_LOSS_SINGLE_TILES = 8           # GF_LINK_LOSS_SINGLE_TILES: up to here the forward is one launch
+LINK_LOSS_MAX_PARTIAL_ROWS = 256     # GF_LINK_LOSS_MAX_PARTIAL_ROWS: half of them for each side
+LINK_LOSS_ACC_FIELDS = 5             # GF_LINK_LOSS_ACC_FIELDS
+
+
+class _LinkLoss(torch.autograd.Function):
+    @staticmethod
+    @_fwd
+    def forward(ctx, pos, neg, acc):
+        # pos [P], neg [N] contiguous, both fp32 or both bf16; acc None or float64 [5]
+        P, N = pos.shape[0], neg.shape[0]
+        lib = _capi.load()
+        rows = C.c_size_t(0)
+        _capi.check(lib.gf_link_loss_partial_rows(P, N, C.byref(rows)))
+        partials = torch.empty(rows.value, dtype=torch.float64, device=pos.device) \
+            if rows.value else None
+        out = torch.empty((), dtype=torch.float32, device=pos.device)
+        fn = lib.gf_link_loss_bf16 if pos.dtype == torch.bfloat16 else lib.gf_link_loss
+        with torch.cuda.device(pos.device):
+            _capi.check(fn(pos.data_ptr(), neg.data_ptr(), P, N, _ptr(partials), rows.value,
+                           out.data_ptr(), _ptr(acc), pos.device.index, _stream(pos.device)))
+        ctx.save_for_backward(pos, neg)
+        return out
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, grad):
+        pos, neg = ctx.saved_tensors
+        need_pos, need_neg, _ = ctx.needs_input_grad
+        if not (need_pos or need_neg):
+            return None, None, None
+        g = _grad_as(grad, torch.float32)
+        gp = torch.empty_like(pos) if need_pos else None
+        gn = torch.empty_like(neg) if need_neg else None
+        lib = _capi.load()
+        fn = lib.gf_link_loss_backward_bf16 if pos.dtype == torch.bfloat16 \
+            else lib.gf_link_loss_backward
+        with torch.cuda.device(pos.device):
+            _capi.check(fn(pos.data_ptr(), neg.data_ptr(), pos.shape[0], neg.shape[0],
+                           g.data_ptr(), _ptr(gp), _ptr(gn), pos.device.index,
+                           _stream(pos.device)))
+        return gp, gn, None
+
+
+def link_loss(pos: torch.Tensor, neg: torch.Tensor,
+              accumulator: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mean(softplus(-pos)) + mean(softplus(neg)) as a float32 scalar tensor (shape []) on the
+    GPU: the reference's training loss, criterion(pred_pos, ones) + criterion(pred_neg, zeros)
+    with BCEWithLogitsLoss, in one launch (two beyond LINK_LOSS_SINGLE_TILES tiles of
+    LINK_LOSS_TILE logits in all) and one more for the backward.
+
+    pos: [P] or [P, 1], the logits of the true edges; neg: [N] or [N, 1], those of the negative
+    ones, as EdgePredictor returns them; N need not be a multiple of P.  Both float32 or both
+    bfloat16 on one GPU, P >= 1, N >= 1; any other dtype or a mixture raises TypeError.  Row
+    slices of one buffer (out[:B], out[B:] of edge_score) are taken as they are; a non-contiguous
+    input is copied.  Differentiable in pos and neg; only the logits are saved.
+
+    Every term is float32 arithmetic, the sums are float64 in a fixed order and the loss is
+    rounded to float32 once: the same inputs give the same bits.  bfloat16 logits follow the
+    module's rule: the loss is float32 and equals link_loss(pos.float(), neg.float()) bit for
+    bit, the gradients are bfloat16, the float32 gradients rounded once.
+
+    accumulator: a float64 contiguous [LINK_LOSS_ACC_FIELDS] = [5] tensor on the same GPU, the
+    running sums of an epoch (sum_loss, sum_loss_times_P, batches, nonfinite, sum_P), updated on
+    the device in the forward from the float32 loss; nn.LinkLoss wraps it.  A NaN logit gives a
+    NaN loss, infinities follow the formulas; a loss that is not finite adds 1 to `nonfinite`
+    alone.
+
+    Runs on the current stream and never synchronises."""
+    for name, x in (("pos", pos), ("neg", neg)):
+        if not isinstance(x, torch.Tensor):
+            raise TypeError("{} must be a tensor, got {}".format(name, type(x).__name__))
+    if (pos.dtype, neg.dtype) not in ((torch.float32,) * 2, (torch.bfloat16,) * 2):
+        raise TypeError("link_loss computes in float32 and takes pos and neg both float32 or both "
+                        "bfloat16, pos is {} and neg is {}".format(pos.dtype, neg.dtype))
+    for name, x in (("pos", pos), ("neg", neg)):
+        if not (x.dim() == 1 or (x.dim() == 2 and x.shape[1] == 1)):
+            raise ValueError("{} must be [n] or [n, 1], got {}".format(name, tuple(x.shape)))
+    P, N = int(pos.shape[0]), int(neg.shape[0])
+    if P == 0 or N == 0:
+        raise ValueError("link_loss needs at least one positive and one negative logit, got "
+                         "{} and {}".format(P, N))
+    if P >= 1 << 31 or N >= 1 << 31:
+        raise ValueError("link_loss takes fewer than 2^31 logits on a side, got {} and {}".format(
+            P, N))
+    acc = accumulator
+    if acc is not None:
+        if not isinstance(acc, torch.Tensor):
+            raise TypeError("accumulator must be a tensor, got {}".format(type(acc).__name__))
+        if acc.dtype != torch.float64:
+            raise TypeError("accumulator must be float64, got {}".format(acc.dtype))
+        if tuple(acc.shape) != (LINK_LOSS_ACC_FIELDS,) or not acc.is_contiguous():
+            raise ValueError("accumulator must be a contiguous [{}] tensor, got {}".format(
+                LINK_LOSS_ACC_FIELDS, tuple(acc.shape)))
+    if neg.device != pos.device:
+        raise ValueError("neg is on {}, pos on {}".format(neg.device, pos.device))
+    if acc is not None and acc.device != pos.device:
+        raise ValueError("accumulator is on {}, pos on {}".format(acc.device, pos.device))
+    if pos.device.type != "cuda":
+        raise ValueError("link_loss runs on the GPU, the inputs are on {}".format(pos.device))
+    return _LinkLoss.apply(pos.reshape(P).contiguous(), neg.reshape(N).contiguous(),
+                           None if acc is None else acc.detach())
 
 
 def _src_dtype(op, src):

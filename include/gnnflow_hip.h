@@ -1119,6 +1119,50 @@ GF_API int gf_link_metrics(const float* d_pos, const float* d_neg, size_t num_po
                            size_t num_neg, void* d_partials, size_t partial_rows, double* d_out,
                            double* d_acc, int device, void* stream);
 
+/* The loss of a link-prediction step from the logits d_pos [num_pos] of its true edges and
+ * d_neg [num_neg] of its negative ones: BCE-with-logits of d_pos against 1 plus that of d_neg
+ * against 0, each a mean, as one float32 d_out[1].  With t(x) = log1p(exp(-|x|)):
+ *   l_pos(x) = max(-x, 0) + t(x)        l_neg(y) = max(y, 0) + t(y)
+ *   loss     = (1 / num_pos) sum_i l_pos(pos[i]) + (1 / num_neg) sum_j l_neg(neg[j])
+ * Every term is float32 arithmetic; the two sums are float64, in an order that depends on
+ * num_pos and num_neg alone; the loss is rounded to float32 once.  No atomics: the same inputs
+ * give the same bits.  One launch on `stream` while ceil(num_pos / GF_LINK_LOSS_TILE) +
+ * ceil(num_neg / GF_LINK_LOSS_TILE) <= GF_LINK_LOSS_SINGLE_TILES, two beyond; the host never
+ * waits.
+ * d_acc (may be NULL) is a caller-owned running sum of GF_LINK_LOSS_ACC_FIELDS doubles:
+ * {sum_loss, sum_loss_times_num_pos, batches, nonfinite, sum_num_pos}.  A call adds its float32
+ * loss, the loss times num_pos, 1, and num_pos.  A NaN logit gives a NaN loss; infinities follow
+ * the formulas.  When the loss is not finite, nonfinite grows by 1 and no other field changes.
+ * d_partials: caller-owned scratch of gf_link_loss_partial_rows(num_pos, num_neg) doubles (at
+ * most GF_LINK_LOSS_MAX_PARTIAL_ROWS; 0 for the one-launch sizes, where it may be NULL).
+ * gf_link_loss_backward writes d_grad_pos[i] = -s(-pos[i]) * d_grad_out[0] / num_pos and
+ * d_grad_neg[j] = s(neg[j]) * d_grad_out[0] / num_neg, s the logistic function, in one launch;
+ * d_grad_out is one float32 in device memory; a NULL d_grad_pos or d_grad_neg is not computed
+ * (both NULL: nothing is launched).
+ * The _bf16 forms take bfloat16 logits (widened on load, exact) and store bfloat16 gradients
+ * (the float32 value rounded once, to nearest even); the loss is float32 and equals the float32
+ * form's on the widened logits bit for bit.
+ * NULL d_pos, d_neg, d_out or d_grad_out, num_pos == 0, num_neg == 0, a side of 2^31 logits or
+ * more, or a d_partials that is missing or too small: GF_ERR_INVALID_ARGUMENT, nothing launched. */
+#define GF_LINK_LOSS_TILE 1024
+#define GF_LINK_LOSS_SINGLE_TILES 8
+#define GF_LINK_LOSS_MAX_PARTIAL_ROWS 256
+#define GF_LINK_LOSS_ACC_FIELDS 5
+GF_API int gf_link_loss_partial_rows(size_t num_pos, size_t num_neg, size_t* rows);
+GF_API int gf_link_loss(const float* d_pos, const float* d_neg, size_t num_pos, size_t num_neg,
+                        double* d_partials, size_t partial_rows, float* d_out, double* d_acc,
+                        int device, void* stream);
+GF_API int gf_link_loss_backward(const float* d_pos, const float* d_neg, size_t num_pos,
+                                 size_t num_neg, const float* d_grad_out, float* d_grad_pos,
+                                 float* d_grad_neg, int device, void* stream);
+GF_API int gf_link_loss_bf16(const uint16_t* d_pos, const uint16_t* d_neg, size_t num_pos,
+                             size_t num_neg, double* d_partials, size_t partial_rows,
+                             float* d_out, double* d_acc, int device, void* stream);
+GF_API int gf_link_loss_backward_bf16(const uint16_t* d_pos, const uint16_t* d_neg,
+                                      size_t num_pos, size_t num_neg, const float* d_grad_out,
+                                      uint16_t* d_grad_pos, uint16_t* d_grad_neg, int device,
+                                      void* stream);
+
 /* ---- measurement support (bench.py) ---------------------------------------- */
 /* Accumulated device time of a kernel family since the last reset, measured with
  * HIP events recorded around each launch on the launching stream.
