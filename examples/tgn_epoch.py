@@ -22,6 +22,9 @@ dtype=torch.bfloat16) and implies --fused-attention: the composed chain is float
 ops.block_attention takes the bfloat16 q, k, v of the Linear layers as they come.
 --fused-loss takes gnnflow_amd.nn.LinkLoss as the criterion (one ops.link_loss launch each way)
 and reports the epoch's mean loss from its device-side sums, read once after the epoch.
+--fused-gru takes the memory updater's GRU cell as its two GEMMs and one ops.gru_cell call, which
+reads the float32 memory as stored, adds the node-feature projection and writes the rows for
+Memory.update_mem_mail itself.
 """
 import argparse
 from collections import deque
@@ -65,16 +68,27 @@ class MemoryUpdater(nn.Module):
     """GRU cell over [mailbox message || time encoding of (now - last update)]; the updated
     memory (plus a projection of the node features) becomes the block's node embedding."""
 
-    def __init__(self, dim_node, dim_edge, dim_time, dim_memory):
+    def __init__(self, dim_node, dim_edge, dim_time, dim_memory, fused_gru=False):
         super().__init__()
         self.time = TimeEncoding(dim_time)
         self.cell = nn.GRUCell(2 * dim_memory + dim_edge + dim_time, dim_memory)
         self.proj = nn.Linear(dim_node, dim_memory) if dim_node else None
+        self.fused_gru = fused_gru      # the cell as two GEMMs and one ops.gru_cell call
 
     def forward(self, b):
         x = torch.cat([b.srcdata['mem_input'], self.time(b.srcdata['ts'] - b.srcdata['mem_ts'])], 1)
-        new_mem = self.cell(x, b.srcdata['mem']).float()      # bfloat16 under autocast
         R = b.num_dst_nodes()
+        if self.fused_gru:
+            cell, mem = self.cell, b.srcdata['mem']
+            b.srcdata['h'], new_mem = ops.gru_cell(
+                F.linear(x, cell.weight_ih, cell.bias_ih),
+                F.linear(mem, cell.weight_hh, cell.bias_hh), mem,
+                residual=self.proj(b.srcdata['h']) if self.proj is not None else None,
+                num_last=R)
+            return dict(last_updated_nid=b.srcdata['ID'][:R].detach(),
+                        last_updated_memory=new_mem,
+                        last_updated_ts=b.srcdata['ts'][:R].detach())
+        new_mem = self.cell(x, b.srcdata['mem']).float()      # bfloat16 under autocast
         last = dict(last_updated_nid=b.srcdata['ID'][:R].detach(),
                     last_updated_memory=new_mem[:R].detach().clone(),
                     last_updated_ts=b.srcdata['ts'][:R].detach())
@@ -143,9 +157,9 @@ class EdgeScorer(nn.Module):
 
 class TGN(nn.Module):
     def __init__(self, dim_node, dim_time=100, dim_embed=100, dim_memory=100, heads=2,
-                 att_dropout=0.0, fused_attention=False):
+                 att_dropout=0.0, fused_attention=False, fused_gru=False):
         super().__init__()
-        self.updater = MemoryUpdater(dim_node, 0, dim_time, dim_memory)
+        self.updater = MemoryUpdater(dim_node, 0, dim_time, dim_memory, fused_gru)
         self.att = Attention(dim_memory, dim_time, dim_embed, heads, att_dropout, fused_attention)
         self.score = EdgeScorer(dim_embed)
 
@@ -171,6 +185,8 @@ def main():
                          "--fused-attention)")
     ap.add_argument("--fused-loss", action="store_true",
                     help="nn.LinkLoss as the criterion; the epoch's mean loss from its sums")
+    ap.add_argument("--fused-gru", action="store_true",
+                    help="the memory updater's GRU cell as two GEMMs and one ops.gru_cell call")
     args = ap.parse_args()
     fused = args.fused_attention or args.amp
     criterion = gnnflow_amd.nn.LinkLoss() if args.fused_loss else None
@@ -191,7 +207,8 @@ def main():
     node_feats = torch.rand((N, args.dim_node), device=dev)
     cache = LRUCache(0.0, 0.2, N, E, dev, node_feats, None, args.dim_node, 0)
     cache.init_cache()
-    model = TGN(args.dim_node, att_dropout=args.att_dropout, fused_attention=fused).to(dev)
+    model = TGN(args.dim_node, att_dropout=args.att_dropout, fused_attention=fused,
+                fused_gru=args.fused_gru).to(dev)
     memory = Memory(N, 0, 100, dev)
     opt = torch.optim.Adam(model.parameters(), lr=1e-4)
     n_train = int(E * args.train_frac)
@@ -295,7 +312,8 @@ def main():
         "graph_build_s": round(build_s, 2), "epochs": out,
         **({"att_dropout": args.att_dropout} if args.att_dropout else {}),
         **({"fused_attention": True} if fused else {}),
-        **({"fused_loss": True} if args.fused_loss else {}), **({"amp": "bfloat16"} if args.amp else {})}))
+        **({"fused_loss": True} if args.fused_loss else {}),
+        **({"fused_gru": True} if args.fused_gru else {}), **({"amp": "bfloat16"} if args.amp else {})}))
 
 
 if __name__ == "__main__":

@@ -312,6 +312,10 @@ PROTOTYPES = {
                                              _p, _sz, _p, _p, _p, C.c_int, _p]),
     "gf_layer_epilogue_backward_bf16": (C.c_int, [_p, _p, _p, _p, _sz, _sz, C.c_float, C.c_uint64,
                                                   _p, _p, _sz, _p, _p, _p, C.c_int, _p]),
+    "gf_gru_cell": (C.c_int, [_p, _p, _p, _p, C.c_int, _sz, _sz, _sz, _p, _p, C.c_int, _p]),
+    "gf_gru_cell_bf16": (C.c_int, [_p, _p, _p, _p, C.c_int, _sz, _sz, _sz, _p, _p, C.c_int, _p]),
+    "gf_gru_cell_backward": (C.c_int, [_p, _p, _p, _sz, _sz, _p, _p, _p, _p, C.c_int, _p]),
+    "gf_gru_cell_backward_bf16": (C.c_int, [_p, _p, _p, _sz, _sz, _p, _p, _p, _p, C.c_int, _p]),
     "gf_link_metrics_partial_rows": (C.c_int, [_sz, C.POINTER(_sz)]),
     "gf_link_metrics": (C.c_int, [_p, _p, _sz, _sz, _p, _sz, _p, _p, C.c_int, _p]),
     "gf_link_loss_partial_rows": (C.c_int, [_sz, _sz, C.POINTER(_sz)]),

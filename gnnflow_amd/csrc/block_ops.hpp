@@ -1,8 +1,8 @@
 // Segment operations on a sampled block (block_ops.hip, block_attention.hip, block_gat.hip and their
 // bfloat16 siblings block_ops_bf16.hip, block_attention_bf16.hip, block_gat_bf16.hip), the fused time
 // encoding in front of them (time_encode.hip) and the fused edge score behind them
-// (edge_score.hip), and the metrics of the scores it leaves (link_metrics.hip): the entry points
-// other translation units call.
+// (edge_score.hip), and the metrics of the scores it leaves (link_metrics.hip), and the GRU gates
+// of the memory updater (gru_cell.hip): the entry points other translation units call.
 #pragma once
 
 #include <cstddef>
@@ -280,5 +280,31 @@ void link_loss_bf16_forward(const uint16_t* d_pos, const uint16_t* d_neg, size_t
 void link_loss_bf16_backward(const uint16_t* d_pos, const uint16_t* d_neg, size_t num_pos,
                              size_t num_neg, const float* d_grad_out, uint16_t* d_grad_pos,
                              uint16_t* d_grad_neg, int device, hipStream_t stream);
+
+// gru_cell.hip: the gates of a GRU cell behind its two GEMMs, gi = x W_ih^T + b_ih and gh = h W_hh^T
+// + b_hh [n, 3 * hidden] in the order r, z, n, hx [n, hidden]:
+//   r = sigma(gi_r + gh_r), z = sigma(gi_z + gh_z), n = tanh(gi_n + r * gh_n), u = (1 - z) n + z hx
+// in one launch: d_out [n, hidden] = u (+ residual, float32 or bfloat16 by residual_bf16, null:
+// none) and d_last [num_last, hidden] = the first rows of u (num_last <= n; 0: d_last may be
+// null).  The backward recomputes the gates and writes d_grad_gi, d_grad_gh [n, 3 * hidden] and
+// d_grad_hx [n, hidden] from d_grad_out [n, hidden] in one launch; a null one is skipped.  The
+// residual's gradient is d_grad_out itself.  n == 0 launches nothing.
+void gru_cell_forward(const float* d_gi, const float* d_gh, const float* d_hx,
+                      const void* d_residual, int residual_bf16, size_t n, size_t hidden,
+                      size_t num_last, float* d_out, float* d_last, int device,
+                      hipStream_t stream);
+void gru_cell_backward(const float* d_gi, const float* d_gh, const float* d_hx, size_t n,
+                       size_t hidden, const float* d_grad_out, float* d_grad_gi, float* d_grad_gh,
+                       float* d_grad_hx, int device, hipStream_t stream);
+// The same with bfloat16 gi and gh and bfloat16 grad_gi / grad_gh (widened on load, rounded once
+// on store); hx, out, last, grad_out and grad_hx float32.
+void gru_cell_bf16_forward(const uint16_t* d_gi, const uint16_t* d_gh, const float* d_hx,
+                           const void* d_residual, int residual_bf16, size_t n, size_t hidden,
+                           size_t num_last, float* d_out, float* d_last, int device,
+                           hipStream_t stream);
+void gru_cell_bf16_backward(const uint16_t* d_gi, const uint16_t* d_gh, const float* d_hx,
+                            size_t n, size_t hidden, const float* d_grad_out,
+                            uint16_t* d_grad_gi, uint16_t* d_grad_gh, float* d_grad_hx,
+                            int device, hipStream_t stream);
 
 }  // namespace gf

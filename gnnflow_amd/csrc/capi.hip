@@ -403,6 +403,40 @@ int gf_layer_epilogue_backward_bf16(const uint16_t* d_x, const float* d_gamma,
   });
 }
 
+int gf_gru_cell(const float* d_gi, const float* d_gh, const float* d_hx, const void* d_residual,
+                int residual_bf16, size_t n, size_t hidden, size_t num_last, float* d_out,
+                float* d_last, int device, void* stream) {
+  return guarded([&] {
+    gf::gru_cell_forward(d_gi, d_gh, d_hx, d_residual, residual_bf16, n, hidden, num_last, d_out,
+                         d_last, device, as_stream(stream));
+  });
+}
+int gf_gru_cell_backward(const float* d_gi, const float* d_gh, const float* d_hx, size_t n,
+                         size_t hidden, const float* d_grad_out, float* d_grad_gi,
+                         float* d_grad_gh, float* d_grad_hx, int device, void* stream) {
+  return guarded([&] {
+    gf::gru_cell_backward(d_gi, d_gh, d_hx, n, hidden, d_grad_out, d_grad_gi, d_grad_gh,
+                          d_grad_hx, device, as_stream(stream));
+  });
+}
+int gf_gru_cell_bf16(const uint16_t* d_gi, const uint16_t* d_gh, const float* d_hx,
+                     const void* d_residual, int residual_bf16, size_t n, size_t hidden,
+                     size_t num_last, float* d_out, float* d_last, int device, void* stream) {
+  return guarded([&] {
+    gf::gru_cell_bf16_forward(d_gi, d_gh, d_hx, d_residual, residual_bf16, n, hidden, num_last,
+                              d_out, d_last, device, as_stream(stream));
+  });
+}
+int gf_gru_cell_backward_bf16(const uint16_t* d_gi, const uint16_t* d_gh, const float* d_hx,
+                              size_t n, size_t hidden, const float* d_grad_out,
+                              uint16_t* d_grad_gi, uint16_t* d_grad_gh, float* d_grad_hx,
+                              int device, void* stream) {
+  return guarded([&] {
+    gf::gru_cell_bf16_backward(d_gi, d_gh, d_hx, n, hidden, d_grad_out, d_grad_gi, d_grad_gh,
+                               d_grad_hx, device, as_stream(stream));
+  });
+}
+
 static_assert(GF_LINK_METRICS_MAX_SCORES == gf::kLinkMetricsMaxScores &&
                   GF_LINK_METRICS_TILE == gf::kLinkMetricsTile &&
                   GF_LINK_METRICS_PARTIAL_WORDS == gf::kLinkMetricsPartialWords,

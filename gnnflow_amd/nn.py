@@ -262,6 +262,16 @@ FUSED_EDGE_SCORE_DEFAULT = True
 FUSED_EPILOGUE_DEFAULT = False
 
 
+# Default of `fused_gru` in GRUMemoryUpdater.  True only once scripts/gru_cell_bench.py has shown
+# the module with ops.gru_cell, forward + backward, ahead of the module with torch's GRU cell on
+# every one of its lines by more than the torch side's own round-to-round spread
+# (profiles/gru_cell_bench.jsonl).  It did not hold on the run recorded there:
+# medians 352-638 us against torch's 334-634 us at N = 1 800 and 19 800 alike (the host's pace of
+# enqueueing 17-31 launches), ahead by more than torch's spread on 1 of the 8 lines, behind at
+# N = 1 800 without node features in float32 (0.949x).  So the default stays False.
+FUSED_GRU_DEFAULT = False
+
+
 class TimeEncode(nn.Module):
     """TGAT's time encoding cos(w * dt + b): w = 1 / 10^linspace(0, 9, dim_time), b = 0 at
     initialisation, both trainable; held as a Linear(1, dim_time) named `w`.  float32 input on
@@ -437,7 +447,13 @@ class GRUMemoryUpdater(nn.Module):
     reference it leaves b.srcdata['mem_input'] as prepare_input wrote it.  With
     `fused_time_encode` the GRU input is one ops.time_encode_cat call.  Under bfloat16 autocast the
     GRU cell returns bfloat16; it is widened once, so 'last_updated_memory' (Memory stores
-    float32) and b.srcdata['h'] come out float32 as they do outside autocast."""
+    float32) and b.srcdata['h'] come out float32 as they do outside autocast.
+
+    With `fused_gru` and float32 memory rows on the GPU, the cell is its two GEMMs (F.linear with
+    the parameters of `updater`, which stays an nn.GRUCell: state dicts do not change) and one
+    ops.gru_cell call that takes b.srcdata['mem'] as stored -- float32, never rounded, under
+    autocast too -- adds the residual and writes 'last_updated_memory' as an output of its own:
+    no cast, no clone of the memory rows and no add behind it."""
 
     def __init__(self, dim_node: int, dim_edge: int, dim_time: int, dim_embed: int,
                  dim_memory: int):
@@ -452,6 +468,25 @@ class GRUMemoryUpdater(nn.Module):
             self.node_feat_proj = nn.Linear(dim_node, dim_memory)
         # False: time_enc + torch.cat instead of ops.time_encode_cat (not part of the state)
         self.fused_time_encode = FUSED_TIME_ENCODE_DEFAULT
+        # True: ops.gru_cell behind the two GEMMs instead of nn.GRUCell (not part of the state)
+        self.fused_gru = FUSED_GRU_DEFAULT
+
+    def _forward_fused(self, b, x):
+        """The rest of forward() through ops.gru_cell."""
+        cell, mem, R = self.updater, b.srcdata['mem'], b.num_dst_nodes()
+        gi = F.linear(x, cell.weight_ih, cell.bias_ih)
+        gh = F.linear(mem, cell.weight_hh, cell.bias_hh)
+        residual = None
+        if self.dim_node > 0:
+            residual = b.srcdata['h']
+            if self.dim_node != self.dim_embed:
+                residual = self.node_feat_proj(residual)
+        h, last_mem = ops.gru_cell(gi, gh, mem, residual=residual, num_last=R)
+        last = {"last_updated_nid": b.srcdata['ID'][:R].detach().clone(),
+                "last_updated_memory": last_mem,
+                "last_updated_ts": b.srcdata['ts'][:R].detach().clone()}
+        b.srcdata['h'] = h
+        return last
 
     def forward(self, b):
         x = b.srcdata['mem_input']
@@ -461,7 +496,13 @@ class GRUMemoryUpdater(nn.Module):
                 x = ops.time_encode_cat((x,), dt, self.time_enc.w.weight, self.time_enc.w.bias)
             else:
                 x = torch.cat([x, self.time_enc(dt)], dim=1)
-        updated = self.updater(x, b.srcdata['mem'])
+        mem = b.srcdata['mem']
+        if self.fused_gru and mem.is_cuda and mem.dtype == torch.float32 and \
+                self.updater.weight_ih.dtype == torch.float32 and \
+                x.dtype in (torch.float32, torch.bfloat16) and \
+                (self.dim_node == 0 or b.srcdata['h'].dtype in (torch.float32, torch.bfloat16)):
+            return self._forward_fused(b, x)
+        updated = self.updater(x, mem)
         if updated.dtype == torch.bfloat16:      # bfloat16 autocast: memory and 'h' stay float32
             updated = updated.float()
         R = b.num_dst_nodes()

@@ -19,6 +19,11 @@ make on a sampled block, on HIP segment kernels (csrc/block_ops.hip) with autogr
                                            TemporalAttentionLayer.forward after w_out, in one launch
                                            with the Philox mask of block_attention, redrawn in the
                                            backward (csrc/layer_epilogue.hip)
+    gru_cell(gi, gh, hx, residual)         everything torch.nn.GRUCell does behind its two GEMMs, the
+                                           residual add of the memory updater and the copy of the
+                                           first rows for Memory.update_mem_mail
+                                           (memory_updater.py:62-85), one launch each way without a
+                                           workspace (csrc/gru_cell.hip)
     link_metrics(pos, neg)                 average_precision_score / roc_auc_score of the reference's
                                            evaluate() (scripts/offline_edge_prediction.py:141-146) and
                                            the MRR, counted on the GPU without a sort, a sync or a copy
@@ -28,8 +33,8 @@ make on a sampled block, on HIP segment kernels (csrc/block_ops.hip) with autogr
                                            each way, with a running epoch sum on the device
                                            (csrc/link_loss.hip)
 
-block_attention, block_reduce, block_max, block_gat, time_encode_cat, edge_score, link_loss and
-dropout_relu_layer_norm also run on bfloat16 (the tensors autocast hands them), by one rule: float32 arithmetic, one rounding on
+block_attention, block_reduce, block_max, block_gat, time_encode_cat, edge_score, link_loss,
+gru_cell and dropout_relu_layer_norm also run on bfloat16 (the tensors autocast hands them), by one rule: float32 arithmetic, one rounding on
 store.  Every bfloat16 element is widened to float32 where it is loaded (exact), the arithmetic is
 the float32 kernels' own in the same order, and each bfloat16 result is rounded once, to nearest
 even.  So op(x.bfloat16()) == op(x.bfloat16().float()).to(torch.bfloat16) bit for bit, forward and
@@ -937,6 +942,123 @@ def dropout_relu_layer_norm(x: torch.Tensor, weight: torch.Tensor, bias: torch.T
             x.device))
     return _DropoutReluLayerNorm.apply(x.contiguous(), weight.contiguous(), bias.contiguous(),
                                        eps, p32, dropout_seed if p32 > 0 else 0)
+
+
+class _GruCell(torch.autograd.Function):
+    @staticmethod
+    @_fwd
+    def forward(ctx, gi, gh, hx, residual, num_last):
+        # gi, gh [N, 3H] contiguous, both fp32 or both bf16; hx [N, H] fp32; residual [N, H] fp32
+        # or bf16 or None
+        N, H = hx.shape
+        f32 = dict(dtype=torch.float32, device=hx.device)
+        out, last = torch.empty((N, H), **f32), torch.empty((num_last, H), **f32)
+        if N:
+            lib = _capi.load()
+            fn = lib.gf_gru_cell_bf16 if gi.dtype == torch.bfloat16 else lib.gf_gru_cell
+            with torch.cuda.device(hx.device):
+                _capi.check(fn(
+                    gi.data_ptr(), gh.data_ptr(), hx.data_ptr(), _ptr(residual),
+                    int(residual is not None and residual.dtype == torch.bfloat16), N, H,
+                    num_last, out.data_ptr(), _ptr(last), hx.device.index, _stream(hx.device)))
+        ctx.save_for_backward(gi, gh, hx)      # neither the gates nor a workspace
+        ctx.residual_dtype = None if residual is None else residual.dtype
+        ctx.mark_non_differentiable(last)
+        return out, last
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, grad, _grad_last):
+        gi, gh, hx = ctx.saved_tensors
+        N, H = hx.shape
+        need_gi, need_gh, need_hx, need_res = ctx.needs_input_grad[:4]
+        need_res = need_res and ctx.residual_dtype is not None
+        if N == 0:      # zeros, and nothing to launch
+            return (torch.zeros_like(gi) if need_gi else None,
+                    torch.zeros_like(gh) if need_gh else None,
+                    torch.zeros_like(hx) if need_hx else None,
+                    torch.zeros_like(hx, dtype=ctx.residual_dtype) if need_res else None, None)
+        if not (need_gi or need_gh or need_hx or need_res):
+            return None, None, None, None, None
+        g = _grad_as(grad, torch.float32)
+        dgi = torch.empty_like(gi) if need_gi else None
+        dgh = torch.empty_like(gh) if need_gh else None
+        dhx = torch.empty_like(hx) if need_hx else None
+        if need_gi or need_gh or need_hx:
+            lib = _capi.load()
+            fn = lib.gf_gru_cell_backward_bf16 if gi.dtype == torch.bfloat16 \
+                else lib.gf_gru_cell_backward
+            with torch.cuda.device(hx.device):
+                _capi.check(fn(
+                    gi.data_ptr(), gh.data_ptr(), hx.data_ptr(), N, H, g.data_ptr(), _ptr(dgi),
+                    _ptr(dgh), _ptr(dhx), hx.device.index, _stream(hx.device)))
+        # the residual's gradient is the incoming one: no kernel
+        return dgi, dgh, dhx, (g.to(ctx.residual_dtype) if need_res else None), None
+
+
+def gru_cell(gi: torch.Tensor, gh: torch.Tensor, hx: torch.Tensor,
+             residual: Optional[torch.Tensor] = None, num_last: int = 0):
+    """What torch.nn.GRUCell does behind its two GEMMs, with the memory updater's residual add and
+    its copy of the first rows, in one kernel each way (csrc/gru_cell.hip).
+
+    gi = F.linear(x, weight_ih, bias_ih) and gh = F.linear(hx, weight_hh, bias_hh): [N, 3H], gate
+    chunks in torch's order r, z, n; hx: [N, H]; residual: [N, H] or None; 0 <= num_last <= N:
+
+        r = sigmoid(gi_r + gh_r)      z = sigmoid(gi_z + gh_z)      n = tanh(gi_n + r * gh_n)
+        u = (1 - z) * n + z * hx
+        h_out = u + residual  (u without one)          last = u[:num_last]
+
+    Returns (h_out [N, H], last [num_last, H]), both float32.  `last` is a buffer of its own,
+    never includes the residual and is not differentiable: what Memory.update_mem_mail stores.
+    Differentiable in gi, gh, hx and residual.  The forward writes no workspace: gi, gh and hx are
+    saved and the gates recomputed by the same expressions in the backward.  A gradient that is
+    not asked for is None and is not computed; the residual's gradient is the incoming gradient
+    itself.  Nothing is summed, so every result is bit-identical from run to run.
+
+    gi and gh are both float32 or both bfloat16 (what the Linears return under autocast), hx is
+    float32 always (Memory's state is never rounded), residual float32 or bfloat16 independently;
+    any other dtype raises TypeError.  The module's rule -- float32 arithmetic, one rounding on
+    store -- applies: h_out, last and the gradient of hx equal, bit for bit, the float32 op's on
+    gi.float() and gh.float(); the gradients of gi and gh are bfloat16, its float32 gradients
+    rounded once.  All on one GPU; row slices such as mem[:N] are taken as they are, any other
+    non-contiguous input is copied first."""
+    for name, x in (("gi", gi), ("gh", gh), ("hx", hx)):
+        if not isinstance(x, torch.Tensor):
+            raise TypeError("{} must be a tensor, got {}".format(name, type(x).__name__))
+    if residual is not None and not isinstance(residual, torch.Tensor):
+        raise TypeError("residual must be a tensor or None, got {}".format(
+            type(residual).__name__))
+    if isinstance(num_last, bool) or not isinstance(num_last, int):
+        raise TypeError("num_last must be an int, got {}".format(type(num_last).__name__))
+    if (gi.dtype, gh.dtype) not in ((torch.float32,) * 2, (torch.bfloat16,) * 2):
+        raise TypeError("gru_cell computes in float32 and takes gi and gh both float32 or both "
+                        "bfloat16, gi is {} and gh is {}".format(gi.dtype, gh.dtype))
+    if hx.dtype != torch.float32:
+        raise TypeError("gru_cell computes in float32, hx is {}".format(hx.dtype))
+    if residual is not None and residual.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("gru_cell takes a float32 or bfloat16 residual, residual is {}".format(
+            residual.dtype))
+    if hx.dim() != 2:
+        raise ValueError("hx must be [N, H], got {}".format(tuple(hx.shape)))
+    N, H = (int(n) for n in hx.shape)
+    if H == 0:
+        raise ValueError("gru_cell needs H >= 1")
+    for name, x in (("gi", gi), ("gh", gh)):
+        if tuple(x.shape) != (N, 3 * H):
+            raise ValueError("{} must be [N, 3H] = [{}, {}], got {}".format(
+                name, N, 3 * H, tuple(x.shape)))
+    if residual is not None and tuple(residual.shape) != (N, H):
+        raise ValueError("residual must be [N, H] = [{}, {}], got {}".format(
+            N, H, tuple(residual.shape)))
+    if not 0 <= num_last <= N:
+        raise ValueError("num_last must be in [0, {}], got {}".format(N, num_last))
+    for name, x in (("gi", gi), ("gh", gh), ("residual", residual)):
+        if x is not None and x.device != hx.device:
+            raise ValueError("{} is on {}, hx on {}".format(name, x.device, hx.device))
+    if hx.device.type != "cuda":
+        raise ValueError("gru_cell runs on the GPU, the inputs are on {}".format(hx.device))
+    return _GruCell.apply(gi.contiguous(), gh.contiguous(), hx.contiguous(),
+                          None if residual is None else residual.contiguous(), num_last)
 
 
 LINK_METRICS_MAX_SCORES = 65536      # GF_LINK_METRICS_MAX_SCORES: the limit on P + N

@@ -1088,6 +1088,53 @@ GF_API int gf_layer_epilogue_backward_bf16(const uint16_t* d_x, const float* d_g
                                            float* d_grad_gamma, float* d_grad_beta, int device,
                                            void* stream);
 
+/* Fused gates of a GRU cell (torch.nn.GRUCell; the reference's TGN memory updater,
+ * modules/memory_updater.py:62-85) behind its two GEMMs: d_gi = x W_ih^T + b_ih and d_gh = h W_hh^T
+ * + b_hh [n, 3 * hidden], gate chunks in the order r, z, n, d_hx [n, hidden], row-major and
+ * contiguous, fp32:
+ *   r = 1 / (1 + expf(-(gi_r + gh_r)))      z = 1 / (1 + expf(-(gi_z + gh_z)))
+ *   n = tanhf(gi_n + r * gh_n)              u = (1 - z) * n + z * hx
+ *   out[i]  = u[i] (+ residual[i])          i < n
+ *   last[i] = u[i]                          i < num_last       (never the residual)
+ * in one launch that writes d_out [n, hidden] and d_last [num_last, hidden] (fp32) and nothing
+ * else.  d_residual [n, hidden] may be NULL (none); it is fp32 when residual_bf16 == 0 and
+ * bfloat16 (uint16_t as above, widened on load) when it is 1.  16-byte accesses when hidden % 4
+ * == 0 and every pointer is 16-byte aligned, element by element otherwise; the bits do not depend
+ * on which.  No pre-activation gives a NaN or an infinity.  hidden == 0, num_last > n,
+ * residual_bf16 other than 0 or 1, 2^31 rows or 2^38 elements or more, or, with n > 0, a NULL
+ * d_gi, d_gh, d_hx or d_out or a NULL d_last with num_last > 0: GF_ERR_INVALID_ARGUMENT; n == 0
+ * launches nothing. */
+GF_API int gf_gru_cell(const float* d_gi, const float* d_gh, const float* d_hx,
+                       const void* d_residual, int residual_bf16, size_t n, size_t hidden,
+                       size_t num_last, float* d_out, float* d_last, int device, void* stream);
+/* Gradients of gf_gru_cell from g = d_grad_out [n, hidden] (fp32), with r, z, n recomputed from
+ * d_gi, d_gh and d_hx by the forward's expressions:
+ *   a_n = g * (1 - z) * (1 - n * n)      a_z = g * (hx - n) * z * (1 - z)
+ *   a_r = a_n * gh_n * r * (1 - r)
+ *   grad_gi = [a_r, a_z, a_n]      grad_gh = [a_r, a_z, a_n * r]      grad_hx = g * z
+ * in one launch, without a reduction (bit-identical from run to run).  Any of d_grad_gi,
+ * d_grad_gh [n, 3 * hidden] and d_grad_hx [n, hidden] may be NULL (skipped; all three: no
+ * launch).  The gradient of the residual is d_grad_out itself.  The checks of gf_gru_cell. */
+GF_API int gf_gru_cell_backward(const float* d_gi, const float* d_gh, const float* d_hx, size_t n,
+                                size_t hidden, const float* d_grad_out, float* d_grad_gi,
+                                float* d_grad_gh, float* d_grad_hx, int device, void* stream);
+/* gf_gru_cell and gf_gru_cell_backward for bfloat16 d_gi and d_gh (uint16_t as above) and
+ * bfloat16 d_grad_gi / d_grad_gh; d_hx, d_out, d_last, d_grad_out and d_grad_hx stay fp32.  Gates
+ * are widened on load, the arithmetic and its order are the fp32 entry points', and grad_gi and
+ * grad_gh are rounded once to nearest even on store: every output equals the fp32 entry point's
+ * on the widened gates (grad_gi, grad_gh: rounded to bfloat16), bit for bit.  16-byte accesses
+ * when hidden % 8 == 0, 8-byte gate accesses when hidden % 4 == 0, and the pointers are aligned
+ * for them.  The same checks. */
+GF_API int gf_gru_cell_bf16(const uint16_t* d_gi, const uint16_t* d_gh, const float* d_hx,
+                            const void* d_residual, int residual_bf16, size_t n, size_t hidden,
+                            size_t num_last, float* d_out, float* d_last, int device,
+                            void* stream);
+GF_API int gf_gru_cell_backward_bf16(const uint16_t* d_gi, const uint16_t* d_gh,
+                                     const float* d_hx, size_t n, size_t hidden,
+                                     const float* d_grad_out, uint16_t* d_grad_gi,
+                                     uint16_t* d_grad_gh, float* d_grad_hx, int device,
+                                     void* stream);
+
 /* Link-prediction metrics of one validation batch from the scores d_pos [num_pos] of its true
  * edges and d_neg [num_neg] of its negative ones (float32, compared as IEEE compares them, so
  * -0 == +0): d_out[3] = {AP, AUC, MRR} as float64, what scikit-learn's average_precision_score
