@@ -25,6 +25,10 @@ and reports the epoch's mean loss from its device-side sums, read once after the
 --fused-gru takes the memory updater's GRU cell as its two GEMMs and one ops.gru_cell call, which
 reads the float32 memory as stored, adds the node-feature projection and writes the rows for
 Memory.update_mem_mail itself.
+--device-batches takes the epoch's batches from a gnnflow_amd.DeviceBatchStream: one materialize()
+launch per epoch writes every batch's roots and timestamps, the negatives drawn by Philox from
+the split's distinct destinations (a DeviceDstSet) as utils.get_batch draws them, keyed by
+(seed, edge row, epoch).  The default run draws them from all node ids with torch.randint.
 """
 import argparse
 from collections import deque
@@ -187,6 +191,9 @@ def main():
                     help="nn.LinkLoss as the criterion; the epoch's mean loss from its sums")
     ap.add_argument("--fused-gru", action="store_true",
                     help="the memory updater's GRU cell as two GEMMs and one ops.gru_cell call")
+    ap.add_argument("--device-batches", action="store_true",
+                    help="the epoch's batches from a DeviceBatchStream (negatives from the "
+                         "split's destination set, one launch per epoch)")
     args = ap.parse_args()
     fused = args.fused_attention or args.amp
     criterion = gnnflow_amd.nn.LinkLoss() if args.fused_loss else None
@@ -219,6 +226,12 @@ def main():
     main_stream = torch.cuda.current_stream(dev)
     gen = torch.Generator(device=dev).manual_seed(0)
     depth = 2                       # samples begun ahead of the batch being trained on
+    batch_stream = None
+    if args.device_batches:
+        n = nb * B
+        dst_set = gnnflow_amd.DeviceDstSet(N, dev, gd["dst"][:n])
+        batch_stream = gnnflow_amd.DeviceBatchStream(gd["src"][:n], gd["dst"][:n], gd["ts"][:n],
+                                                     gd["eid"][:n], B, dst_set, seed=0)
 
     def epoch_roots():
         """Roots / timestamps of EVERY batch of the split, resident in HBM: [nb, 3 B] =
@@ -226,6 +239,10 @@ def main():
         device.  (Until round 5 each batch's roots were assembled in numpy and copied H2D on
         the training stream, i.e. BEHIND the previous batch's model kernels: 1.0 ms of every
         batch's "sample" time.)"""
+        if batch_stream is not None:
+            batch_stream.set_epoch(epoch)
+            batches = batch_stream.materialize()      # one launch; read on `side` after the wait
+            return [b[0] for b in batches], [b[1] for b in batches]
         n = nb * B
         neg = torch.randint(0, N, (nb, B), device=dev, generator=gen, dtype=torch.int64)
         roots = torch.cat([gd["src"][:n].view(nb, B), gd["dst"][:n].view(nb, B), neg], dim=1)
@@ -313,7 +330,8 @@ def main():
         **({"att_dropout": args.att_dropout} if args.att_dropout else {}),
         **({"fused_attention": True} if fused else {}),
         **({"fused_loss": True} if args.fused_loss else {}),
-        **({"fused_gru": True} if args.fused_gru else {}), **({"amp": "bfloat16"} if args.amp else {})}))
+        **({"fused_gru": True} if args.fused_gru else {}),
+        **({"device_batches": True} if args.device_batches else {}), **({"amp": "bfloat16"} if args.amp else {})}))
 
 
 if __name__ == "__main__":

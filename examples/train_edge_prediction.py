@@ -5,7 +5,7 @@ of the reference's static models, the 2-layer `gnnflow_amd.models.SAGE` (GraphSA
 `gnnflow_amd.models.GAT`.  Synthetic REDDIT-shaped data; a usage example, not a benchmark.
 
     python examples/train_edge_prediction.py [--batches 50] [--model {sage,gat}] [--amp]
-                                             [--fused-loss]
+                                             [--fused-loss] [--device-batches]
 
 --amp runs the forward and the loss under torch.autocast('cuda', dtype=torch.bfloat16).  No
 GradScaler: bfloat16 has float32's range.  The models need no cast for it: the block ops take
@@ -14,6 +14,10 @@ the bfloat16 rows autocast produces (as models.DGNN does, examples/tgn_epoch.py 
 --fused-loss takes gnnflow_amd.nn.LinkLoss as the criterion: one ops.link_loss launch each way
 instead of torch's two BCE-with-logits expressions, the epoch's sums kept on the device, and no
 float(loss) per batch -- the losses are read once, after the loop.
+
+--device-batches takes the batches from a gnnflow_amd.DeviceBatchStream instead of the
+DataLoader: the edge stream and the destination set live in HBM, every batch is one kernel
+launch, and no numpy array reaches the sampler.
 """
 import argparse
 import os
@@ -43,7 +47,7 @@ def build_model(name, dim_in, dim_hidden):
 
 
 def main(num_batches=50, batch_size=600, seed=0, verbose=True, amp=False, model='sage',
-         fused_loss=False):
+         fused_loss=False, device_batches=False):
     import pandas as pd
     torch.manual_seed(seed)
     dev = torch.device("cuda", 0)
@@ -57,9 +61,14 @@ def main(num_batches=50, batch_size=600, seed=0, verbose=True, amp=False, model=
     cache = LRUCache(0.0, 0.2, g["num_nodes"], g["num_edges"], dev, node_feats, None, d, 0)
     cache.init_cache()
 
-    ds = EdgePredictionDataset(df, DstRandEdgeSampler(df["dst"].to_numpy(), seed=seed))
-    loader = DataLoader(ds, sampler=RandomStartBatchSampler(SequentialSampler(ds), batch_size, False),
-                        collate_fn=default_collate_ndarray, num_workers=0)
+    if device_batches:
+        dst_set = gnnflow_amd.DeviceDstSet(g["num_nodes"], dev, df["dst"].to_numpy())
+        loader = gnnflow_amd.DeviceBatchStream.from_dataframe(df, batch_size, dst_set, seed=seed)
+    else:
+        ds = EdgePredictionDataset(df, DstRandEdgeSampler(df["dst"].to_numpy(), seed=seed))
+        loader = DataLoader(ds, sampler=RandomStartBatchSampler(SequentialSampler(ds), batch_size,
+                                                                False),
+                            collate_fn=default_collate_ndarray, num_workers=0)
     model = build_model(model, d, 64).to(dev)
     opt = torch.optim.Adam(model.parameters(), lr=1e-3)
     criterion = gnnflow_amd.nn.LinkLoss() if fused_loss else None
@@ -103,5 +112,8 @@ if __name__ == "__main__":
     ap.add_argument("--model", choices=["sage", "gat"], default="sage")
     ap.add_argument("--fused-loss", action="store_true",
                     help="nn.LinkLoss as the criterion, the losses read once after the loop")
+    ap.add_argument("--device-batches", action="store_true",
+                    help="batches from a DeviceBatchStream: assembled on the GPU, one launch each")
     args = ap.parse_args()
-    main(args.batches, amp=args.amp, model=args.model, fused_loss=args.fused_loss)
+    main(args.batches, amp=args.amp, model=args.model, fused_loss=args.fused_loss,
+         device_batches=args.device_batches)

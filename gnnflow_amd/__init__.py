@@ -4,6 +4,7 @@ Drop-in for the hot path of jasperzhong/GNNFlow: `DynamicGraph`, `TemporalSample
 `cache.LRUCache` keep the reference's Python API; the work runs in hand-written HIP
 kernels (gfx950) behind the C ABI of include/gnnflow_hip.h.
 """
+from .data import DeviceBatchStream, DeviceDstSet
 from .dynamic_graph import DynamicGraph
 from .metrics import LinkMetrics
 from .mfg import MFGBlock
@@ -13,4 +14,5 @@ from .temporal_sampler import SamplingResult, TemporalSampler
 
 __all__ = ["DynamicGraph", "TemporalSampler", "SamplingResult", "MFGBlock", "SAGEConv", "GATConv",
            "TimeEncode", "TemporalAttentionLayer", "TransfomerAttentionLayer", "GRUMemoryUpdater",
-           "GRUMemeoryUpdater", "EdgePredictor", "MLP", "LinkMetrics", "LinkLoss"]
+           "GRUMemeoryUpdater", "EdgePredictor", "MLP", "LinkMetrics", "LinkLoss",
+           "DeviceDstSet", "DeviceBatchStream"]

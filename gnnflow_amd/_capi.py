@@ -323,6 +323,13 @@ PROTOTYPES = {
     "gf_link_loss_bf16": (C.c_int, [_p, _p, _sz, _sz, _p, _sz, _p, _p, C.c_int, _p]),
     "gf_link_loss_backward": (C.c_int, [_p, _p, _sz, _sz, _p, _p, _p, C.c_int, _p]),
     "gf_link_loss_backward_bf16": (C.c_int, [_p, _p, _sz, _sz, _p, _p, _p, C.c_int, _p]),
+    "gf_batch_assemble": (C.c_int, [_p, _p, _p, _sz, _sz, _sz, _sz, _p, _p, C.c_uint64, C.c_uint64,
+                                    C.c_uint64, _p, _p, C.c_int, _p]),
+    "gf_batch_assemble_many": (C.c_int, [_p, _p, _p, _sz, _p, _sz, _sz, _sz, _p, _p, C.c_uint64,
+                                         C.c_uint64, C.c_uint64, _p, _p, _sz, C.c_int, _p]),
+    "gf_dst_set_mark": (C.c_int, [_p, _sz, _p, _sz, _p, C.c_int, _p]),
+    "gf_dst_set_scratch_bytes": (C.c_int, [_sz, C.POINTER(_sz)]),
+    "gf_dst_set_compact": (C.c_int, [_p, _sz, _p, _sz, _p, _p, _sz, C.c_int, _p]),
     "gf_debug_part_host_us": (C.c_int, [C.POINTER(C.c_double), C.c_int]),
     "gf_debug_merge_recounts": (C.c_int, [C.POINTER(C.c_uint64)]),
     "gf_debug_part_reused_roots": (C.c_int, [C.POINTER(C.c_uint64)]),

@@ -1,6 +1,7 @@
 // extern "C" entry points of include/gnnflow_hip.h: thin, exception-free shims.  Here: the error
 // slot they all report through, the pid behind foreign_process(), the shims over free functions
-// (block ops, time encoding, edge score, link metrics, debug counters).  Those over a handle: capi_{graph,sampler,cache,comm}.
+// (block ops, time encoding, edge score, link metrics, batch stream, debug counters).  Those over a handle: capi_{graph,sampler,cache,comm}.
+#include "batch_stream.hpp"
 #include "block_ops.hpp"
 #include "capi_handles.hpp"
 #include "partition.hpp"
@@ -497,6 +498,51 @@ int gf_link_loss_backward_bf16(const uint16_t* d_pos, const uint16_t* d_neg, siz
   return guarded([&] {
     gf::link_loss_bf16_backward(d_pos, d_neg, num_pos, num_neg, d_grad_out, d_grad_pos,
                                 d_grad_neg, device, as_stream(stream));
+  });
+}
+
+static_assert(GF_DST_SET_TILE_WORDS == gf::kDstSetTileWords,
+              "gnnflow_hip.h and batch_stream.hpp disagree on the destination-set tile");
+int gf_batch_assemble(const int64_t* d_src, const int64_t* d_dst, const float* d_time,
+                      size_t num_rows, size_t lo, size_t hi, size_t neg_ratio,
+                      const int64_t* d_dl, const int64_t* d_dl_count, uint64_t seed,
+                      uint64_t epoch, uint64_t first_row, int64_t* d_roots, float* d_ts,
+                      int device, void* stream) {
+  return guarded([&] {
+    gf::batch_assemble(d_src, d_dst, d_time, num_rows, lo, hi, neg_ratio, d_dl, d_dl_count, seed,
+                       epoch, first_row, d_roots, d_ts, device, as_stream(stream));
+  });
+}
+int gf_batch_assemble_many(const int64_t* d_src, const int64_t* d_dst, const float* d_time,
+                           size_t num_rows, const int64_t* d_borders, size_t num_batches,
+                           size_t max_batch_rows, size_t neg_ratio, const int64_t* d_dl,
+                           const int64_t* d_dl_count, uint64_t seed, uint64_t epoch,
+                           uint64_t first_row, int64_t* d_roots, float* d_ts, size_t capacity,
+                           int device, void* stream) {
+  return guarded([&] {
+    gf::batch_assemble_many(d_src, d_dst, d_time, num_rows, d_borders, num_batches,
+                            max_batch_rows, neg_ratio, d_dl, d_dl_count, seed, epoch, first_row,
+                            d_roots, d_ts, capacity, device, as_stream(stream));
+  });
+}
+int gf_dst_set_mark(const int64_t* d_ids, size_t n, uint64_t* d_bitmap, size_t num_nodes,
+                    uint64_t* d_out_of_range, int device, void* stream) {
+  return guarded([&] {
+    gf::dst_set_mark(d_ids, n, d_bitmap, num_nodes, d_out_of_range, device, as_stream(stream));
+  });
+}
+int gf_dst_set_scratch_bytes(size_t num_nodes, size_t* bytes) {
+  return guarded([&] {
+    GF_REQUIRE(bytes != nullptr, "gf_dst_set_scratch_bytes: null output");
+    *bytes = gf::dst_set_scratch_bytes(num_nodes);
+  });
+}
+int gf_dst_set_compact(const uint64_t* d_bitmap, size_t num_nodes, int64_t* d_ids,
+                       size_t ids_capacity, int64_t* d_count, void* d_scratch,
+                       size_t scratch_bytes, int device, void* stream) {
+  return guarded([&] {
+    gf::dst_set_compact(d_bitmap, num_nodes, d_ids, ids_capacity, d_count, d_scratch,
+                        scratch_bytes, device, as_stream(stream));
   });
 }
 

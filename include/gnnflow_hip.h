@@ -1210,6 +1210,68 @@ GF_API int gf_link_loss_backward_bf16(const uint16_t* d_pos, const uint16_t* d_n
                                       uint16_t* d_grad_pos, uint16_t* d_grad_neg, int device,
                                       void* stream);
 
+/* One batch of an edge stream that lives in device memory, as the reference's utils.get_batch
+ * lays it out, its negative destinations drawn on the device.  d_src, d_dst (int64) and d_time
+ * (float32) are the num_rows rows of the stream, [lo, hi) the batch, B = hi - lo, K = neg_ratio,
+ * d_dl the ascending list of distinct destinations and M = d_dl_count[0] its length, READ FROM
+ * DEVICE MEMORY when the kernel runs (the set may have grown since without the host knowing):
+ *   d_roots[0:B]          = d_src[lo:hi]
+ *   d_roots[B:2B]         = d_dst[lo:hi]
+ *   d_roots[2B + k*B + i] = d_dl[((uint64_t)u * M) >> 32]       k < K, i < B
+ *   d_ts[j*B + i]         = d_time[lo + i]                      j < 2 + K
+ *   u   = gf_philox4x32_10_first(seed, tid, epoch)              (gnnflow_rng.h)
+ *   tid = (first_row + lo + i) * K + k                          (uint64, wrapping)
+ * k-major: positive i's negatives are at stride B, the layout gf_link_metrics takes.  The key of
+ * a draw is the GLOBAL row first_row + lo + i of the edge, so an edge gets the same negatives
+ * whatever the batch borders are and whichever rank (each with the first_row of its slice)
+ * assembles it.  The range reduction is one 32 x 32 -> 64 multiply, no modulo; as in the
+ * reference a negative may equal the true destination.  M <= 0 or M >= 2^32: every negative is
+ * -1.  The edge ids of the batch are d_eid[lo:hi] as they stand and need no kernel.
+ * d_roots and d_ts hold (2 + K) * B elements.  One launch on `stream`, no atomics, every output
+ * written once; 16-byte loads and stores where lo, B and the pointers allow, scalar otherwise.
+ * lo == hi: nothing is launched.
+ * d_src == NULL asks for the negatives alone (then d_dst, d_time and d_ts must be NULL too and
+ * num_rows only bounds hi): d_roots[k*B + i], K * B elements, same tid.
+ * gf_batch_assemble_many assembles num_batches consecutive batches in one launch: batch b is
+ * [d_borders[b], d_borders[b + 1]) with the num_batches + 1 int64 borders in device memory, and
+ * its slices of d_roots / d_ts start at element (2 + K) * (d_borders[b] - d_borders[0]), laid out
+ * as above with its own B.  capacity: elements d_roots and d_ts each hold.  max_batch_rows sizes
+ * the grid (a longer batch is still written in full).  A batch whose borders are not ascending,
+ * negative, past num_rows, or whose slices would pass capacity writes nothing.
+ * lo > hi, hi > num_rows, a NULL buffer that is needed, K > 0 with a NULL d_dl or d_dl_count,
+ * K >= 65536, num_rows >= 2^44, num_batches >= 2^31: GF_ERR_INVALID_ARGUMENT, nothing launched. */
+GF_API int gf_batch_assemble(const int64_t* d_src, const int64_t* d_dst, const float* d_time,
+                             size_t num_rows, size_t lo, size_t hi, size_t neg_ratio,
+                             const int64_t* d_dl, const int64_t* d_dl_count, uint64_t seed,
+                             uint64_t epoch, uint64_t first_row, int64_t* d_roots, float* d_ts,
+                             int device, void* stream);
+GF_API int gf_batch_assemble_many(const int64_t* d_src, const int64_t* d_dst,
+                                  const float* d_time, size_t num_rows, const int64_t* d_borders,
+                                  size_t num_batches, size_t max_batch_rows, size_t neg_ratio,
+                                  const int64_t* d_dl, const int64_t* d_dl_count, uint64_t seed,
+                                  uint64_t epoch, uint64_t first_row, int64_t* d_roots,
+                                  float* d_ts, size_t capacity, int device, void* stream);
+
+/* The set of distinct destinations behind d_dl: a bitmap of num_nodes bits in
+ * ceil(num_nodes / 64) 64-bit words (bit id % 64 of word id / 64), zeroed by the caller.
+ * gf_dst_set_mark sets the bit of each of the n ids (atomic OR); an id outside [0, num_nodes)
+ * sets nothing and adds 1 to d_out_of_range[0].  One launch; n == 0: none.
+ * gf_dst_set_compact writes the set's ids in ascending order to d_ids and their number to
+ * d_count[0] (what numpy.unique gives for everything marked so far): a popcount per tile of
+ * GF_DST_SET_TILE_WORDS words, an exclusive scan of the tile counts by one workgroup, an emit
+ * per tile; three launches on `stream`, no atomics, no kernel waits on another workgroup.  Ids
+ * past ids_capacity are not written and d_count[0] is then ids_capacity.  d_scratch:
+ * gf_dst_set_scratch_bytes(num_nodes) bytes, 8-byte aligned, caller-owned.
+ * num_nodes >= 2^40, a NULL buffer that is needed, or a d_scratch that is too small or
+ * misaligned: GF_ERR_INVALID_ARGUMENT, nothing launched. */
+#define GF_DST_SET_TILE_WORDS 1024
+GF_API int gf_dst_set_mark(const int64_t* d_ids, size_t n, uint64_t* d_bitmap, size_t num_nodes,
+                           uint64_t* d_out_of_range, int device, void* stream);
+GF_API int gf_dst_set_scratch_bytes(size_t num_nodes, size_t* bytes);
+GF_API int gf_dst_set_compact(const uint64_t* d_bitmap, size_t num_nodes, int64_t* d_ids,
+                              size_t ids_capacity, int64_t* d_count, void* d_scratch,
+                              size_t scratch_bytes, int device, void* stream);
+
 /* ---- measurement support (bench.py) ---------------------------------------- */
 /* Accumulated device time of a kernel family since the last reset, measured with
  * HIP events recorded around each launch on the launching stream.
