@@ -316,6 +316,9 @@ PROTOTYPES = {
     "gf_gru_cell_bf16": (C.c_int, [_p, _p, _p, _p, C.c_int, _sz, _sz, _sz, _p, _p, C.c_int, _p]),
     "gf_gru_cell_backward": (C.c_int, [_p, _p, _p, _sz, _sz, _p, _p, _p, _p, C.c_int, _p]),
     "gf_gru_cell_backward_bf16": (C.c_int, [_p, _p, _p, _sz, _sz, _p, _p, _p, _p, C.c_int, _p]),
+    "gf_edge_rank_scratch": (C.c_int, [_sz, _sz, _sz, C.POINTER(_sz)]),
+    "gf_edge_rank": (C.c_int, [_p, _p, _p, _p, _sz, _sz, _sz, _sz, _p, _p, _p, _sz, _p, _p, _p,
+                               _p, C.c_int, _p]),
     "gf_link_metrics_partial_rows": (C.c_int, [_sz, C.POINTER(_sz)]),
     "gf_link_metrics": (C.c_int, [_p, _p, _sz, _sz, _p, _sz, _p, _p, C.c_int, _p]),
     "gf_link_loss_partial_rows": (C.c_int, [_sz, _sz, C.POINTER(_sz)]),

@@ -457,6 +457,26 @@ int gf_link_metrics(const float* d_pos, const float* d_neg, size_t num_pos, size
   });
 }
 
+static_assert(GF_EDGE_RANK_MAX_K == gf::kEdgeRankMaxK && GF_EDGE_RANK_CHUNK == gf::kEdgeRankChunk,
+              "gnnflow_hip.h and block_ops.hpp disagree on the edge-rank constants");
+int gf_edge_rank_scratch(size_t num_src, size_t num_cand, size_t k, size_t* bytes) {
+  return guarded([&] {
+    GF_REQUIRE(bytes != nullptr, "gf_edge_rank_scratch: null output");
+    *bytes = gf::edge_rank_scratch_bytes(num_src, num_cand, k);
+  });
+}
+int gf_edge_rank(const float* d_src, const float* d_cand, const float* d_w, const float* d_bias,
+                 size_t num_src, size_t num_cand, size_t dim, size_t k, const float* d_ref_score,
+                 const int64_t* d_skip, void* d_scratch, size_t scratch_bytes, float* d_values,
+                 int64_t* d_indices, int64_t* d_greater, int64_t* d_equal, int device,
+                 void* stream) {
+  return guarded([&] {
+    gf::edge_rank(d_src, d_cand, d_w, d_bias, num_src, num_cand, dim, k, d_ref_score, d_skip,
+                  d_scratch, scratch_bytes, d_values, d_indices, d_greater, d_equal, device,
+                  as_stream(stream));
+  });
+}
+
 static_assert(GF_LINK_LOSS_TILE == gf::kLinkLossTile &&
                   GF_LINK_LOSS_SINGLE_TILES == gf::kLinkLossSingleTiles &&
                   GF_LINK_LOSS_MAX_PARTIAL_ROWS == gf::kLinkLossMaxPartialRows &&

@@ -15,6 +15,8 @@ spelled GRUMemeoryUpdater), the consumer of gnnflow_amd.memory.Memory.prepare_in
 
 EdgePredictor / MLP are the reference's heads (layers.py:171-214); EdgePredictor's tail can run as
 one ops.edge_score call.  LinkLoss is the training criterion that follows them, on ops.link_loss."""
+from typing import Optional
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -559,6 +561,79 @@ class EdgePredictor(nn.Module):
         pos_edge = F.relu(src_h + self.dst_fc(h[B:2 * B]))
         neg_edge = F.relu(src_h + self.dst_fc(h[2 * B:]))
         return self.out_fc(pos_edge), self.out_fc(neg_edge)
+
+    _RANK_TORCH_CHUNK = 4096      # candidates per step of the torch expression of rank()
+
+    @torch.no_grad()
+    def rank(self, h_src: torch.Tensor, h_cand: torch.Tensor, k: int = 0,
+             target: Optional[torch.Tensor] = None) -> "ops.EdgeRank":
+        """Ranks the candidates h_cand [C, dim_embed] for every source h_src [B, dim_embed]:
+        the score of forward() for every (source, candidate) pair, of which the k best
+        candidates per source (ops.EdgeRank.values / .indices, [B, k]) are kept and, with
+        `target` (int64 [B], the index of each source's true destination among the candidates,
+        all in range, not checked), the counts .greater / .equal of the OTHER candidates that
+        beat / tie the target's score; .rank is 1 + greater + equal / 2.  The target is left
+        out of its own row's list too (the filtered setting).  No gradient, no state.
+
+        float32 rows on the GPU with `fused_score` take ops.edge_rank, whose scores are those of
+        ops.edge_score bit for bit: the target's score is ops.edge_score's and is compared
+        exactly.  Anything else (the CPU, fused_score off, bfloat16 under autocast, widened to
+        float32) takes the torch expression over chunks of the candidates, with the same order
+        (score descending, then index ascending; NaN last) and the same (-inf, -1) fill."""
+        src_p, cand_p = self.src_fc(h_src), self.dst_fc(h_cand)
+        w, b = self.out_fc.weight, self.out_fc.bias
+        if self.fused_score and src_p.is_cuda and src_p.dtype == cand_p.dtype == torch.float32 \
+                and w.dtype == torch.float32:
+            ref = None
+            if target is not None:
+                ref = ops.edge_score(src_p, cand_p[target], w, b)
+            return ops.edge_rank(src_p, cand_p, w, b, k=k, ref_score=ref, skip=target)
+        return _rank_torch(src_p.float(), cand_p.float(), w.float().reshape(-1), b.float(), k,
+                           target, self._RANK_TORCH_CHUNK)
+
+
+def _rank_torch(src, cand, w, b, k, target, step):
+    """ops.edge_rank's semantics as a torch expression, `step` candidates at a time."""
+    (B, D), Cn = src.shape, cand.shape[0]
+    if not 0 <= k <= min(Cn, ops.EDGE_RANK_MAX_K):
+        raise ValueError("k must be in [0, min(C, {})] with C = {}, got {}".format(
+            ops.EDGE_RANK_MAX_K, Cn, k))
+    dev = src.device
+    ref = None
+    if target is not None:
+        ref = (F.relu(src + cand[target]) * w).sum(-1) + b
+    greater = torch.zeros(B, dtype=torch.int64, device=dev) if ref is not None else None
+    equal = torch.zeros(B, dtype=torch.int64, device=dev) if ref is not None else None
+    neg_inf = float("-inf")
+    # the running list: (is a number, value, -index) ascending under lexsort = the kernel's key
+    vals = torch.full((B, 0), neg_inf, dtype=torch.float32, device=dev)
+    idx = torch.full((B, 0), -1, dtype=torch.int64, device=dev)
+    for a in range(0, Cn, step):
+        c = cand[a:a + step]
+        score = (F.relu(src[:, None, :] + c[None, :, :]) * w).sum(-1) + b      # [B, n]
+        ids = torch.arange(a, a + c.shape[0], device=dev).expand(B, -1)
+        keep = torch.ones_like(ids, dtype=torch.bool) if target is None \
+            else ids != target[:, None]
+        if ref is not None:
+            greater += ((score > ref[:, None]) & keep).sum(1)
+            equal += ((score == ref[:, None]) & keep).sum(1)
+        if k:
+            vals = torch.cat([vals, torch.where(keep, score, torch.full_like(score, neg_inf))], 1)
+            idx = torch.cat([idx, torch.where(keep, ids, torch.full_like(ids, -1))], 1)
+            # three stable sorts, least significant key first: index ascending, value
+            # descending (NaN as the smallest), skipped entries last
+            order = torch.argsort(torch.where(idx < 0, torch.full_like(idx, Cn), idx), dim=1,
+                                  stable=True)
+            vals, idx = vals.gather(1, order), idx.gather(1, order)
+            sort_v = torch.where(torch.isnan(vals), torch.full_like(vals, neg_inf), vals)
+            tier = torch.where(idx < 0, 2, torch.where(torch.isnan(vals), 1, 0))
+            order = torch.argsort(sort_v, dim=1, descending=True, stable=True)
+            vals, idx, tier = vals.gather(1, order), idx.gather(1, order), tier.gather(1, order)
+            order = torch.argsort(tier, dim=1, stable=True)[:, :k]
+            vals, idx = vals.gather(1, order), idx.gather(1, order)
+    if not k:
+        vals, idx = vals[:, :0], idx[:, :0]
+    return ops.EdgeRank(vals, idx, greater, equal)
 
 
 class LinkLoss(nn.Module):

@@ -32,6 +32,10 @@ make on a sampled block, on HIP segment kernels (csrc/block_ops.hip) with autogr
                                            reference's training step (BCEWithLogitsLoss), one launch
                                            each way, with a running epoch sum on the device
                                            (csrc/link_loss.hip)
+    edge_rank(src, cand, w, b, k, ...)     the edge score of every source against one shared candidate
+                                           set, of which the top k and the rank counts of a reference
+                                           score are kept and nothing else is stored
+                                           (csrc/edge_rank.hip); no autograd
 
 block_attention, block_reduce, block_max, block_gat, time_encode_cat, edge_score, link_loss,
 gru_cell and dropout_relu_layer_norm also run on bfloat16 (the tensors autocast hands them), by one rule: float32 arithmetic, one rounding on
@@ -50,7 +54,7 @@ A block's edges are grouped by destination (the sampler emits them that way); bl
 hand with unordered edges are handled through a stable permutation.
 """
 import ctypes as C
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -819,6 +823,132 @@ def edge_score(src: torch.Tensor, dst: torch.Tensor, weight: torch.Tensor, bias:
         raise ValueError("edge_score runs on the GPU, the inputs are on {}".format(dst.device))
     return _EdgeScore.apply(src.contiguous(), dst.contiguous(), weight.reshape(D).contiguous(),
                             bias.contiguous())
+
+
+EDGE_RANK_MAX_K = 64                 # GF_EDGE_RANK_MAX_K: the longest top-k list
+EDGE_RANK_CHUNK = 256                # GF_EDGE_RANK_CHUNK: candidates per workgroup pass of the kernel
+
+
+class EdgeRank(NamedTuple):
+    """What edge_rank returns.  values, indices: [B, k] (float32, int64); greater, equal: [B]
+    (int64) or None without a reference score."""
+    values: torch.Tensor
+    indices: torch.Tensor
+    greater: Optional[torch.Tensor]
+    equal: Optional[torch.Tensor]
+
+    @property
+    def rank(self) -> Optional[torch.Tensor]:
+        """float64 [B]: 1 + greater + equal / 2, the mean of the optimistic and the pessimistic
+        rank (the convention of link_metrics); None without a reference score."""
+        if self.greater is None:
+            return None
+        return 1.0 + self.greater.double() + self.equal.double() / 2
+
+
+def edge_rank(src: torch.Tensor, cand: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
+              k: int = 0, ref_score: Optional[torch.Tensor] = None,
+              skip: Optional[torch.Tensor] = None) -> EdgeRank:
+    """Scores every source against ONE shared candidate set and keeps, per source, the k best
+    candidates and the number of candidates that beat or tie a reference score:
+
+        score(i, c) = bias + sum_d weight[d] * relu(src[i, d] + cand[c, d])
+
+    in one streaming kernel (csrc/edge_rank.hip) that stores neither the [B * C, D] rows that
+    edge_score(src, cand.repeat_interleave(B, 0)) would need nor the [B, C] scores.  score(i, c)
+    is the float32 value edge_score returns for that pair of rows, bit for bit, so a ref_score
+    taken from edge_score ties exactly with the same candidate here; the one exception is a NaN
+    in src[i, d] + cand[c, d], which makes the score NaN (torch.relu keeps a NaN, edge_score's
+    relu turns it into 0).
+
+    src: [B, D]; cand: [C, D]; weight: [D] or [1, D]; bias: [1]; ref_score: [B] or [B, 1] or
+    None; all float32 on one GPU.  skip: int64 [B] or None.  0 <= k <= min(C, EDGE_RANK_MAX_K),
+    D >= 1, 1 <= C < 2**31.  Inputs are detached: there is no autograd.  Row slices are taken as
+    they are; any other non-contiguous input is copied.
+
+    Returns EdgeRank(values, indices, greater, equal):
+      values, indices [B, k]  the k best candidates of each source, score descending, then
+          candidate index ascending among equal scores.  A NaN score sorts below -inf (by
+          ascending index among NaNs) and is returned as NaN.  A row with fewer than k candidates
+          left (k == C with a valid skip) ends in (-inf, -1).  [B, 0] when k == 0.
+      greater, equal [B]  the candidates with score > / == ref_score[i]; a NaN score is neither,
+          and a NaN ref_score gives two zeros.  None without ref_score.  .rank is
+          1 + greater + equal / 2.
+    Candidate skip[i] is left out of row i's counts and list (the "filtered" setting: the true
+    destination); a value outside [0, C) excludes nothing.  skip works without ref_score too.
+
+    Runs on the current stream and never synchronises; selection under a total order and
+    integer counts: the same inputs give the same bits.
+
+    A candidate set too large for one call is cut into shards cand[a:b]: the counts of the
+    shards add, and the lists (indices + a) are concatenated and go through one
+    torch.topk(values, k) -- after which equal scores are no longer in index order across
+    shards, unless the shards' lists are merged by (value, index) instead."""
+    named = (("src", src), ("cand", cand), ("weight", weight), ("bias", bias))
+    if ref_score is not None:
+        named += (("ref_score", ref_score),)
+    for name, x in named + ((("skip", skip),) if skip is not None else ()):
+        if not isinstance(x, torch.Tensor):
+            raise TypeError("{} must be a tensor, got {}".format(name, type(x).__name__))
+    for name, x in named:
+        if x.dtype != torch.float32:
+            raise TypeError("edge_rank computes in float32, {} is {}".format(name, x.dtype))
+    if skip is not None and skip.dtype != torch.int64:
+        raise TypeError("skip must be int64, got {}".format(skip.dtype))
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise TypeError("k must be an int, got {}".format(type(k).__name__))
+    if src.dim() != 2 or cand.dim() != 2:
+        raise ValueError("src and cand must be [B, D] and [C, D], got {} and {}".format(
+            tuple(src.shape), tuple(cand.shape)))
+    (B, D), Cn = (int(n) for n in src.shape), int(cand.shape[0])
+    if cand.shape[1] != D:
+        raise ValueError("src has {} columns, cand has {}".format(D, cand.shape[1]))
+    if D == 0:
+        raise ValueError("edge_rank needs D >= 1")
+    if Cn == 0:
+        raise ValueError("edge_rank needs at least one candidate")
+    if Cn >= 2 ** 31:
+        raise ValueError("edge_rank takes fewer than 2**31 candidates per call, got {}".format(Cn))
+    if tuple(weight.shape) not in ((D,), (1, D)):
+        raise ValueError("weight must be [D] or [1, D] with D = {}, got {}".format(
+            D, tuple(weight.shape)))
+    if tuple(bias.shape) != (1,):
+        raise ValueError("bias must be [1], got {}".format(tuple(bias.shape)))
+    if k < 0 or k > min(Cn, EDGE_RANK_MAX_K):
+        raise ValueError("k must be in [0, min(C, {})] with C = {}, got {}".format(
+            EDGE_RANK_MAX_K, Cn, k))
+    if ref_score is not None and tuple(ref_score.shape) not in ((B,), (B, 1)):
+        raise ValueError("ref_score must be [B] or [B, 1] with B = {}, got {}".format(
+            B, tuple(ref_score.shape)))
+    if skip is not None and tuple(skip.shape) != (B,):
+        raise ValueError("skip must be [B] with B = {}, got {}".format(B, tuple(skip.shape)))
+    for name, x in named[1:] + ((("skip", skip),) if skip is not None else ()):
+        if x.device != src.device:
+            raise ValueError("{} is on {}, src on {}".format(name, x.device, src.device))
+    if src.device.type != "cuda":
+        raise ValueError("edge_rank runs on the GPU, the inputs are on {}".format(src.device))
+    dev = src.device
+    s, c = src.detach().contiguous(), cand.detach().contiguous()
+    w, b = weight.detach().reshape(D).contiguous(), bias.detach().contiguous()
+    ref = None if ref_score is None else ref_score.detach().reshape(B).contiguous()
+    sk = None if skip is None else skip.detach().contiguous()
+    values = torch.empty((B, k), dtype=torch.float32, device=dev)
+    indices = torch.empty((B, k), dtype=torch.int64, device=dev)
+    greater = equal = None
+    if ref is not None:
+        greater = torch.empty(B, dtype=torch.int64, device=dev)
+        equal = torch.empty(B, dtype=torch.int64, device=dev)
+    if B and (k or ref is not None):
+        lib = _capi.load()
+        nbytes = C.c_size_t(0)
+        _capi.check(lib.gf_edge_rank_scratch(B, Cn, k, C.byref(nbytes)))
+        scratch = torch.empty((nbytes.value + 7) // 8, dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            _capi.check(lib.gf_edge_rank(
+                s.data_ptr(), c.data_ptr(), w.data_ptr(), b.data_ptr(), B, Cn, D, k, _ptr(ref),
+                _ptr(sk), scratch.data_ptr(), scratch.numel() * 8, _ptr(values), _ptr(indices),
+                _ptr(greater), _ptr(equal), dev.index, _stream(dev)))
+    return EdgeRank(values, indices, greater, equal)
 
 
 LAYER_EPILOGUE_MAX_WIDTH = 1024      # GF_LAYER_EPILOGUE_MAX_WIDTH: the limit on D

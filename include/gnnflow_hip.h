@@ -1166,6 +1166,36 @@ GF_API int gf_link_metrics(const float* d_pos, const float* d_neg, size_t num_po
                            size_t num_neg, void* d_partials, size_t partial_rows, double* d_out,
                            double* d_acc, int device, void* stream);
 
+/* Ranking with the edge score: d_src [num_src, dim] against ONE candidate set d_cand [num_cand,
+ * dim] (both fp32, row-major, contiguous), d_w [dim], d_bias [1],
+ *   score(i, c) = bias + sum_d w[d] * max(src[i, d] + cand[c, d], 0)
+ * which is what gf_edge_score returns for that pair of rows, bit for bit (the same adds in the
+ * same order), except that a NaN in src[i, d] + cand[c, d] stays a NaN.  Neither the pairs
+ * [num_src * num_cand, dim] nor the scores [num_src, num_cand] are stored.  Per source i:
+ *   d_values, d_indices [num_src, k]   the k best candidates, score descending, then candidate
+ *       index ascending among equal scores; a NaN score sorts below -inf (by ascending index among
+ *       NaNs) and is returned as NaN; a row with fewer than k candidates left ends in (-inf, -1).
+ *   d_greater, d_equal [num_src]       the number of candidates with score > / == d_ref_score[i]
+ *       (a NaN on either side: neither).  The rank of the reference is 1 + greater + equal / 2,
+ *       the convention of gf_link_metrics.
+ * Candidate d_skip[i] is left out of row i's counts and list; a value outside [0, num_cand)
+ * excludes nothing.  d_ref_score NULL: no counts, d_greater and d_equal are not touched; k == 0:
+ * no list; d_skip NULL: nothing skipped.  num_src == 0, or k == 0 without d_ref_score, launches
+ * nothing.  Two launches on `stream`, no atomics, selection under a total order: the same inputs
+ * give the same bits, and the host never waits.  16-byte loads when dim % 4 == 0 and d_src,
+ * d_cand and d_w are 16-byte aligned, element loads otherwise, the same result either way.
+ * d_scratch: caller-owned, 8-byte aligned, the bytes gf_edge_rank_scratch(num_src, num_cand, k)
+ * gives.  A workgroup pass covers GF_EDGE_RANK_CHUNK candidates.  dim == 0, num_cand == 0 or
+ * >= 2^31, k > min(num_cand, GF_EDGE_RANK_MAX_K): GF_ERR_INVALID_ARGUMENT. */
+#define GF_EDGE_RANK_MAX_K 64
+#define GF_EDGE_RANK_CHUNK 256
+GF_API int gf_edge_rank_scratch(size_t num_src, size_t num_cand, size_t k, size_t* bytes);
+GF_API int gf_edge_rank(const float* d_src, const float* d_cand, const float* d_w,
+                        const float* d_bias, size_t num_src, size_t num_cand, size_t dim, size_t k,
+                        const float* d_ref_score, const int64_t* d_skip, void* d_scratch,
+                        size_t scratch_bytes, float* d_values, int64_t* d_indices,
+                        int64_t* d_greater, int64_t* d_equal, int device, void* stream);
+
 /* The loss of a link-prediction step from the logits d_pos [num_pos] of its true edges and
  * d_neg [num_neg] of its negative ones: BCE-with-logits of d_pos against 1 plus that of d_neg
  * against 0, each a mean, as one float32 d_out[1].  With t(x) = log1p(exp(-|x|)):
