@@ -6,6 +6,13 @@ GPU until the one `compute()` at the end.  Synthetic REDDIT-shaped data and an u
 by default; a usage example, not a benchmark.
 
     python examples/evaluate_edge_prediction.py [--batches 20] [--train-batches 0]
+                                                [--hist-negatives N]
+
+--hist-negatives N takes the validation batches from a `gnnflow_amd.DeviceBatchStream` with N
+negatives per edge, all of them historical where the source has a history (`hist_ratio=N`:
+destinations the source interacted with before the edge's time, drawn on the GPU from the
+graph's edge store), and prints the share of negative slots that hold one.  The graph is built
+with reverse edges, so a source's history includes the nodes that pointed at it.
 """
 import argparse
 import os
@@ -26,7 +33,20 @@ from gnnflow_amd.models import DGNN
 from gnnflow_amd.utils import DstRandEdgeSampler, build_dynamic_graph
 
 
-def evaluate(loader, sampler, model, cache, metrics, num_batches):
+def scores(model, mfgs, neg_ratio):
+    """(pred_pos [B, 1], pred_neg [K * B, 1], k-major) of roots laid out [src | dst | K negative
+    planes].  The model's edge predictor takes one negative per edge: with K > 1 it scores the
+    embeddings once per negative plane."""
+    if neg_ratio == 1:
+        return model(mfgs)
+    h = model(mfgs, return_embed=True)
+    B = h.shape[0] // (2 + neg_ratio)
+    planes = [model.edge_predictor(torch.cat([h[:2 * B], h[(2 + k) * B:(3 + k) * B]]))
+              for k in range(neg_ratio)]
+    return planes[0][0], torch.cat([neg for _, neg in planes])
+
+
+def evaluate(loader, sampler, model, cache, metrics, num_batches, neg_ratio=1):
     """One validation pass: returns (ap, auc) as the reference does, and leaves the other
     fields in `metrics`."""
     model.eval()
@@ -37,13 +57,14 @@ def evaluate(loader, sampler, model, cache, metrics, num_batches):
                 break
             mfgs = sampler.sample(roots, ts)
             cache.fetch_feature(mfgs, eid)
-            pred_pos, pred_neg = model(mfgs)
+            pred_pos, pred_neg = scores(model, mfgs, neg_ratio)
             metrics.update(pred_pos, pred_neg)      # sigmoid, then AP / AUC / MRR; no sync
     result = metrics.compute()                      # the one sync of the pass
     return result["ap"], result["auc"]
 
 
-def main(num_batches=20, batch_size=600, train_batches=0, seed=0, verbose=True):
+def main(num_batches=20, batch_size=600, train_batches=0, seed=0, verbose=True,
+         hist_negatives=0):
     import pandas as pd
     torch.manual_seed(seed)
     dev = torch.device("cuda", 0)
@@ -80,11 +101,24 @@ def main(num_batches=20, batch_size=600, train_batches=0, seed=0, verbose=True):
             opt.step()
 
     metrics = gnnflow_amd.LinkMetrics(dev)
-    ap, auc = evaluate(loader, sampler, model, cache, metrics, num_batches)
+    if hist_negatives:
+        dst_set = gnnflow_amd.DeviceDstSet(g["num_nodes"], dev, df["dst"].to_numpy())
+        # the rows of the pass only, so that the counter below is over exactly its batches
+        loader = gnnflow_amd.DeviceBatchStream.from_dataframe(
+            df.iloc[:num_batches * batch_size], batch_size, dst_set, neg_ratio=hist_negatives,
+            seed=seed, graph=graph, hist_ratio=hist_negatives)
+    ap, auc = evaluate(loader, sampler, model, cache, metrics, num_batches,
+                       neg_ratio=hist_negatives or 1)
     result = metrics.compute()
+    if hist_negatives:
+        # read once per pass, like the metrics
+        slots = int(loader.borders[-1] - loader.borders[0]) * hist_negatives
+        result["hist_share"] = int(loader.hist_filled.item()) / max(slots, 1)
     if verbose:
         print("ap {:.4f} auc {:.4f} mrr {:.4f} over {} batches ({} left out as non-finite)".format(
-            ap, auc, result["mrr"], result["batches"], result["nonfinite"]))
+            ap, auc, result["mrr"], result["batches"], result["nonfinite"]) +
+            (" historical negatives {:.1%} of {} per edge".format(
+                result["hist_share"], hist_negatives) if hist_negatives else ""))
     return result
 
 
@@ -92,5 +126,8 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, default=20)
     ap.add_argument("--train-batches", type=int, default=0)
+    ap.add_argument("--hist-negatives", type=int, default=0,
+                    help="N historical negatives per edge from a DeviceBatchStream (0: the "
+                         "host loader's one random negative)")
     a = ap.parse_args()
-    main(a.batches, train_batches=a.train_batches)
+    main(a.batches, train_batches=a.train_batches, hist_negatives=a.hist_negatives)

@@ -1,5 +1,7 @@
-// extern "C" entry points of include/gnnflow_hip.h over EdgeStore: gf_graph_*.
+// extern "C" entry points of include/gnnflow_hip.h over EdgeStore: gf_graph_* and the one
+// batch call that reads the store, gf_batch_hist_negatives.
 #include "capi_handles.hpp"
+#include "hist_negatives.hpp"
 
 extern "C" {
 
@@ -68,6 +70,20 @@ int gf_graph_metadata_memory_usage(const gf_graph* g, float* out) {
 }
 int gf_graph_device(const gf_graph* g, int* out) {
   return guarded([&] { GF_G(g); *out = g->impl.device(); });
+}
+// reads the store's view NOW: ordered against add_edges / offload_old_blocks by the caller
+int gf_batch_hist_negatives(const gf_graph* g, const int64_t* d_src, const int64_t* d_dst,
+                            const float* d_time, size_t num_rows, const int64_t* d_borders,
+                            size_t num_batches, size_t max_batch_rows, size_t neg_ratio,
+                            size_t hist_ratio, uint64_t seed, uint64_t epoch, uint64_t first_row,
+                            int64_t* d_roots, size_t capacity, uint64_t* d_filled, int device,
+                            void* stream) {
+  return guarded([&] {
+    GF_G(g);
+    gf::batch_hist_negatives(g->impl.view(), d_src, d_dst, d_time, num_rows, d_borders,
+                             num_batches, max_batch_rows, neg_ratio, hist_ratio, seed, epoch,
+                             first_row, d_roots, capacity, d_filled, device, as_stream(stream));
+  });
 }
 
 }  // extern "C"

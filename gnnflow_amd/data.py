@@ -427,15 +427,39 @@ class DeviceBatchStream:
 
     `borders` are the row positions where batches begin plus the end (ascending, host
     integers); the default cuts every `batch_size` rows.  The columns are copied to the device
-    once, here."""
+    once, here.
+
+    `hist_ratio=Kh` (with `graph`, a `DynamicGraph` on the same device) makes the first Kh of
+    the K negatives *historical*: a destination the source interacted with strictly before the
+    edge's time that is not the true one, drawn with replacement from the source's live edges in
+    the graph's temporal edge store (include/gnnflow_hip.h, gf_batch_hist_negatives; up to four
+    attempts per slot under a seed tag of their own).  A second launch directly behind the
+    assemble launch, same stream, overwrites those slots; a slot whose source has no earlier
+    edge, is unknown to the graph, or drew the true destination four times keeps its random
+    negative.  `hist_filled` is a device int64[1] that accumulates the number of slots
+    overwritten (`reset_hist_filled()` zeroes it); divided by the slots asked for, rows x Kh, it
+    is the share of historical negatives — read it once per pass.  Edges added to the graph are
+    drawn from by batches launched after `add_edges` returns.  `add_edges` and
+    `offload_old_blocks` move and free segments: synchronise the streams that batches were
+    launched on before calling either, as for `TemporalSampler.sample`.  On a graph built with
+    reverse edges the history includes nodes that pointed at the source."""
 
     def __init__(self, src, dst, time, eid, batch_size: int, dst_set: Optional[DeviceDstSet],
                  neg_ratio: int = 1, seed: int = 0, first_row: int = 0, borders=None,
-                 device=None):
+                 device=None, graph=None, hist_ratio: int = 0):
         batch_size = _count(batch_size, "batch_size", 1)
         neg_ratio = _count(neg_ratio, "neg_ratio", 0)
         if neg_ratio >= 1 << 16:
             raise ValueError("neg_ratio must be below 65536, got {}".format(neg_ratio))
+        hist_ratio = _count(hist_ratio, "hist_ratio", 0)
+        if hist_ratio > neg_ratio:
+            raise ValueError("hist_ratio must not exceed neg_ratio = {}, got {}".format(
+                neg_ratio, hist_ratio))
+        if graph is None:
+            if hist_ratio:
+                raise ValueError("hist_ratio > 0 needs the graph to draw the history from")
+        elif not (hasattr(graph, "_h") and isinstance(getattr(graph, "device", None), int)):
+            raise TypeError("graph must be a DynamicGraph, got {}".format(type(graph).__name__))
         seed, first_row = _u64(seed, "seed"), _u64(first_row, "first_row")
         src, dst, eid = _id_column(src, "src"), _id_column(dst, "dst"), _id_column(eid, "eid")
         time = _time_column(time)
@@ -455,6 +479,7 @@ class DeviceBatchStream:
         elif device is None:
             raise ValueError("without a destination set a device must be given")
         device = _cuda_device(device)
+        self._check_graph_device(graph, device)
         if borders is None:
             borders = np.append(np.arange(0, rows, batch_size, dtype=np.int64), rows)
         else:
@@ -471,9 +496,12 @@ class DeviceBatchStream:
             device = dst_set.device
         elif device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
+        self._check_graph_device(graph, device)      # "cuda" without an index is known only now
         self._lib = _capi.load()
         self.device, self.dst_set = device, dst_set
         self.batch_size, self.neg_ratio = batch_size, neg_ratio
+        self.graph, self.hist_ratio = graph, hist_ratio
+        self.hist_filled = torch.zeros(1, dtype=torch.int64, device=device) if hist_ratio else None
         self.seed, self.first_row, self.epoch = seed, first_row, 0
         self.rows = rows
         self.src, self.dst = src.to(device), dst.to(device)
@@ -503,9 +531,28 @@ class DeviceBatchStream:
         return cls(df['src'].values, df['dst'].values, df['time'].values, df['eid'].values,
                    batch_size, dst_set, borders=np.asarray(borders, dtype=np.int64), **kwargs)
 
+    @staticmethod
+    def _check_graph_device(graph, device):
+        if graph is not None and device.index is not None and device.index != graph.device:
+            raise ValueError("the graph is on device {}, the stream on {}".format(
+                graph.device, device))
+
     def set_epoch(self, epoch: int):
         """The Philox call word of the negatives: another epoch, other draws for every row."""
         self.epoch = _u64(epoch, "epoch")
+
+    def reset_hist_filled(self):
+        """Zeroes `hist_filled` on the current stream."""
+        if self.hist_filled is not None:
+            self.hist_filled.zero_()
+
+    def _hist_negatives(self, d_borders, count, max_rows, roots, capacity):
+        """The launch behind an assemble launch that overwrote `roots` (same borders)."""
+        _capi.check(self._lib.gf_batch_hist_negatives(
+            self.graph._h, self.src.data_ptr(), self.dst.data_ptr(), self.time.data_ptr(),
+            self.rows, d_borders, count, max_rows, self.neg_ratio, self.hist_ratio, self.seed,
+            self.epoch, self.first_row, roots.data_ptr(), capacity, self.hist_filled.data_ptr(),
+            self.device.index, _capi.current_stream(self.device)))
 
     def __len__(self):
         return len(self.borders) - 1
@@ -533,7 +580,7 @@ class DeviceBatchStream:
 
     def batch(self, i: int, stream=None):
         """(roots, ts, eids) of batch i: one launch on `stream` (default: the current stream),
-        none for an empty batch."""
+        two with historical negatives, none for an empty batch."""
         i = self._index(i)
         lo, hi = int(self.borders[i]), int(self.borders[i + 1])
         planes, dev = 2 + self.neg_ratio, self.device
@@ -548,10 +595,14 @@ class DeviceBatchStream:
                         lo, hi, self.neg_ratio, dl, dl_count, self.seed, self.epoch,
                         self.first_row, roots.data_ptr(), ts.data_ptr(), dev.index,
                         _capi.current_stream(dev)))
+                    if self.hist_ratio:
+                        self._hist_negatives(self._d_borders.data_ptr() + 8 * i, 1, hi - lo,
+                                             roots, planes * (hi - lo))
         return roots, ts, self.eid[lo:hi]
 
     def materialize(self, first: int = 0, count: Optional[int] = None, stream=None):
-        """Batches first .. first + count - 1 (default: to the end) in ONE launch, as a list of
+        """Batches first .. first + count - 1 (default: to the end) in ONE launch (one more for
+        all their historical negatives), as a list of
         (roots, ts, eids) tuples of views into one roots and one ts buffer: the form
         `ReplayPipeline(batches=...)` takes.  The pipeline reads its batches on side streams,
         so synchronise the producing stream (the current one, or `stream`) ONCE after this
@@ -576,6 +627,9 @@ class DeviceBatchStream:
                         self.neg_ratio, dl, dl_count, self.seed, self.epoch, self.first_row,
                         roots.data_ptr(), ts.data_ptr(), total, dev.index,
                         _capi.current_stream(dev)))
+                    if self.hist_ratio:
+                        self._hist_negatives(self._d_borders.data_ptr() + 8 * first, count,
+                                             int(np.diff(b).max()), roots, total)
         out = []
         for k in range(count):
             lo, hi = int(b[k]), int(b[k + 1])

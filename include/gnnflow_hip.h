@@ -1302,6 +1302,71 @@ GF_API int gf_dst_set_compact(const uint64_t* d_bitmap, size_t num_nodes, int64_
                               size_t ids_capacity, int64_t* d_count, void* d_scratch,
                               size_t scratch_bytes, int device, void* stream);
 
+/* Historical negatives: one launch overwrites the first Kh = hist_ratio negative planes of
+ * batches that gf_batch_assemble[_many] has already written.  A slot is overwritten only where
+ * a historical negative exists.  A slot without one keeps the random draw it already holds, so
+ * the fall-back costs nothing and no slot is left undefined.  Every other element stays
+ * bit-identical: the src and dst planes, the negative planes k >= Kh, and all of ts.
+ *
+ * Inputs per slot.  The slot belongs to batch-local row i with global row
+ * g = first_row + lo + i.  It has source s, true destination d, time t, and index
+ * k < Kh <= K.
+ *
+ * History size c.
+ * - Let e = table[s].
+ * - c is the number of elements x in ts_pool[e.start .. e.start + e.size) with x < t.
+ * - The comparison is strict and uses the float < operator, so a NaN t gives c = 0.
+ * - c counts only the live range, that is, what offload_old_blocks has left.
+ * - If s < 0, s >= table_len or c == 0, the slot is kept.
+ *
+ * Draw.  For attempts a = 0 .. GF_HIST_NEG_ATTEMPTS - 1 (4 attempts):
+ * - u = gf_philox4x32_10_first(seed ^ (GF_HIST_NEG_SEED_TAG + a), tid, epoch).
+ * - tid = g * K + k, wrapping, as in gf_batch_assemble.
+ * - j = (uint64(u) * c) >> 32.
+ * - cand = nbr_pool[e.start + j].dst.
+ * - Index j counts from the node's oldest live edge in the store's order.  That order is the
+ *   reverse of what get_temporal_neighbors returns.
+ * - The first attempt with cand != d is written to roots[2B + k*B + i].  If all four attempts
+ *   fail, the slot is kept.
+ *
+ * Documented consequences.
+ * - Draws are with replacement.
+ * - A historical negative may be a destination of another edge of s at time t.
+ * - On a graph built with reverse edges the history includes nodes that pointed at s.
+ *
+ * table, ts_pool and nbr_pool are the node table and the two pools of the graph's temporal edge
+ * store (one contiguous, chronologically sorted segment per node).  GF_HIST_NEG_SEED_TAG keeps
+ * the historical draws independent of the random ones of the same tid; hist_ratio == 0 draws
+ * nothing, so what gf_batch_assemble wrote stands.
+ *
+ * d_src, d_dst, d_time, num_rows, d_borders, num_batches, max_batch_rows, neg_ratio, seed,
+ * epoch, first_row, d_roots and capacity are those of the gf_batch_assemble_many call that wrote
+ * the batches (a single batch: num_batches = 1 and d_borders advanced to its two borders; a
+ * batch written by gf_batch_assemble: the same with capacity = (2 + K) * B).  A batch with bad
+ * borders, or one whose slices would pass capacity, writes nothing, as there.  d_filled: NULL,
+ * or a device uint64 to which the number of slots overwritten is ADDED (one atomic add per
+ * workgroup; zero it yourself).  One launch on `stream`, which must be the stream of the
+ * assemble call or ordered behind it.
+ * Ordering against ingest: the call takes the graph's device view (table and pool addresses,
+ * table length) when it is made, as gf_sampler_sample does.  gf_graph_add_edges and
+ * gf_graph_offload_old_blocks run on the graph's own stream and return with the device state
+ * complete, so a call made after they return sees their edges without further ordering.  They
+ * move segments that fill, reuse freed ones and may reallocate the table and the pools: every
+ * earlier launch of this call must have COMPLETED (stream synchronised, or an event waited for
+ * on the host) before either of them is called, and the graph must outlive the launch.
+ * A NULL graph, a NULL buffer that is needed, hist_ratio > neg_ratio, neg_ratio >= 65536,
+ * num_rows >= 2^44, num_batches >= 2^31: GF_ERR_INVALID_ARGUMENT, nothing launched.
+ * hist_ratio == 0 or num_batches == 0: GF_OK, nothing launched. */
+#define GF_HIST_NEG_ATTEMPTS 4
+#define GF_HIST_NEG_SEED_TAG 0x484953544E454730ULL /* "HISTNEG0" */
+GF_API int gf_batch_hist_negatives(const gf_graph* g, const int64_t* d_src, const int64_t* d_dst,
+                                   const float* d_time, size_t num_rows,
+                                   const int64_t* d_borders, size_t num_batches,
+                                   size_t max_batch_rows, size_t neg_ratio, size_t hist_ratio,
+                                   uint64_t seed, uint64_t epoch, uint64_t first_row,
+                                   int64_t* d_roots, size_t capacity, uint64_t* d_filled,
+                                   int device, void* stream);
+
 /* ---- measurement support (bench.py) ---------------------------------------- */
 /* Accumulated device time of a kernel family since the last reset, measured with
  * HIP events recorded around each launch on the launching stream.
