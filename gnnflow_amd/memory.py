@@ -5,16 +5,79 @@
 gather / last-writer-wins scatter run as HIP kernels (gnnflow_amd/csrc/memory_ops.hip) instead
 of CPU `torch.unique` + index ops."""
 import ctypes as C
+import operator
 from typing import Dict, Optional, Union
 
 import torch
 
 from . import _capi
 
+# The winner tables are tagged `epoch << 32 | position`; the native call takes epochs below this.
+_EPOCH_LIMIT = 1 << 31
+
+_ID_DTYPES = (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)
+
+
+def _shape(t):
+    return tuple(t.shape)
+
+
+def check_ids(ids, name='ids'):
+    """`ids` of prepare_input: a 1-D integer tensor.  Needs no device."""
+    if not isinstance(ids, torch.Tensor):
+        raise TypeError('{} must be a tensor, got {}'.format(name, type(ids).__name__))
+    if ids.dtype not in _ID_DTYPES:
+        raise ValueError('{} must have an integer dtype, got {}'.format(name, ids.dtype))
+    if ids.dim() != 1:
+        raise ValueError('{} must be 1-D, got shape {}'.format(name, _shape(ids)))
+
+
+def check_update_shapes(dim_memory, dim_edge, last_updated_nid, last_updated_memory,
+                        last_updated_ts, edge_feats=None, neg_sample_ratio=1):
+    """Shapes of an update_mem_mail call, checked before anything is launched: the kernels
+    take raw pointers and trust them.  Needs no device.  Returns (n, B)."""
+    check_ids(last_updated_nid, 'last_updated_nid')
+    for name, t in (('last_updated_memory', last_updated_memory),
+                    ('last_updated_ts', last_updated_ts)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError('{} must be a tensor, got {}'.format(name, type(t).__name__))
+    if edge_feats is not None and not isinstance(edge_feats, torch.Tensor):
+        raise TypeError('edge_feats must be a tensor or None, got {}'.format(
+            type(edge_feats).__name__))
+    neg_sample_ratio = operator.index(neg_sample_ratio)     # TypeError for what is no integer
+    if neg_sample_ratio < 0:
+        raise ValueError('neg_sample_ratio must be >= 0, got {}'.format(neg_sample_ratio))
+    n = int(last_updated_nid.shape[0])
+    chunks = 2 + neg_sample_ratio
+    if n % chunks != 0:
+        raise ValueError('last_updated_nid has {} ids, not a multiple of 2 + neg_sample_ratio = {}'
+                         .format(n, chunks))
+    B = n // chunks
+    if _shape(last_updated_memory) != (n, dim_memory):
+        raise ValueError('last_updated_memory must be [{}, {}], got shape {}'.format(
+            n, dim_memory, _shape(last_updated_memory)))
+    if _shape(last_updated_ts) != (n,):
+        raise ValueError('last_updated_ts must be [{}], got shape {}'.format(
+            n, _shape(last_updated_ts)))
+    if edge_feats is not None and _shape(edge_feats) != (B, dim_edge):
+        raise ValueError('edge_feats must be [{}, {}] or None, got shape {}'.format(
+            B, dim_edge, _shape(edge_feats)))
+    return n, B
+
 
 class Memory:
     """
     Memory module proposed by TGN
+
+    Node ids outside [0, num_nodes) are not an error: `update_mem_mail` skips their positions
+    (the other positions of the batch are written as usual) and `prepare_input` returns all-zero
+    rows for them.  The native calls trust the shapes they are given; `update_mem_mail` and
+    `prepare_input` check them first (`check_update_shapes`, `check_ids`) and raise ValueError
+    before anything is launched or changed.
+
+    The last writer of a node is found with per-node tags `epoch << 32 | position`, one epoch
+    per update, in tables that are never cleared.  Epochs stay below 2^31: when the next one
+    would reach it, the tables are zeroed and the count restarts at 1.
     """
 
     def __init__(self, num_nodes: int, dim_edge: int, dim_memory: int,
@@ -92,8 +155,10 @@ class Memory:
         """
         Prepare the input for the memory module (memory.py:156-190): fills
         b.srcdata['mem', 'mem_ts', 'mail_ts', 'mem_input'] for b.srcdata['ID'].
+        An id outside [0, num_nodes) gets all-zero rows.
         """
         ids = b.srcdata['ID']
+        check_ids(ids)
         if ids.device != self.device or ids.dtype != torch.int64 or not ids.is_contiguous():
             ids = ids.to(self.device, torch.int64).contiguous()
         n = int(ids.shape[0])
@@ -122,7 +187,13 @@ class Memory:
                         neg_sample_ratio: int = 1):
         """
         Update the mem and mailbox of last updated nodes (memory.py:192-269).
+        Positions whose id is outside [0, num_nodes) are skipped.
         """
+        n, _ = check_update_shapes(self.dim_memory, self.dim_edge, last_updated_nid,
+                                   last_updated_memory, last_updated_ts, edge_feats,
+                                   neg_sample_ratio)
+        if n == 0:
+            return
         def dev(t, dtype):
             if t.device != self.device or t.dtype != dtype or not t.is_contiguous():
                 t = t.to(self.device, dtype).contiguous()
@@ -131,9 +202,9 @@ class Memory:
         mem = dev(last_updated_memory, torch.float32)
         ts = dev(last_updated_ts, torch.float32)
         ef = None if edge_feats is None else dev(edge_feats, torch.float32)
-        n = int(nid.shape[0])
-        if n == 0:
-            return
+        if self._epoch + 1 >= _EPOCH_LIMIT:     # stale tags would outrank epoch 1: clear them
+            self._win.zero_()
+            self._epoch = 0
         self._epoch += 1
         with torch.cuda.device(self.device):
             _capi.check(self._lib.gf_memory_update(

@@ -436,7 +436,9 @@ GF_API int gf_gather_rows(const float* d_feats, size_t num_rows, size_t dim,
 /* Memory.prepare_input (memory.py:156-190): mem = node_memory[ids], mem_ts =
  * node_memory_ts[ids], mail_ts = mailbox_ts[ids], mem_input = mailbox[ids] — the reference's
  * CPU unique + inverse scatter is only an optimisation of exactly that.  One launch.
- * dim_mail = 2 * dim_memory + dim_edge. */
+ * dim_mail = 2 * dim_memory + dim_edge.  An id outside [0, num_nodes) is no error: its four
+ * output rows are all zero.  The call trusts its shapes (tables of num_nodes rows, d_ids and the
+ * outputs of n rows); gnnflow_amd.memory.Memory checks them before it calls. */
 GF_API int gf_memory_prepare_input(const float* d_node_memory, const float* d_node_memory_ts,
                                    const float* d_mailbox, const float* d_mailbox_ts,
                                    size_t num_nodes, size_t dim_memory, size_t dim_mail,
@@ -448,7 +450,12 @@ GF_API int gf_memory_prepare_input(const float* d_node_memory, const float* d_no
  * [B, dim_edge] or NULL (zeros).  Per distinct node the LAST occurrence wins (mailbox: in the
  * interleaved src0,dst0,src1,... order; memory: in src.. ++ dst.. order).  d_win_mail /
  * d_win_mem: caller-owned uint64[num_nodes] scratch, zero-initialised once; epoch: strictly
- * increasing, starting at 1. */
+ * increasing, starting at 1 and below 2^31 (a caller that gets there zeroes both scratch tables
+ * and starts again at 1).  A position whose id is outside [0, num_nodes) is skipped, in the
+ * table whose order meets it; the batch's other positions are written as usual.  The call
+ * trusts its shapes (d_nid and d_ts of n, d_memory of n rows, d_edge_feats of
+ * n / (2 + neg_sample_ratio) rows) and reads past a shorter buffer;
+ * gnnflow_amd.memory.Memory checks them before it calls. */
 GF_API int gf_memory_update(float* d_node_memory, float* d_node_memory_ts, float* d_mailbox,
                             float* d_mailbox_ts, size_t num_nodes, size_t dim_memory,
                             size_t dim_edge, const int64_t* d_nid, const float* d_memory,

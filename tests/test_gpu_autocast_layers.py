@@ -242,9 +242,13 @@ def _train_two_steps(world, name, fused):
             assert p.grad is not None and torch.isfinite(p.grad).all(), k
         opt.step()
         if model.has_memory():
+            # (a 2-layer model's outer block: whole (src, dst, neg) thirds only, update_mem_mail
+            # refuses a remainder; it read none of those rows when it still let them through)
+            last = model.last_updated
+            whole = last["last_updated_nid"].shape[0] // 3 * 3
             with torch.no_grad():
-                model.memory.update_mem_mail(**model.last_updated, edge_feats=None,
-                                             neg_sample_ratio=1)
+                model.memory.update_mem_mail(**{k: v[:whole] for k, v in last.items()},
+                                             edge_feats=None, neg_sample_ratio=1)
         scores += [pos.detach().float().clone(), neg.detach().float().clone()]
         assert torch.isfinite(loss) and all(torch.isfinite(s).all() for s in scores)
     assert all(torch.isfinite(p).all() for p in model.parameters())

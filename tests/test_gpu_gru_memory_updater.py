@@ -186,8 +186,13 @@ def _dgnn_step(world, fused, codes=False):
             1, R * H + 1, dtype=torch.float32, device="cuda").reshape(R, H))
         mem.node_memory.fill_(0)
         mem.mailbox.fill_(0)
+    # the outer block of a 2-layer model has any number of destination rows; update_mem_mail
+    # takes whole (src, dst, neg) thirds and refuses a remainder, so the rows behind the last
+    # whole third go (it read none of them when it still let them through)
+    whole = last["last_updated_nid"].shape[0] // 3 * 3
     with torch.no_grad():
-        mem.update_mem_mail(**last, edge_feats=None, neg_sample_ratio=1)
+        mem.update_mem_mail(**{k: v[:whole] for k, v in last.items()}, edge_feats=None,
+                            neg_sample_ratio=1)
     return mem.node_memory.clone(), mem.mailbox.clone(), model.last_updated, src, model
 
 
