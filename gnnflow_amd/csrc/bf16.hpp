@@ -21,4 +21,9 @@ __device__ inline uint16_t narrow(float x) {
   return static_cast<uint16_t>((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
 }
 
+// the value as a kernel templated on its element type T stores it: as it is, or narrowed
+template <class T> __device__ inline T narrow_to(float x);
+template <> __device__ inline float narrow_to<float>(float x) { return x; }
+template <> __device__ inline uint16_t narrow_to<uint16_t>(float x) { return narrow(x); }
+
 }  // namespace gf

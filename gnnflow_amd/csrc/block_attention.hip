@@ -8,7 +8,7 @@
 //
 // The layer computes K and V PER EDGE and a block's edges are grouped by destination, so edge
 // e reads k[e], v[e] and q[row[e]]: no source index, no atomics, forward or backward, and
-// every output address is written exactly once.  fp32 throughout.
+// every output address is written exactly once.  The arithmetic is fp32 throughout.
 //
 // Work item = one (destination, head) pair, given to a GROUP of G lanes (G = 8, 16, 32 or 64,
 // the smallest that covers the D columns of a head; a head wider than 64 columns gives each
@@ -37,20 +37,34 @@
 // The kernels without dropout are kept as they were and compile to the code they had before
 // dropout existed.
 //
-// block_attention_bf16.hip holds these four kernels once more for bfloat16 q, k, v, out and
-// gradients: the same bodies with widen() on the loads and narrow() on the stores.  A fix to a
-// kernel here must be made there too (tests/test_gpu_block_attention_bf16.py holds the two bit
-// for bit together).  What both files share is in block_attention_common.hpp.
+// Element type T: float, or uint16_t carrying bfloat16, for q, k, v, out and the gradients.
+// Every element is widened to float32 when it is loaded (exact; widen() of a float is the float)
+// and a result is rounded once, to nearest even, when it is stored (narrow_to<T>()).  att[] and
+// the dropped attention stay float32 whatever T: the softmax Jacobian needs them at full
+// precision and they are only [E, H].  One body serves both types, so
+//
+//   bf16 kernel(x)  ==  round_to_bf16(float32 kernel(widen(x)))      bit for bit,
+//
+// forward and backward, which is what tests/test_gpu_block_attention_bf16.py asserts.
+//
+// bfloat16 loads are one 2-byte access per column.  A lane owns the columns lig + G * j whatever
+// the type: that map fixes the order in which head_dot() sums, so pairing two adjacent columns
+// into one 4-byte load would either change the sums (and break the equality above) or need a
+// shuffle per pair to hand the odd column to its owner.  A group's 2-byte loads are one
+// contiguous run of the row.  Measured at the TGN epoch's shapes (2 heads of 50 columns, 12 000
+// destinations, 120 000 edges; profiles/amp_bf16_epoch.json) the bfloat16 kernels take the
+// float32 kernels' time, 24 us forward and 40 us backward per launch: half the bytes bought
+// nothing there, so bytes are not what bounds them at that width and the load form is not either.
 #include "block_attention_common.hpp"
 
 namespace gf {
 namespace {
 
-template <int G, int NC>
+template <class T, int G, int NC>
 __global__ void block_attention_fwd(const int64_t* __restrict__ offsets, uint64_t items,
-                                    uint32_t H, uint32_t D, const float* __restrict__ q,
-                                    const float* __restrict__ k, const float* __restrict__ v,
-                                    float slope, float* __restrict__ out, float* att) {
+                                    uint32_t H, uint32_t D, const T* __restrict__ q,
+                                    const T* __restrict__ k, const T* __restrict__ v,
+                                    float slope, T* __restrict__ out, float* att) {
   const uint32_t lig = threadIdx.x & (G - 1);
   const uint64_t w = (static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / G;
   if (w >= items) return;                     // group-uniform
@@ -58,11 +72,11 @@ __global__ void block_attention_fwd(const int64_t* __restrict__ offsets, uint64_
   const uint32_t h = static_cast<uint32_t>(w - d * H);
   const int64_t b = offsets[d], e = offsets[d + 1];
   const uint64_t width = static_cast<uint64_t>(H) * D;
-  float* out_row = out + d * width + static_cast<uint64_t>(h) * D;
+  T* out_row = out + d * width + static_cast<uint64_t>(h) * D;
   if (e <= b) {                               // no in-edges: exactly 0
 #pragma unroll
     for (int j = 0; j < NC; ++j)
-      if (lig + G * j < D) out_row[lig + G * j] = 0.f;
+      if (lig + G * j < D) out_row[lig + G * j] = narrow_to<T>(0.f);
     return;
   }
   float qr[NC];
@@ -95,17 +109,17 @@ __global__ void block_attention_fwd(const int64_t* __restrict__ offsets, uint64_
     const int n = static_cast<int>(e - base < G ? e - base : G);
     for (int t = 0; t < n; ++t) {
       const float at = group_read<G>(a, t);
-      const float* vr = v + (base + t) * width + static_cast<uint64_t>(h) * D;
+      const T* vr = v + (base + t) * width + static_cast<uint64_t>(h) * D;
 #pragma unroll
       for (int j = 0; j < NC; ++j) {
         const uint32_t c = lig + G * j;
-        if (c < D) acc[j] += at * vr[c];
+        if (c < D) acc[j] += at * widen(vr[c]);
       }
     }
   }
 #pragma unroll
   for (int j = 0; j < NC; ++j)
-    if (lig + G * j < D) out_row[lig + G * j] = acc[j];
+    if (lig + G * j < D) out_row[lig + G * j] = narrow_to<T>(acc[j]);
 }
 
 // The forward with dropout: block_attention_fwd with the mask applied in pass 2b.  The lane
@@ -113,12 +127,11 @@ __global__ void block_attention_fwd(const int64_t* __restrict__ offsets, uint64_
 // negative), so still one value per edge goes round the group.  A kernel of its own rather than
 // a template flag on block_attention_fwd: a shared body changed the register allocation of the
 // NC > 1 instantiations without dropout.
-template <int G, int NC>
+template <class T, int G, int NC>
 __global__ void block_attention_dropout_fwd(
     const int64_t* __restrict__ offsets, uint64_t items, uint32_t H, uint32_t D,
-    const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
-    float slope, Dropout dr, float* __restrict__ out, float* att,
-    float* __restrict__ att_dropped) {
+    const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, float slope,
+    Dropout dr, T* __restrict__ out, float* att, float* __restrict__ att_dropped) {
   const uint32_t lig = threadIdx.x & (G - 1);
   const uint64_t w = (static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / G;
   if (w >= items) return;                     // group-uniform
@@ -126,11 +139,11 @@ __global__ void block_attention_dropout_fwd(
   const uint32_t h = static_cast<uint32_t>(w - d * H);
   const int64_t b = offsets[d], e = offsets[d + 1];
   const uint64_t width = static_cast<uint64_t>(H) * D;
-  float* out_row = out + d * width + static_cast<uint64_t>(h) * D;
+  T* out_row = out + d * width + static_cast<uint64_t>(h) * D;
   if (e <= b) {                               // no in-edges: exactly 0
 #pragma unroll
     for (int j = 0; j < NC; ++j)
-      if (lig + G * j < D) out_row[lig + G * j] = 0.f;
+      if (lig + G * j < D) out_row[lig + G * j] = narrow_to<T>(0.f);
     return;
   }
   float qr[NC];
@@ -165,17 +178,17 @@ __global__ void block_attention_dropout_fwd(
     for (int t = 0; t < n; ++t) {
       const float at = group_read<G>(a, t);
       if (at < 0.f) continue;                 // dropped: exactly 0, v not read (group-uniform)
-      const float* vr = v + (base + t) * width + static_cast<uint64_t>(h) * D;
+      const T* vr = v + (base + t) * width + static_cast<uint64_t>(h) * D;
 #pragma unroll
       for (int j = 0; j < NC; ++j) {
         const uint32_t c = lig + G * j;
-        if (c < D) acc[j] += at * vr[c];
+        if (c < D) acc[j] += at * widen(vr[c]);
       }
     }
   }
 #pragma unroll
   for (int j = 0; j < NC; ++j)
-    if (lig + G * j < D) out_row[lig + G * j] = acc[j];
+    if (lig + G * j < D) out_row[lig + G * j] = narrow_to<T>(acc[j]);
 }
 
 // ga[e,h] = sum_c gout[d,h,c] v[e,h,c]        gv[e,h,c] = a[e,h] gout[d,h,c]
@@ -184,13 +197,13 @@ __global__ void block_attention_dropout_fwd(
 // Sweep 1 forms sum a ga; sweep 2 recomputes ga (the same head_dot, so the same bits) instead
 // of parking it anywhere.  A null gq / gk / gv skips that output's work; z is recomputed by
 // the forward's own instruction sequence only when gq or gk is wanted.
-template <int G, int NC>
+template <class T, int G, int NC>
 __global__ void block_attention_bwd(const int64_t* __restrict__ offsets, uint64_t items,
-                                    uint32_t H, uint32_t D, const float* __restrict__ q,
-                                    const float* __restrict__ k, const float* __restrict__ v,
+                                    uint32_t H, uint32_t D, const T* __restrict__ q,
+                                    const T* __restrict__ k, const T* __restrict__ v,
                                     const float* __restrict__ att, float slope,
-                                    const float* __restrict__ gout, float* __restrict__ gq,
-                                    float* __restrict__ gk, float* __restrict__ gv) {
+                                    const T* __restrict__ gout, T* __restrict__ gq,
+                                    T* __restrict__ gk, T* __restrict__ gv) {
   const uint32_t lig = threadIdx.x & (G - 1);
   const uint64_t w = (static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / G;
   if (w >= items) return;
@@ -203,7 +216,7 @@ __global__ void block_attention_bwd(const int64_t* __restrict__ offsets, uint64_
     if (gq) {
 #pragma unroll
       for (int j = 0; j < NC; ++j)
-        if (lig + G * j < D) gq[d * width + head + lig + G * j] = 0.f;
+        if (lig + G * j < D) gq[d * width + head + lig + G * j] = narrow_to<T>(0.f);
     }
     return;
   }
@@ -216,7 +229,7 @@ __global__ void block_attention_bwd(const int64_t* __restrict__ offsets, uint64_
 #pragma unroll
       for (int j = 0; j < NC; ++j) {
         const uint32_t c = lig + G * j;
-        if (c < D) gv[i * width + head + c] = a * gr[j];
+        if (c < D) gv[i * width + head + c] = narrow_to<T>(a * gr[j]);
       }
     }
   }
@@ -231,7 +244,7 @@ __global__ void block_attention_bwd(const int64_t* __restrict__ offsets, uint64_
 #pragma unroll
   for (int j = 0; j < NC; ++j) acc[j] = 0.f;
   for (int64_t i = b; i < e; ++i) {
-    const float* kr = k + i * width + head;
+    const T* kr = k + i * width + head;
     const float ga = head_dot<G, NC>(gr, v + i * width + head, D, lig);
     const float z = head_dot<G, NC>(qr, kr, D, lig);
     const float gs = att[i * H + h] * (ga - dot);
@@ -240,15 +253,15 @@ __global__ void block_attention_bwd(const int64_t* __restrict__ offsets, uint64_
     for (int j = 0; j < NC; ++j) {
       const uint32_t c = lig + G * j;
       if (c < D) {
-        if (gk) gk[i * width + head + c] = gz * qr[j];
-        acc[j] += gz * kr[c];
+        if (gk) gk[i * width + head + c] = narrow_to<T>(gz * qr[j]);
+        acc[j] += gz * widen(kr[c]);
       }
     }
   }
   if (gq) {
 #pragma unroll
     for (int j = 0; j < NC; ++j)
-      if (lig + G * j < D) gq[d * width + head + lig + G * j] = acc[j];
+      if (lig + G * j < D) gq[d * width + head + lig + G * j] = narrow_to<T>(acc[j]);
   }
 }
 
@@ -258,12 +271,12 @@ __global__ void block_attention_bwd(const int64_t* __restrict__ offsets, uint64_
 // w for edge base + t, and both are handed round the group, so each sweep costs one Philox per
 // (edge, head) like the forward.  A dropped edge has ga = 0: its v row is not read, its gv row
 // is written as zeros, and it still takes its share -a dot of the softmax Jacobian.
-template <int G, int NC>
+template <class T, int G, int NC>
 __global__ void block_attention_dropout_bwd(
     const int64_t* __restrict__ offsets, uint64_t items, uint32_t H, uint32_t D,
-    const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
-    const float* __restrict__ att, float slope, Dropout dr, const float* __restrict__ gout,
-    float* __restrict__ gq, float* __restrict__ gk, float* __restrict__ gv) {
+    const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
+    const float* __restrict__ att, float slope, Dropout dr, const T* __restrict__ gout,
+    T* __restrict__ gq, T* __restrict__ gk, T* __restrict__ gv) {
   const uint32_t lig = threadIdx.x & (G - 1);
   const uint64_t w = (static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / G;
   if (w >= items) return;
@@ -276,7 +289,7 @@ __global__ void block_attention_dropout_bwd(
     if (gq) {
 #pragma unroll
       for (int j = 0; j < NC; ++j)
-        if (lig + G * j < D) gq[d * width + head + lig + G * j] = 0.f;
+        if (lig + G * j < D) gq[d * width + head + lig + G * j] = narrow_to<T>(0.f);
     }
     return;
   }
@@ -302,7 +315,7 @@ __global__ void block_attention_dropout_bwd(
         if (gv) {
 #pragma unroll
           for (int j = 0; j < NC; ++j)
-            if (lig + G * j < D) gv[i * width + head + lig + G * j] = 0.f;
+            if (lig + G * j < D) gv[i * width + head + lig + G * j] = narrow_to<T>(0.f);
         }
         continue;
       }
@@ -311,7 +324,7 @@ __global__ void block_attention_dropout_bwd(
 #pragma unroll
         for (int j = 0; j < NC; ++j) {
           const uint32_t c = lig + G * j;
-          if (c < D) gv[i * width + head + c] = aw * gr[j];
+          if (c < D) gv[i * width + head + c] = narrow_to<T>(aw * gr[j]);
         }
       }
       if (chain) dot += at * (wt * head_dot<G, NC>(gr, v + i * width + head, D, lig));
@@ -336,7 +349,7 @@ __global__ void block_attention_dropout_bwd(
       const float at = group_read<G>(a, t);
       const float wt = group_read<G>(wm, t);
       const int64_t i = base + t;
-      const float* kr = k + i * width + head;
+      const T* kr = k + i * width + head;
       float ga = 0.f;
       if (wt != 0.f) ga = wt * head_dot<G, NC>(gr, v + i * width + head, D, lig);
       const float z = head_dot<G, NC>(qr, kr, D, lig);
@@ -346,8 +359,8 @@ __global__ void block_attention_dropout_bwd(
       for (int j = 0; j < NC; ++j) {
         const uint32_t c = lig + G * j;
         if (c < D) {
-          if (gk) gk[i * width + head + c] = gz * qr[j];
-          acc[j] += gz * kr[c];
+          if (gk) gk[i * width + head + c] = narrow_to<T>(gz * qr[j]);
+          acc[j] += gz * widen(kr[c]);
         }
       }
     }
@@ -355,98 +368,72 @@ __global__ void block_attention_dropout_bwd(
   if (gq) {
 #pragma unroll
     for (int j = 0; j < NC; ++j)
-      if (lig + G * j < D) gq[d * width + head + lig + G * j] = acc[j];
+      if (lig + G * j < D) gq[d * width + head + lig + G * j] = narrow_to<T>(acc[j]);
   }
 }
 
-template <int G, int NC>
-void launch_fwd(const Shape& s, const float* q, const float* k, const float* v, float slope,
-                float* out, float* att, hipStream_t stream) {
-  const uint64_t threads = s.items * G;
-  block_attention_fwd<G, NC><<<dim3(static_cast<unsigned>((threads + kThreads - 1) / kThreads)),
-                               dim3(kThreads), 0, stream>>>(s.offsets, s.items, s.H, s.D, q, k, v,
-                                                            slope, out, att);
-}
-
-template <int G, int NC>
-void launch_bwd(const Shape& s, const float* q, const float* k, const float* v, const float* att,
-                float slope, const float* gout, float* gq, float* gk, float* gv,
-                hipStream_t stream) {
-  const uint64_t threads = s.items * G;
-  block_attention_bwd<G, NC><<<dim3(static_cast<unsigned>((threads + kThreads - 1) / kThreads)),
-                               dim3(kThreads), 0, stream>>>(s.offsets, s.items, s.H, s.D, q, k, v,
-                                                            att, slope, gout, gq, gk, gv);
-}
-
-template <int G, int NC>
-void launch_dropout_fwd(const Shape& s, const float* q, const float* k, const float* v,
-                        float slope, const Dropout& dr, float* out, float* att,
-                        float* att_dropped, hipStream_t stream) {
-  const uint64_t threads = s.items * G;
-  block_attention_dropout_fwd<G, NC>
-      <<<dim3(static_cast<unsigned>((threads + kThreads - 1) / kThreads)), dim3(kThreads), 0,
-         stream>>>(s.offsets, s.items, s.H, s.D, q, k, v, slope, dr, out, att, att_dropped);
-}
-
-template <int G, int NC>
-void launch_dropout_bwd(const Shape& s, const float* q, const float* k, const float* v,
-                        const float* att, float slope, const Dropout& dr, const float* gout,
-                        float* gq, float* gk, float* gv, hipStream_t stream) {
-  const uint64_t threads = s.items * G;
-  block_attention_dropout_bwd<G, NC>
-      <<<dim3(static_cast<unsigned>((threads + kThreads - 1) / kThreads)), dim3(kThreads), 0,
-         stream>>>(s.offsets, s.items, s.H, s.D, q, k, v, att, slope, dr, gout, gq, gk, gv);
-}
-
+template <class T>
 struct Fwd {
-  Shape s; const float *q, *k, *v; float slope; float *out, *att; hipStream_t stream;
+  Shape s; const T *q, *k, *v; float slope; T* out; float* att; hipStream_t stream;
   template <int G, int NC> void operator()() {
-    launch_fwd<G, NC>(s, q, k, v, slope, out, att, stream);
+    block_attention_fwd<T, G, NC><<<dim3(grid_of(s, G)), dim3(kThreads), 0, stream>>>(
+        s.offsets, s.items, s.H, s.D, q, k, v, slope, out, att);
   }
 };
+template <class T>
 struct Bwd {
-  Shape s; const float *q, *k, *v, *att; float slope; const float* gout; float *gq, *gk, *gv;
+  Shape s; const T *q, *k, *v; const float* att; float slope; const T* gout; T *gq, *gk, *gv;
   hipStream_t stream;
   template <int G, int NC> void operator()() {
-    launch_bwd<G, NC>(s, q, k, v, att, slope, gout, gq, gk, gv, stream);
+    block_attention_bwd<T, G, NC><<<dim3(grid_of(s, G)), dim3(kThreads), 0, stream>>>(
+        s.offsets, s.items, s.H, s.D, q, k, v, att, slope, gout, gq, gk, gv);
   }
 };
-
+template <class T>
 struct DropoutFwd {
-  Shape s; const float *q, *k, *v; float slope; Dropout dr; float *out, *att, *att_dropped;
+  Shape s; const T *q, *k, *v; float slope; Dropout dr; T* out; float *att, *att_dropped;
   hipStream_t stream;
   template <int G, int NC> void operator()() {
-    launch_dropout_fwd<G, NC>(s, q, k, v, slope, dr, out, att, att_dropped, stream);
+    block_attention_dropout_fwd<T, G, NC><<<dim3(grid_of(s, G)), dim3(kThreads), 0, stream>>>(
+        s.offsets, s.items, s.H, s.D, q, k, v, slope, dr, out, att, att_dropped);
   }
 };
+template <class T>
 struct DropoutBwd {
-  Shape s; const float *q, *k, *v, *att; float slope; Dropout dr; const float* gout;
-  float *gq, *gk, *gv; hipStream_t stream;
+  Shape s; const T *q, *k, *v; const float* att; float slope; Dropout dr; const T* gout;
+  T *gq, *gk, *gv; hipStream_t stream;
   template <int G, int NC> void operator()() {
-    launch_dropout_bwd<G, NC>(s, q, k, v, att, slope, dr, gout, gq, gk, gv, stream);
+    block_attention_dropout_bwd<T, G, NC><<<dim3(grid_of(s, G)), dim3(kThreads), 0, stream>>>(
+        s.offsets, s.items, s.H, s.D, q, k, v, att, slope, dr, gout, gq, gk, gv);
   }
 };
 
-}  // namespace
-
-void block_attention_forward(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
-                             size_t heads, size_t head_dim, const float* d_q, const float* d_k,
-                             const float* d_v, float negative_slope, float* d_out, float* d_att,
-                             int device, hipStream_t stream) {
+// The host side of the entry points below: the checks once, for both element types and with or
+// without dropout (`dr` null: without).  The dropout entry points check p before they call in,
+// so every message keeps its place in the order.
+template <class T>
+void forward(const int64_t* d_offsets, size_t num_dst, size_t num_edges, size_t heads,
+             size_t head_dim, const T* d_q, const T* d_k, const T* d_v, float negative_slope,
+             const Dropout* dr, T* d_out, float* d_att, float* d_att_dropped, int device,
+             hipStream_t stream) {
   const Shape s = checked_shape(d_offsets, num_dst, heads, head_dim);
   if (num_dst == 0) return;
   GF_REQUIRE(d_q && d_out, "block_attention: null q or out");
   GF_REQUIRE(num_edges == 0 || (d_k && d_v && d_att), "block_attention: null k, v or att");
   DeviceGuard dg(device);
-  dispatch(s.D, Fwd{s, d_q, d_k, d_v, negative_slope, d_out, d_att, stream});
+  if (dr)
+    dispatch(s.D, DropoutFwd<T>{s, d_q, d_k, d_v, negative_slope, *dr, d_out, d_att,
+                                d_att_dropped, stream});
+  else
+    dispatch(s.D, Fwd<T>{s, d_q, d_k, d_v, negative_slope, d_out, d_att, stream});
   GF_HIP(hipGetLastError());
 }
 
-void block_attention_backward(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
-                              size_t heads, size_t head_dim, const float* d_q, const float* d_k,
-                              const float* d_v, const float* d_att, float negative_slope,
-                              const float* d_grad_out, float* d_grad_q, float* d_grad_k,
-                              float* d_grad_v, int device, hipStream_t stream) {
+template <class T>
+void backward(const int64_t* d_offsets, size_t num_dst, size_t num_edges, size_t heads,
+              size_t head_dim, const T* d_q, const T* d_k, const T* d_v, const float* d_att,
+              float negative_slope, const Dropout* dr, const T* d_grad_out, T* d_grad_q,
+              T* d_grad_k, T* d_grad_v, int device, hipStream_t stream) {
   const Shape s = checked_shape(d_offsets, num_dst, heads, head_dim);
   if (num_dst == 0 || (!d_grad_q && !d_grad_k && !d_grad_v)) return;
   GF_REQUIRE(d_grad_out != nullptr, "block_attention backward: null gradient");
@@ -455,9 +442,32 @@ void block_attention_backward(const int64_t* d_offsets, size_t num_dst, size_t n
              "block_attention backward: grad_q / grad_k need q and k");
   if (num_edges == 0 && !d_grad_q) return;
   DeviceGuard dg(device);
-  dispatch(s.D, Bwd{s, d_q, d_k, d_v, d_att, negative_slope, d_grad_out, d_grad_q, d_grad_k,
-                    d_grad_v, stream});
+  if (dr)
+    dispatch(s.D, DropoutBwd<T>{s, d_q, d_k, d_v, d_att, negative_slope, *dr, d_grad_out,
+                                d_grad_q, d_grad_k, d_grad_v, stream});
+  else
+    dispatch(s.D, Bwd<T>{s, d_q, d_k, d_v, d_att, negative_slope, d_grad_out, d_grad_q, d_grad_k,
+                         d_grad_v, stream});
   GF_HIP(hipGetLastError());
+}
+
+}  // namespace
+
+void block_attention_forward(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                             size_t heads, size_t head_dim, const float* d_q, const float* d_k,
+                             const float* d_v, float negative_slope, float* d_out, float* d_att,
+                             int device, hipStream_t stream) {
+  forward(d_offsets, num_dst, num_edges, heads, head_dim, d_q, d_k, d_v, negative_slope, nullptr,
+          d_out, d_att, nullptr, device, stream);
+}
+
+void block_attention_backward(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                              size_t heads, size_t head_dim, const float* d_q, const float* d_k,
+                              const float* d_v, const float* d_att, float negative_slope,
+                              const float* d_grad_out, float* d_grad_q, float* d_grad_k,
+                              float* d_grad_v, int device, hipStream_t stream) {
+  backward(d_offsets, num_dst, num_edges, heads, head_dim, d_q, d_k, d_v, d_att, negative_slope,
+           nullptr, d_grad_out, d_grad_q, d_grad_k, d_grad_v, device, stream);
 }
 
 void block_attention_dropout_forward(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
@@ -466,14 +476,8 @@ void block_attention_dropout_forward(const int64_t* d_offsets, size_t num_dst, s
                                      float p, uint64_t seed, float* d_out, float* d_att,
                                      float* d_att_dropped, int device, hipStream_t stream) {
   const Dropout dr = checked_dropout(p, seed);
-  const Shape s = checked_shape(d_offsets, num_dst, heads, head_dim);
-  if (num_dst == 0) return;
-  GF_REQUIRE(d_q && d_out, "block_attention: null q or out");
-  GF_REQUIRE(num_edges == 0 || (d_k && d_v && d_att), "block_attention: null k, v or att");
-  DeviceGuard dg(device);
-  dispatch(s.D, DropoutFwd{s, d_q, d_k, d_v, negative_slope, dr, d_out, d_att, d_att_dropped,
-                           stream});
-  GF_HIP(hipGetLastError());
+  forward(d_offsets, num_dst, num_edges, heads, head_dim, d_q, d_k, d_v, negative_slope, &dr,
+          d_out, d_att, d_att_dropped, device, stream);
 }
 
 void block_attention_dropout_backward(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
@@ -483,17 +487,50 @@ void block_attention_dropout_backward(const int64_t* d_offsets, size_t num_dst, 
                                       const float* d_grad_out, float* d_grad_q, float* d_grad_k,
                                       float* d_grad_v, int device, hipStream_t stream) {
   const Dropout dr = checked_dropout(p, seed);
-  const Shape s = checked_shape(d_offsets, num_dst, heads, head_dim);
-  if (num_dst == 0 || (!d_grad_q && !d_grad_k && !d_grad_v)) return;
-  GF_REQUIRE(d_grad_out != nullptr, "block_attention backward: null gradient");
-  GF_REQUIRE(num_edges == 0 || (d_att && d_v), "block_attention backward: null att or v");
-  GF_REQUIRE(num_edges == 0 || (!d_grad_q && !d_grad_k) || (d_q && d_k),
-             "block_attention backward: grad_q / grad_k need q and k");
-  if (num_edges == 0 && !d_grad_q) return;
-  DeviceGuard dg(device);
-  dispatch(s.D, DropoutBwd{s, d_q, d_k, d_v, d_att, negative_slope, dr, d_grad_out, d_grad_q,
-                           d_grad_k, d_grad_v, stream});
-  GF_HIP(hipGetLastError());
+  backward(d_offsets, num_dst, num_edges, heads, head_dim, d_q, d_k, d_v, d_att, negative_slope,
+           &dr, d_grad_out, d_grad_q, d_grad_k, d_grad_v, device, stream);
+}
+
+void block_attention_bf16_forward(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                                  size_t heads, size_t head_dim, const uint16_t* d_q,
+                                  const uint16_t* d_k, const uint16_t* d_v, float negative_slope,
+                                  uint16_t* d_out, float* d_att, int device, hipStream_t stream) {
+  forward(d_offsets, num_dst, num_edges, heads, head_dim, d_q, d_k, d_v, negative_slope, nullptr,
+          d_out, d_att, nullptr, device, stream);
+}
+
+void block_attention_bf16_backward(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
+                                   size_t heads, size_t head_dim, const uint16_t* d_q,
+                                   const uint16_t* d_k, const uint16_t* d_v, const float* d_att,
+                                   float negative_slope, const uint16_t* d_grad_out,
+                                   uint16_t* d_grad_q, uint16_t* d_grad_k, uint16_t* d_grad_v,
+                                   int device, hipStream_t stream) {
+  backward(d_offsets, num_dst, num_edges, heads, head_dim, d_q, d_k, d_v, d_att, negative_slope,
+           nullptr, d_grad_out, d_grad_q, d_grad_k, d_grad_v, device, stream);
+}
+
+void block_attention_dropout_bf16_forward(const int64_t* d_offsets, size_t num_dst,
+                                          size_t num_edges, size_t heads, size_t head_dim,
+                                          const uint16_t* d_q, const uint16_t* d_k,
+                                          const uint16_t* d_v, float negative_slope, float p,
+                                          uint64_t seed, uint16_t* d_out, float* d_att,
+                                          float* d_att_dropped, int device, hipStream_t stream) {
+  const Dropout dr = checked_dropout(p, seed);
+  forward(d_offsets, num_dst, num_edges, heads, head_dim, d_q, d_k, d_v, negative_slope, &dr,
+          d_out, d_att, d_att_dropped, device, stream);
+}
+
+void block_attention_dropout_bf16_backward(const int64_t* d_offsets, size_t num_dst,
+                                           size_t num_edges, size_t heads, size_t head_dim,
+                                           const uint16_t* d_q, const uint16_t* d_k,
+                                           const uint16_t* d_v, const float* d_att,
+                                           float negative_slope, float p, uint64_t seed,
+                                           const uint16_t* d_grad_out, uint16_t* d_grad_q,
+                                           uint16_t* d_grad_k, uint16_t* d_grad_v, int device,
+                                           hipStream_t stream) {
+  const Dropout dr = checked_dropout(p, seed);
+  backward(d_offsets, num_dst, num_edges, heads, head_dim, d_q, d_k, d_v, d_att, negative_slope,
+           &dr, d_grad_out, d_grad_q, d_grad_k, d_grad_v, device, stream);
 }
 
 }  // namespace gf

@@ -1,9 +1,9 @@
-// What the float32 kernels of block_attention.hip and the bfloat16 kernels of
-// block_attention_bf16.hip share: the lane-group helpers, head_dot() -- the only place a score is
-// computed, whatever the element type --, the dropout mask, the G / NC dispatch and the argument
-// checks.  Everything sits in an unnamed namespace: each of the two translation units gets its
-// own copy, and the float32 kernels compile to the code they had when these lines were part of
-// block_attention.hip.
+// What the kernels of block_attention.hip and block_gat.hip share, whatever their element type:
+// the lane-group helpers, head_dot() -- the only place a dot over a head's columns is computed
+// --, the dropout mask (layer_epilogue.hip draws it from here too) and the G / NC dispatch; and
+// block_attention's own argument checks.  Everything sits in an unnamed namespace: each
+// translation unit gets its own copy, and the kernels compile to the code they had when these
+// lines were part of their files.
 #pragma once
 
 #include "bf16.hpp"
@@ -24,6 +24,13 @@ template <int G>
 __device__ inline float group_sum(float v) {
 #pragma unroll
   for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+template <int G>
+__device__ inline float group_max(float v) {
+#pragma unroll
+  for (int off = G / 2; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
   return v;
 }
 

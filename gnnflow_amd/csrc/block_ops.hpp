@@ -1,7 +1,6 @@
-// Segment operations on a sampled block (block_ops.hip, block_attention.hip, block_gat.hip and their
-// bfloat16 siblings block_ops_bf16.hip, block_attention_bf16.hip, block_gat_bf16.hip), the fused time
-// encoding in front of them (time_encode.hip) and the fused edge score behind them
-// (edge_score.hip), and the metrics of the scores it leaves (link_metrics.hip), and the GRU gates
+// Segment operations on a sampled block (block_ops.hip, block_attention.hip, block_gat.hip, each
+// for float32 and for bfloat16 rows), the fused time encoding in front of them (time_encode.hip)
+// and the fused edge score behind them (edge_score.hip), and the metrics of the scores it leaves (link_metrics.hip), and the GRU gates
 // of the memory updater (gru_cell.hip): the entry points other translation units call.
 #pragma once
 
@@ -31,7 +30,7 @@ void segment_max_backward(size_t num_dst, const int64_t* d_col, size_t dim,
                           const float* d_grad_out, const int64_t* d_arg, float* d_grad_src,
                           size_t num_src, int device, hipStream_t stream);
 
-// block_ops_bf16.hip: the reductions above for bfloat16 src, out, grad_out and grad_src
+// block_ops.hip again: the reductions above for bfloat16 src, out, grad_out and grad_src
 // (uint16_t; edge weights, their gradient and arg stay as they are): widened on load, the float32
 // kernels' arithmetic, one rounding to nearest even on store.  The same checks.  d_scratch is a
 // caller-owned float32 [num_src, dim] the gradient of the source rows is accumulated in when d_col
@@ -85,7 +84,7 @@ void block_attention_dropout_backward(const int64_t* d_offsets, size_t num_dst, 
                                       const float* d_grad_out, float* d_grad_q, float* d_grad_k,
                                       float* d_grad_v, int device, hipStream_t stream);
 
-// block_attention_bf16.hip: the four entry points above for bfloat16 q, k, v, out and gradients
+// block_attention.hip again: the four entry points above for bfloat16 q, k, v, out and gradients
 // (uint16_t; d_att and d_att_dropped stay float32): widened on load, the float32 kernels'
 // arithmetic, one rounding to nearest even on store.  The same checks.
 void block_attention_bf16_forward(const int64_t* d_offsets, size_t num_dst, size_t num_edges,
@@ -132,7 +131,7 @@ void block_gat_backward(const int64_t* d_offsets, size_t num_dst, size_t num_edg
                         uint64_t seed, const float* d_grad_out, float* d_grad_feat,
                         float* d_grad_el, float* d_grad_er, int device, hipStream_t stream);
 
-// block_gat_bf16.hip: the two entry points above for bfloat16 feat, out, grad_out and grad_feat
+// block_gat.hip again: the two entry points above for bfloat16 feat, out, grad_out and grad_feat
 // (el, er, att, the dropped attention, grad_el and grad_er float32).  d_out_f32 [num_dst, heads,
 // head_dim] receives the forward's sums before they are rounded: it is the `out` the backward
 // reads (null in the forward: not written).  d_scratch: float32 [num_src, heads, head_dim] that

@@ -31,12 +31,12 @@
 // of the inputs and bit-reproducible.  Without gw and gbias there are no partials and no second
 // launch.
 //
-// bfloat16 (the *_bf16 kernels; bf16.hpp): src and dst rows, and their gradients, may be bfloat16
-// while w, bias, g, out, gw and gbias stay float32.  Each element is widened (exact) where the
-// float32 kernel loads it, the arithmetic and its order are the float32 kernels' own, and gsrc
-// and gdst are rounded once, to nearest even, when they are stored; the partials and the finish
-// kernel are shared.  The forward's 4-column chunk of a bfloat16 row is one 8-byte access when
-// D % 4 == 0, src and dst are 8-byte aligned and w is 16-byte aligned.
+// bfloat16 (T = uint16_t; bf16.hpp): src and dst rows, and their gradients, may be bfloat16
+// while w, bias, g, out, gw and gbias stay float32.  Each element is widened (exact) when it is
+// loaded, one kernel body does the arithmetic for both types, and gsrc and gdst are rounded
+// once, to nearest even, when they are stored; the partials and the finish kernel know no T.
+// The forward's 4-column chunk of a bfloat16 row is one 8-byte access when D % 4 == 0, src and
+// dst are 8-byte aligned and w is 16-byte aligned.
 #include "bf16.hpp"
 #include "block_ops.hpp"
 #include "common.hpp"
@@ -56,61 +56,44 @@ constexpr size_t kMinRowsPerGroup = 8;
 __device__ __forceinline__ float es_pre(float s, float p) { return s + p; }
 __device__ __forceinline__ float es_relu(float x) { return x > 0.f ? x : 0.f; }
 
-template <bool VEC>
+// Columns c .. c + 3 of a row in one access, 16 bytes of float32 or 8 bytes of bfloat16, and
+// column I of what was loaded.  A bfloat16 column is widened where it is used, not where it is
+// loaded: the compiler schedules the two differently.
+__device__ __forceinline__ float4 load4(const float* p) {
+  return *reinterpret_cast<const float4*>(p);
+}
+__device__ __forceinline__ uint2 load4(const uint16_t* p) {
+  return *reinterpret_cast<const uint2*>(p);
+}
+template <int I>
+__device__ __forceinline__ float col(const float4& v) {
+  return I == 0 ? v.x : I == 1 ? v.y : I == 2 ? v.z : v.w;
+}
+template <int I>
+__device__ __forceinline__ float col(const uint2& u) {
+  const uint32_t pair = I < 2 ? u.x : u.y;
+  return __uint_as_float(I % 2 ? pair & 0xffff0000u : pair << 16);
+}
+
+template <class T, bool VEC>
 __global__ void __launch_bounds__(kThreads)
-edge_score_fwd(const float* __restrict__ src, const float* __restrict__ dst,
+edge_score_fwd(const T* __restrict__ src, const T* __restrict__ dst,
                const float* __restrict__ w, const float* __restrict__ bias, uint32_t B, uint32_t M,
                uint32_t D, float* __restrict__ out) {
   const uint32_t lane = threadIdx.x % kLanes;
   const uint32_t j = blockIdx.x * static_cast<uint32_t>(kRowsPerBlock) + threadIdx.x / kLanes;
   float acc = 0.f;
   if (j < M) {
-    const float* s = src + static_cast<uint64_t>(j % B) * D;
-    const float* p = dst + static_cast<uint64_t>(j) * D;
+    const T* s = src + static_cast<uint64_t>(j % B) * D;
+    const T* p = dst + static_cast<uint64_t>(j) * D;
     for (uint32_t c = lane * 4; c < D; c += kLanes * 4) {
       if (VEC) {
-        const float4 sv = *reinterpret_cast<const float4*>(s + c);
-        const float4 pv = *reinterpret_cast<const float4*>(p + c);
-        const float4 wv = *reinterpret_cast<const float4*>(w + c);
-        acc += wv.x * es_relu(es_pre(sv.x, pv.x));
-        acc += wv.y * es_relu(es_pre(sv.y, pv.y));
-        acc += wv.z * es_relu(es_pre(sv.z, pv.z));
-        acc += wv.w * es_relu(es_pre(sv.w, pv.w));
-      } else {
-        const uint32_t end = c + 4 < D ? c + 4 : D;
-        for (uint32_t d = c; d < end; ++d) acc += w[d] * es_relu(es_pre(s[d], p[d]));
-      }
-    }
-  }
-  // every lane of the wave takes part; rows past M carry zeros
-#pragma unroll
-  for (int off = kLanes / 2; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, kLanes);
-  if (j < M && lane == 0) out[j] = acc + bias[0];
-}
-
-// edge_score_fwd on bfloat16 src and dst rows
-template <bool VEC>
-__global__ void __launch_bounds__(kThreads)
-edge_score_bf16_fwd(const uint16_t* __restrict__ src, const uint16_t* __restrict__ dst,
-                    const float* __restrict__ w, const float* __restrict__ bias, uint32_t B,
-                    uint32_t M, uint32_t D, float* __restrict__ out) {
-  const uint32_t lane = threadIdx.x % kLanes;
-  const uint32_t j = blockIdx.x * static_cast<uint32_t>(kRowsPerBlock) + threadIdx.x / kLanes;
-  float acc = 0.f;
-  if (j < M) {
-    const uint16_t* s = src + static_cast<uint64_t>(j % B) * D;
-    const uint16_t* p = dst + static_cast<uint64_t>(j) * D;
-    for (uint32_t c = lane * 4; c < D; c += kLanes * 4) {
-      if (VEC) {
-        const uint2 sv = *reinterpret_cast<const uint2*>(s + c);
-        const uint2 pv = *reinterpret_cast<const uint2*>(p + c);
-        const float4 wv = *reinterpret_cast<const float4*>(w + c);
-        acc += wv.x * es_relu(es_pre(__uint_as_float(sv.x << 16), __uint_as_float(pv.x << 16)));
-        acc += wv.y * es_relu(es_pre(__uint_as_float(sv.x & 0xffff0000u),
-                                     __uint_as_float(pv.x & 0xffff0000u)));
-        acc += wv.z * es_relu(es_pre(__uint_as_float(sv.y << 16), __uint_as_float(pv.y << 16)));
-        acc += wv.w * es_relu(es_pre(__uint_as_float(sv.y & 0xffff0000u),
-                                     __uint_as_float(pv.y & 0xffff0000u)));
+        const auto sv = load4(s + c), pv = load4(p + c);
+        const float4 wv = load4(w + c);
+        acc += wv.x * es_relu(es_pre(col<0>(sv), col<0>(pv)));
+        acc += wv.y * es_relu(es_pre(col<1>(sv), col<1>(pv)));
+        acc += wv.z * es_relu(es_pre(col<2>(sv), col<2>(pv)));
+        acc += wv.w * es_relu(es_pre(col<3>(sv), col<3>(pv)));
       } else {
         const uint32_t end = c + 4 < D ? c + 4 : D;
         for (uint32_t d = c; d < end; ++d)
@@ -126,62 +109,12 @@ edge_score_bf16_fwd(const uint16_t* __restrict__ src, const uint16_t* __restrict
 
 // partials[p, c]: c < D -> gw[c]'s share of workgroup p's rows, c == D -> gbias's.  A null gsrc,
 // gdst or partials is skipped (uniform over the grid).
-template <int CX>
+template <class T, int CX>
 __global__ void __launch_bounds__(kThreads)
-edge_score_bwd(const float* __restrict__ src, const float* __restrict__ dst,
+edge_score_bwd(const T* __restrict__ src, const T* __restrict__ dst,
                const float* __restrict__ w, const float* __restrict__ g, uint32_t B, uint32_t r,
-               uint32_t D, uint32_t rows_per_wg, float* __restrict__ gsrc,
-               float* __restrict__ gdst, float* __restrict__ partials) {
-  constexpr int RY = kThreads / CX;
-  __shared__ float sp[RY][CX];
-  const uint32_t cx = threadIdx.x % CX, ry = threadIdx.x / CX;
-  const uint32_t i0 = blockIdx.x * rows_per_wg;
-  const uint32_t i1 = B - i0 < rows_per_wg ? B : i0 + rows_per_wg;      // i0 < B
-  const uint32_t width = D + 1;
-  for (uint32_t c0 = 0; c0 < width; c0 += CX) {      // uniform over the workgroup
-    const uint32_t c = c0 + cx;
-    float acc = 0.f;
-    if (c < D) {
-      const float wc = w[c];
-      for (uint32_t i = i0 + ry; i < i1; i += RY) {
-        const float s = src[static_cast<uint64_t>(i) * D + c];
-        float gs = 0.f;
-        for (uint32_t k = 0; k < r; ++k) {
-          const uint64_t j = i + static_cast<uint64_t>(k) * B;      // < r * B
-          const float gj = g[j];
-          const float x = es_pre(s, dst[j * D + c]);
-          const float gd = x > 0.f ? gj * wc : 0.f;
-          if (gdst) gdst[j * D + c] = gd;
-          gs += gd;
-          acc += gj * es_relu(x);
-        }
-        if (gsrc) gsrc[static_cast<uint64_t>(i) * D + c] = gs;
-      }
-    } else if (c == D && partials) {
-      for (uint32_t i = i0 + ry; i < i1; i += RY)
-        for (uint32_t k = 0; k < r; ++k) acc += g[i + static_cast<uint64_t>(k) * B];
-    }
-    if (partials) {
-      sp[ry][cx] = acc;
-      __syncthreads();
-      if (ry == 0 && c < width) {
-        float t = sp[0][cx];
-#pragma unroll
-        for (int q = 1; q < RY; ++q) t += sp[q][cx];
-        partials[static_cast<uint64_t>(blockIdx.x) * width + c] = t;
-      }
-      __syncthreads();
-    }
-  }
-}
-
-// edge_score_bwd on bfloat16 src and dst rows, gsrc and gdst narrowed on store
-template <int CX>
-__global__ void __launch_bounds__(kThreads)
-edge_score_bf16_bwd(const uint16_t* __restrict__ src, const uint16_t* __restrict__ dst,
-               const float* __restrict__ w, const float* __restrict__ g, uint32_t B, uint32_t r,
-               uint32_t D, uint32_t rows_per_wg, uint16_t* __restrict__ gsrc,
-               uint16_t* __restrict__ gdst, float* __restrict__ partials) {
+               uint32_t D, uint32_t rows_per_wg, T* __restrict__ gsrc, T* __restrict__ gdst,
+               float* __restrict__ partials) {
   constexpr int RY = kThreads / CX;
   __shared__ float sp[RY][CX];
   const uint32_t cx = threadIdx.x % CX, ry = threadIdx.x / CX;
@@ -201,11 +134,11 @@ edge_score_bf16_bwd(const uint16_t* __restrict__ src, const uint16_t* __restrict
           const float gj = g[j];
           const float x = es_pre(s, widen(dst[j * D + c]));
           const float gd = x > 0.f ? gj * wc : 0.f;
-          if (gdst) gdst[j * D + c] = narrow(gd);
+          if (gdst) gdst[j * D + c] = narrow_to<T>(gd);
           gs += gd;
           acc += gj * es_relu(x);
         }
-        if (gsrc) gsrc[static_cast<uint64_t>(i) * D + c] = narrow(gs);
+        if (gsrc) gsrc[static_cast<uint64_t>(i) * D + c] = narrow_to<T>(gs);
       }
     } else if (c == D && partials) {
       for (uint32_t i = i0 + ry; i < i1; i += RY)
@@ -248,7 +181,9 @@ edge_score_bwd_finish(const float* __restrict__ partials, uint32_t rows, uint32_
   }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// can four elements at p be one access?  16-byte aligned float32, 8-byte aligned bfloat16
+template <class T>
+bool aligned4(const T* p) { return (reinterpret_cast<uintptr_t>(p) & (4 * sizeof(T) - 1)) == 0; }
 
 size_t partial_rows(size_t num_src) {
   const size_t groups = (num_src + kMinRowsPerGroup - 1) / kMinRowsPerGroup;
@@ -266,6 +201,57 @@ bool check_shape(const char* what, size_t num_src, size_t num_dst, size_t dim) {
   return true;
 }
 
+template <class T>
+void forward(const T* d_src, const T* d_dst, const float* d_w, const float* d_bias, size_t num_src,
+             size_t num_dst, size_t dim, float* d_out, int device, hipStream_t stream) {
+  if (!check_shape("edge_score", num_src, num_dst, dim)) return;
+  GF_REQUIRE(d_src && d_dst && d_w && d_bias && d_out,
+             "edge_score: null src, dst, weight, bias or out");
+  const bool vec = dim % 4 == 0 && aligned4(d_src) && aligned4(d_dst) && aligned4(d_w);
+  const uint32_t B = static_cast<uint32_t>(num_src), M = static_cast<uint32_t>(num_dst),
+                 D = static_cast<uint32_t>(dim);
+  const dim3 grid((M + kRowsPerBlock - 1) / kRowsPerBlock), block(kThreads);
+  DeviceGuard dg(device);
+  if (vec)
+    edge_score_fwd<T, true><<<grid, block, 0, stream>>>(d_src, d_dst, d_w, d_bias, B, M, D, d_out);
+  else
+    edge_score_fwd<T, false><<<grid, block, 0, stream>>>(d_src, d_dst, d_w, d_bias, B, M, D, d_out);
+  GF_HIP(hipGetLastError());
+}
+
+template <class T>
+void backward(const T* d_src, const T* d_dst, const float* d_w, size_t num_src, size_t num_dst,
+              size_t dim, const float* d_grad_out, float* d_partials, size_t partial_rows_given,
+              T* d_grad_src, T* d_grad_dst, float* d_grad_w, float* d_grad_bias, int device,
+              hipStream_t stream) {
+  if (!check_shape("edge_score backward", num_src, num_dst, dim)) return;
+  GF_REQUIRE(d_src && d_dst && d_w, "edge_score backward: null src, dst or weight");
+  GF_REQUIRE(d_grad_out != nullptr, "edge_score backward: null gradient");
+  const bool reduce = d_grad_w || d_grad_bias;
+  if (!reduce && !d_grad_src && !d_grad_dst) return;
+  const size_t want = partial_rows(num_src);
+  GF_REQUIRE(!reduce || (d_partials != nullptr && partial_rows_given >= want),
+             "edge_score backward: partials buffer missing or smaller than "
+             "gf_edge_score_backward_partial_rows() asks for");
+  const uint32_t B = static_cast<uint32_t>(num_src), D = static_cast<uint32_t>(dim);
+  const uint32_t r = static_cast<uint32_t>(num_dst / num_src);
+  const uint32_t rows_per_wg = static_cast<uint32_t>((num_src + want - 1) / want);
+  const uint32_t groups = (B + rows_per_wg - 1) / rows_per_wg;      // <= want
+  float* partials = reduce ? d_partials : nullptr;
+  DeviceGuard dg(device);
+  if (D + 1 <= 32)
+    edge_score_bwd<T, 32><<<dim3(groups), dim3(kThreads), 0, stream>>>(
+        d_src, d_dst, d_w, d_grad_out, B, r, D, rows_per_wg, d_grad_src, d_grad_dst, partials);
+  else
+    edge_score_bwd<T, 64><<<dim3(groups), dim3(kThreads), 0, stream>>>(
+        d_src, d_dst, d_w, d_grad_out, B, r, D, rows_per_wg, d_grad_src, d_grad_dst, partials);
+  GF_HIP(hipGetLastError());
+  if (!reduce) return;
+  edge_score_bwd_finish<<<dim3((D + 1 + 31) / 32), dim3(kFinishThreads), 0, stream>>>(
+      d_partials, groups, D, d_grad_w, d_grad_bias);
+  GF_HIP(hipGetLastError());
+}
+
 }  // namespace
 
 size_t edge_score_backward_partial_rows(size_t num_src) { return partial_rows(num_src); }
@@ -273,72 +259,21 @@ size_t edge_score_backward_partial_rows(size_t num_src) { return partial_rows(nu
 void edge_score_forward(const float* d_src, const float* d_dst, const float* d_w,
                         const float* d_bias, size_t num_src, size_t num_dst, size_t dim,
                         float* d_out, int device, hipStream_t stream) {
-  if (!check_shape("edge_score", num_src, num_dst, dim)) return;
-  GF_REQUIRE(d_src && d_dst && d_w && d_bias && d_out,
-             "edge_score: null src, dst, weight, bias or out");
-  const bool vec = dim % 4 == 0 && aligned16(d_src) && aligned16(d_dst) && aligned16(d_w);
-  const uint32_t B = static_cast<uint32_t>(num_src), M = static_cast<uint32_t>(num_dst),
-                 D = static_cast<uint32_t>(dim);
-  const dim3 grid((M + kRowsPerBlock - 1) / kRowsPerBlock), block(kThreads);
-  DeviceGuard dg(device);
-  if (vec)
-    edge_score_fwd<true><<<grid, block, 0, stream>>>(d_src, d_dst, d_w, d_bias, B, M, D, d_out);
-  else
-    edge_score_fwd<false><<<grid, block, 0, stream>>>(d_src, d_dst, d_w, d_bias, B, M, D, d_out);
-  GF_HIP(hipGetLastError());
+  forward(d_src, d_dst, d_w, d_bias, num_src, num_dst, dim, d_out, device, stream);
 }
 
 void edge_score_backward(const float* d_src, const float* d_dst, const float* d_w, size_t num_src,
                          size_t num_dst, size_t dim, const float* d_grad_out, float* d_partials,
                          size_t partial_rows_given, float* d_grad_src, float* d_grad_dst,
                          float* d_grad_w, float* d_grad_bias, int device, hipStream_t stream) {
-  if (!check_shape("edge_score backward", num_src, num_dst, dim)) return;
-  GF_REQUIRE(d_src && d_dst && d_w, "edge_score backward: null src, dst or weight");
-  GF_REQUIRE(d_grad_out != nullptr, "edge_score backward: null gradient");
-  const bool reduce = d_grad_w || d_grad_bias;
-  if (!reduce && !d_grad_src && !d_grad_dst) return;
-  const size_t want = partial_rows(num_src);
-  GF_REQUIRE(!reduce || (d_partials != nullptr && partial_rows_given >= want),
-             "edge_score backward: partials buffer missing or smaller than "
-             "gf_edge_score_backward_partial_rows() asks for");
-  const uint32_t B = static_cast<uint32_t>(num_src), D = static_cast<uint32_t>(dim);
-  const uint32_t r = static_cast<uint32_t>(num_dst / num_src);
-  const uint32_t rows_per_wg = static_cast<uint32_t>((num_src + want - 1) / want);
-  const uint32_t groups = (B + rows_per_wg - 1) / rows_per_wg;      // <= want
-  float* partials = reduce ? d_partials : nullptr;
-  DeviceGuard dg(device);
-  if (D + 1 <= 32)
-    edge_score_bwd<32><<<dim3(groups), dim3(kThreads), 0, stream>>>(
-        d_src, d_dst, d_w, d_grad_out, B, r, D, rows_per_wg, d_grad_src, d_grad_dst, partials);
-  else
-    edge_score_bwd<64><<<dim3(groups), dim3(kThreads), 0, stream>>>(
-        d_src, d_dst, d_w, d_grad_out, B, r, D, rows_per_wg, d_grad_src, d_grad_dst, partials);
-  GF_HIP(hipGetLastError());
-  if (!reduce) return;
-  edge_score_bwd_finish<<<dim3((D + 1 + 31) / 32), dim3(kFinishThreads), 0, stream>>>(
-      d_partials, groups, D, d_grad_w, d_grad_bias);
-  GF_HIP(hipGetLastError());
+  backward(d_src, d_dst, d_w, num_src, num_dst, dim, d_grad_out, d_partials, partial_rows_given,
+           d_grad_src, d_grad_dst, d_grad_w, d_grad_bias, device, stream);
 }
 
 void edge_score_bf16_forward(const uint16_t* d_src, const uint16_t* d_dst, const float* d_w,
                              const float* d_bias, size_t num_src, size_t num_dst, size_t dim,
                              float* d_out, int device, hipStream_t stream) {
-  if (!check_shape("edge_score", num_src, num_dst, dim)) return;
-  GF_REQUIRE(d_src && d_dst && d_w && d_bias && d_out,
-             "edge_score: null src, dst, weight, bias or out");
-  const bool vec = dim % 4 == 0 && (reinterpret_cast<uintptr_t>(d_src) & 7) == 0 &&
-                   (reinterpret_cast<uintptr_t>(d_dst) & 7) == 0 && aligned16(d_w);
-  const uint32_t B = static_cast<uint32_t>(num_src), M = static_cast<uint32_t>(num_dst),
-                 D = static_cast<uint32_t>(dim);
-  const dim3 grid((M + kRowsPerBlock - 1) / kRowsPerBlock), block(kThreads);
-  DeviceGuard dg(device);
-  if (vec)
-    edge_score_bf16_fwd<true><<<grid, block, 0, stream>>>(d_src, d_dst, d_w, d_bias, B, M, D,
-                                                          d_out);
-  else
-    edge_score_bf16_fwd<false><<<grid, block, 0, stream>>>(d_src, d_dst, d_w, d_bias, B, M, D,
-                                                           d_out);
-  GF_HIP(hipGetLastError());
+  forward(d_src, d_dst, d_w, d_bias, num_src, num_dst, dim, d_out, device, stream);
 }
 
 void edge_score_bf16_backward(const uint16_t* d_src, const uint16_t* d_dst, const float* d_w,
@@ -346,32 +281,8 @@ void edge_score_bf16_backward(const uint16_t* d_src, const uint16_t* d_dst, cons
                               float* d_partials, size_t partial_rows_given, uint16_t* d_grad_src,
                               uint16_t* d_grad_dst, float* d_grad_w, float* d_grad_bias,
                               int device, hipStream_t stream) {
-  if (!check_shape("edge_score backward", num_src, num_dst, dim)) return;
-  GF_REQUIRE(d_src && d_dst && d_w, "edge_score backward: null src, dst or weight");
-  GF_REQUIRE(d_grad_out != nullptr, "edge_score backward: null gradient");
-  const bool reduce = d_grad_w || d_grad_bias;
-  if (!reduce && !d_grad_src && !d_grad_dst) return;
-  const size_t want = partial_rows(num_src);
-  GF_REQUIRE(!reduce || (d_partials != nullptr && partial_rows_given >= want),
-             "edge_score backward: partials buffer missing or smaller than "
-             "gf_edge_score_backward_partial_rows() asks for");
-  const uint32_t B = static_cast<uint32_t>(num_src), D = static_cast<uint32_t>(dim);
-  const uint32_t r = static_cast<uint32_t>(num_dst / num_src);
-  const uint32_t rows_per_wg = static_cast<uint32_t>((num_src + want - 1) / want);
-  const uint32_t groups = (B + rows_per_wg - 1) / rows_per_wg;      // <= want
-  float* partials = reduce ? d_partials : nullptr;
-  DeviceGuard dg(device);
-  if (D + 1 <= 32)
-    edge_score_bf16_bwd<32><<<dim3(groups), dim3(kThreads), 0, stream>>>(
-        d_src, d_dst, d_w, d_grad_out, B, r, D, rows_per_wg, d_grad_src, d_grad_dst, partials);
-  else
-    edge_score_bf16_bwd<64><<<dim3(groups), dim3(kThreads), 0, stream>>>(
-        d_src, d_dst, d_w, d_grad_out, B, r, D, rows_per_wg, d_grad_src, d_grad_dst, partials);
-  GF_HIP(hipGetLastError());
-  if (!reduce) return;
-  edge_score_bwd_finish<<<dim3((D + 1 + 31) / 32), dim3(kFinishThreads), 0, stream>>>(
-      d_partials, groups, D, d_grad_w, d_grad_bias);
-  GF_HIP(hipGetLastError());
+  backward(d_src, d_dst, d_w, num_src, num_dst, dim, d_grad_out, d_partials, partial_rows_given,
+           d_grad_src, d_grad_dst, d_grad_w, d_grad_bias, device, stream);
 }
 
 }  // namespace gf

@@ -33,15 +33,14 @@
 // cosf / sinf are the precise forms: a real timestamp times the first frequency is an argument
 // of 1e6 rad and more, where __cosf / __sinf are wrong in the first digit.
 //
-// bfloat16 (the *_bf16 kernels; bf16.hpp).  The forward can write a bfloat16 row from the same
-// float32 parts, t, w and bias: the value of every column is the float32 kernel's, rounded once
-// to nearest even when it is stored.  Rows of an odd width put every second row on a 2-byte
+// bfloat16 (T = uint16_t; bf16.hpp).  The forward can write a bfloat16 row from the same
+// float32 parts, t, w and bias: one kernel body computes every column and only the chunk's store
+// knows T, rounding once to nearest even.  Rows of an odd width put every second row on a 2-byte
 // boundary, so the 4-column path (one 8-byte store) is taken only when, besides the float32
 // path's conditions, out is 8-byte aligned: with every width a multiple of 4 each chunk then
 // starts on an 8-byte boundary.  The backward can read a bfloat16 grad_out: each element is
-// widened (exact) where the float32 kernel loads it, and the partials, their layout and the
-// finish kernel are the float32 path's own, so gw and gbias are the float32 kernels' results on
-// the widened gradient, bit for bit.
+// widened (exact) when it is loaded, and the partials, their layout and the finish kernel know
+// no T, so gw and gbias are the float32 results on the widened gradient, bit for bit.
 #include "bf16.hpp"
 #include "block_ops.hpp"
 #include "common.hpp"
@@ -62,6 +61,7 @@ template <> struct Chunk<1> {
   float v[1];
   __device__ static Chunk load(const float* p) { return Chunk{{*p}}; }
   __device__ void store(float* p) const { *p = v[0]; }
+  __device__ void store(uint16_t* p) const { *p = narrow(v[0]); }
 };
 template <> struct Chunk<4> {
   float v[4];
@@ -72,15 +72,21 @@ template <> struct Chunk<4> {
   __device__ void store(float* p) const {
     *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
   }
+  __device__ void store(uint16_t* p) const {
+    const uint32_t lo = narrow(v[0]) | static_cast<uint32_t>(narrow(v[1])) << 16;
+    const uint32_t hi = narrow(v[2]) | static_cast<uint32_t>(narrow(v[3])) << 16;
+    *reinterpret_cast<uint2*>(p) = make_uint2(lo, hi);
+  }
 };
 
-// qa, qb, qt: the widths of a, b and the time columns in chunks of V floats; chunks = n * Q
-template <int V>
+// qa, qb, qt: the widths of a, b and the time columns in chunks of V floats; chunks = n * Q.
+// T is out's element type: a chunk is narrowed, if at all, when it is stored.
+template <class T, int V>
 __global__ void __launch_bounds__(kThreads)
 time_encode_cat_fwd(const float* __restrict__ a, uint32_t qa, const float* __restrict__ b,
                     uint32_t qb, const float* __restrict__ t, const float* __restrict__ w,
                     const float* __restrict__ bias, uint32_t qt, uint32_t chunks,
-                    float* __restrict__ out) {
+                    T* __restrict__ out) {
   const uint32_t k = blockIdx.x * static_cast<uint32_t>(kThreads) + threadIdx.x;
   if (k >= chunks) return;
   const uint32_t Q = qa + qb + qt;
@@ -101,46 +107,13 @@ time_encode_cat_fwd(const float* __restrict__ a, uint32_t qa, const float* __res
   x.store(out + static_cast<uint64_t>(k) * V);
 }
 
-// time_encode_cat_fwd with a bfloat16 out: the same chunks, each value narrowed on store
-__device__ inline void store_bf16(const Chunk<1>& x, uint16_t* p) { *p = narrow(x.v[0]); }
-__device__ inline void store_bf16(const Chunk<4>& x, uint16_t* p) {
-  const uint32_t lo = narrow(x.v[0]) | static_cast<uint32_t>(narrow(x.v[1])) << 16;
-  const uint32_t hi = narrow(x.v[2]) | static_cast<uint32_t>(narrow(x.v[3])) << 16;
-  *reinterpret_cast<uint2*>(p) = make_uint2(lo, hi);
-}
-
-template <int V>
-__global__ void __launch_bounds__(kThreads)
-time_encode_cat_bf16_fwd(const float* __restrict__ a, uint32_t qa, const float* __restrict__ b,
-                         uint32_t qb, const float* __restrict__ t, const float* __restrict__ w,
-                         const float* __restrict__ bias, uint32_t qt, uint32_t chunks,
-                         uint16_t* __restrict__ out) {
-  const uint32_t k = blockIdx.x * static_cast<uint32_t>(kThreads) + threadIdx.x;
-  if (k >= chunks) return;
-  const uint32_t Q = qa + qb + qt;
-  const uint32_t row = k / Q;
-  const uint32_t c = k - row * Q;
-  Chunk<V> x;
-  if (c < qa) {
-    x = Chunk<V>::load(a + (static_cast<uint64_t>(row) * qa + c) * V);
-  } else if (c < qa + qb) {
-    x = Chunk<V>::load(b + (static_cast<uint64_t>(row) * qb + (c - qa)) * V);
-  } else {
-    const uint32_t j = (c - qa - qb) * V;
-    const Chunk<V> wj = Chunk<V>::load(w + j), bj = Chunk<V>::load(bias + j);
-    const float ti = t[row];
-#pragma unroll
-    for (int e = 0; e < V; ++e) x.v[e] = cosf(te_arg(wj.v[e], ti, bj.v[e]));
-  }
-  store_bf16(x, out + static_cast<uint64_t>(k) * V);
-}
-
-// partials[p, 0, j] = gw's share of workgroup p's rows, partials[p, 1, j] = gbias's
-template <int CX>
+// partials[p, 0, j] = gw's share of workgroup p's rows, partials[p, 1, j] = gbias's.
+// G is the gradient's element type, widened where it is loaded.
+template <class G, int CX>
 __global__ void __launch_bounds__(kThreads)
 time_encode_bwd_partials(const float* __restrict__ t, const float* __restrict__ w,
                          const float* __restrict__ bias, uint64_t n, uint32_t T,
-                         const float* __restrict__ g, uint64_t pitch, uint64_t rows_per_wg,
+                         const G* __restrict__ g, uint64_t pitch, uint64_t rows_per_wg,
                          float* __restrict__ partials) {
   constexpr int RY = kThreads / CX;
   __shared__ float sw[RY][CX], sb[RY][CX];
@@ -154,51 +127,7 @@ time_encode_bwd_partials(const float* __restrict__ t, const float* __restrict__ 
     float aw = 0.f, ab = 0.f;
     if (active) {
       const float wj = w[j], bj = bias[j];
-      const float* gj = g + j;
-      for (uint64_t i = r0 + ry; i < r1; i += RY) {
-        const float ti = t[i];
-        const float p = gj[i * pitch] * sinf(te_arg(wj, ti, bj));
-        ab += p;
-        aw += p * ti;
-      }
-    }
-    sw[ry][cx] = aw;
-    sb[ry][cx] = ab;
-    __syncthreads();
-    if (ry == 0 && active) {
-      float tw = sw[0][cx], tb = sb[0][cx];
-#pragma unroll
-      for (int r = 1; r < RY; ++r) {
-        tw += sw[r][cx];
-        tb += sb[r][cx];
-      }
-      prow[j] = -tw;
-      prow[T + j] = -tb;
-    }
-    __syncthreads();
-  }
-}
-
-// time_encode_bwd_partials reading a bfloat16 gradient: widened where it is loaded
-template <int CX>
-__global__ void __launch_bounds__(kThreads)
-time_encode_bwd_partials_bf16(const float* __restrict__ t, const float* __restrict__ w,
-                         const float* __restrict__ bias, uint64_t n, uint32_t T,
-                         const uint16_t* __restrict__ g, uint64_t pitch, uint64_t rows_per_wg,
-                         float* __restrict__ partials) {
-  constexpr int RY = kThreads / CX;
-  __shared__ float sw[RY][CX], sb[RY][CX];
-  const uint32_t cx = threadIdx.x % CX, ry = threadIdx.x / CX;
-  const uint64_t r0 = blockIdx.x * rows_per_wg;
-  const uint64_t r1 = r0 + rows_per_wg < n ? r0 + rows_per_wg : n;
-  float* prow = partials + static_cast<uint64_t>(blockIdx.x) * 2 * T;
-  for (uint32_t j0 = 0; j0 < T; j0 += CX) {      // uniform over the workgroup
-    const uint32_t j = j0 + cx;
-    const bool active = j < T;
-    float aw = 0.f, ab = 0.f;
-    if (active) {
-      const float wj = w[j], bj = bias[j];
-      const uint16_t* gj = g + j;
+      const G* gj = g + j;
       for (uint64_t i = r0 + ry; i < r1; i += RY) {
         const float ti = t[i];
         const float p = widen(gj[i * pitch]) * sinf(te_arg(wj, ti, bj));
@@ -247,10 +176,79 @@ time_encode_bwd_finish(const float* __restrict__ partials, uint32_t rows, uint32
 }
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// can four elements at p be one store?  16-byte aligned float32, 8-byte aligned bfloat16
+template <class T>
+bool aligned4(const T* p) { return (reinterpret_cast<uintptr_t>(p) & (4 * sizeof(T) - 1)) == 0; }
 
 size_t partial_rows(size_t n) {
   const size_t groups = (n + kMinRowsPerGroup - 1) / kMinRowsPerGroup;
   return groups < kTimeEncodeMaxPartialRows ? groups : kTimeEncodeMaxPartialRows;
+}
+
+template <class T>
+void cat_forward(const float* d_a, size_t width_a, const float* d_b, size_t width_b,
+                 const float* d_t, const float* d_w, const float* d_bias, size_t n,
+                 size_t dim_time, T* d_out, int device, hipStream_t stream) {
+  GF_REQUIRE(dim_time >= 1, "time_encode_cat: dim_time must be >= 1");
+  if (n == 0) return;
+  GF_REQUIRE(d_t && d_w && d_bias && d_out, "time_encode_cat: null t, w, bias or out");
+  GF_REQUIRE((width_a == 0 || d_a) && (width_b == 0 || d_b),
+             "time_encode_cat: null part of non-zero width");
+  const size_t limit = size_t{1} << 32;
+  GF_REQUIRE(width_a < limit && width_b < limit && dim_time < limit &&
+                 width_a + width_b + dim_time < limit &&
+                 n <= (limit - 1) / (width_a + width_b + dim_time),
+             "time_encode_cat: more than 2^32 - 1 output elements");
+  const bool vec = width_a % 4 == 0 && width_b % 4 == 0 && dim_time % 4 == 0 &&
+                   aligned16(d_a) && aligned16(d_b) && aligned16(d_w) && aligned16(d_bias) &&
+                   aligned4(d_out);
+  const uint32_t v = vec ? 4 : 1;
+  const uint32_t qa = static_cast<uint32_t>(width_a / v), qb = static_cast<uint32_t>(width_b / v),
+                 qt = static_cast<uint32_t>(dim_time / v);
+  const uint32_t chunks = static_cast<uint32_t>(n * (qa + qb + qt));
+  const dim3 grid(static_cast<unsigned>((uint64_t{chunks} + kThreads - 1) / kThreads)),
+      block(kThreads);
+  DeviceGuard dg(device);
+  if (vec)
+    time_encode_cat_fwd<T, 4><<<grid, block, 0, stream>>>(d_a, qa, d_b, qb, d_t, d_w, d_bias, qt,
+                                                          chunks, d_out);
+  else
+    time_encode_cat_fwd<T, 1><<<grid, block, 0, stream>>>(d_a, qa, d_b, qb, d_t, d_w, d_bias, qt,
+                                                          chunks, d_out);
+  GF_HIP(hipGetLastError());
+}
+
+template <class G>
+void backward(const float* d_t, const float* d_w, const float* d_bias, size_t n, size_t dim_time,
+              const G* d_grad_out, size_t grad_pitch, size_t grad_col, float* d_partials,
+              size_t partial_rows_given, float* d_grad_w, float* d_grad_bias, int device,
+              hipStream_t stream) {
+  GF_REQUIRE(dim_time >= 1, "time_encode backward: dim_time must be >= 1");
+  GF_REQUIRE(dim_time < (size_t{1} << 30), "time_encode backward: dim_time too large");
+  if (n == 0 || (!d_grad_w && !d_grad_bias)) return;
+  GF_REQUIRE(d_t && d_w && d_bias, "time_encode backward: null t, w or bias");
+  GF_REQUIRE(d_grad_out != nullptr, "time_encode backward: null gradient");
+  GF_REQUIRE(grad_col + dim_time <= grad_pitch,
+             "time_encode backward: the time columns do not fit the gradient's row pitch");
+  GF_REQUIRE(d_partials != nullptr && partial_rows_given >= partial_rows(n),
+             "time_encode backward: partials buffer missing or smaller than "
+             "gf_time_encode_backward_partial_rows() asks for");
+  const size_t want = partial_rows(n);
+  const uint64_t rows_per_wg = (n + want - 1) / want;
+  const uint32_t groups = static_cast<uint32_t>((n + rows_per_wg - 1) / rows_per_wg);   // <= want
+  const uint32_t T = static_cast<uint32_t>(dim_time);
+  const G* g = d_grad_out + grad_col;
+  DeviceGuard dg(device);
+  if (T <= 32)
+    time_encode_bwd_partials<G, 32><<<dim3(groups), dim3(kThreads), 0, stream>>>(
+        d_t, d_w, d_bias, n, T, g, grad_pitch, rows_per_wg, d_partials);
+  else
+    time_encode_bwd_partials<G, 128><<<dim3(groups), dim3(kThreads), 0, stream>>>(
+        d_t, d_w, d_bias, n, T, g, grad_pitch, rows_per_wg, d_partials);
+  GF_HIP(hipGetLastError());
+  time_encode_bwd_finish<<<dim3((2 * T + 31) / 32), dim3(kFinishThreads), 0, stream>>>(
+      d_partials, groups, T, d_grad_w, d_grad_bias);
+  GF_HIP(hipGetLastError());
 }
 
 }  // namespace
@@ -260,99 +258,22 @@ size_t time_encode_backward_partial_rows(size_t n) { return partial_rows(n); }
 void time_encode_cat_forward(const float* d_a, size_t width_a, const float* d_b, size_t width_b,
                              const float* d_t, const float* d_w, const float* d_bias, size_t n,
                              size_t dim_time, float* d_out, int device, hipStream_t stream) {
-  GF_REQUIRE(dim_time >= 1, "time_encode_cat: dim_time must be >= 1");
-  if (n == 0) return;
-  GF_REQUIRE(d_t && d_w && d_bias && d_out, "time_encode_cat: null t, w, bias or out");
-  GF_REQUIRE((width_a == 0 || d_a) && (width_b == 0 || d_b),
-             "time_encode_cat: null part of non-zero width");
-  const size_t limit = size_t{1} << 32;
-  GF_REQUIRE(width_a < limit && width_b < limit && dim_time < limit &&
-                 width_a + width_b + dim_time < limit &&
-                 n <= (limit - 1) / (width_a + width_b + dim_time),
-             "time_encode_cat: more than 2^32 - 1 output elements");
-  const bool vec = width_a % 4 == 0 && width_b % 4 == 0 && dim_time % 4 == 0 &&
-                   aligned16(d_a) && aligned16(d_b) && aligned16(d_w) && aligned16(d_bias) &&
-                   aligned16(d_out);
-  const uint32_t v = vec ? 4 : 1;
-  const uint32_t qa = static_cast<uint32_t>(width_a / v), qb = static_cast<uint32_t>(width_b / v),
-                 qt = static_cast<uint32_t>(dim_time / v);
-  const uint32_t chunks = static_cast<uint32_t>(n * (qa + qb + qt));
-  const dim3 grid(static_cast<unsigned>((uint64_t{chunks} + kThreads - 1) / kThreads)),
-      block(kThreads);
-  DeviceGuard dg(device);
-  if (vec)
-    time_encode_cat_fwd<4><<<grid, block, 0, stream>>>(d_a, qa, d_b, qb, d_t, d_w, d_bias, qt,
-                                                       chunks, d_out);
-  else
-    time_encode_cat_fwd<1><<<grid, block, 0, stream>>>(d_a, qa, d_b, qb, d_t, d_w, d_bias, qt,
-                                                       chunks, d_out);
-  GF_HIP(hipGetLastError());
+  cat_forward(d_a, width_a, d_b, width_b, d_t, d_w, d_bias, n, dim_time, d_out, device, stream);
 }
 
 void time_encode_backward(const float* d_t, const float* d_w, const float* d_bias, size_t n,
                           size_t dim_time, const float* d_grad_out, size_t grad_pitch,
                           size_t grad_col, float* d_partials, size_t partial_rows_given,
                           float* d_grad_w, float* d_grad_bias, int device, hipStream_t stream) {
-  GF_REQUIRE(dim_time >= 1, "time_encode backward: dim_time must be >= 1");
-  GF_REQUIRE(dim_time < (size_t{1} << 30), "time_encode backward: dim_time too large");
-  if (n == 0 || (!d_grad_w && !d_grad_bias)) return;
-  GF_REQUIRE(d_t && d_w && d_bias, "time_encode backward: null t, w or bias");
-  GF_REQUIRE(d_grad_out != nullptr, "time_encode backward: null gradient");
-  GF_REQUIRE(grad_col + dim_time <= grad_pitch,
-             "time_encode backward: the time columns do not fit the gradient's row pitch");
-  GF_REQUIRE(d_partials != nullptr && partial_rows_given >= partial_rows(n),
-             "time_encode backward: partials buffer missing or smaller than "
-             "gf_time_encode_backward_partial_rows() asks for");
-  const size_t want = partial_rows(n);
-  const uint64_t rows_per_wg = (n + want - 1) / want;
-  const uint32_t groups = static_cast<uint32_t>((n + rows_per_wg - 1) / rows_per_wg);   // <= want
-  const uint32_t T = static_cast<uint32_t>(dim_time);
-  const float* g = d_grad_out + grad_col;
-  DeviceGuard dg(device);
-  if (T <= 32)
-    time_encode_bwd_partials<32><<<dim3(groups), dim3(kThreads), 0, stream>>>(
-        d_t, d_w, d_bias, n, T, g, grad_pitch, rows_per_wg, d_partials);
-  else
-    time_encode_bwd_partials<128><<<dim3(groups), dim3(kThreads), 0, stream>>>(
-        d_t, d_w, d_bias, n, T, g, grad_pitch, rows_per_wg, d_partials);
-  GF_HIP(hipGetLastError());
-  time_encode_bwd_finish<<<dim3((2 * T + 31) / 32), dim3(kFinishThreads), 0, stream>>>(
-      d_partials, groups, T, d_grad_w, d_grad_bias);
-  GF_HIP(hipGetLastError());
+  backward(d_t, d_w, d_bias, n, dim_time, d_grad_out, grad_pitch, grad_col, d_partials,
+           partial_rows_given, d_grad_w, d_grad_bias, device, stream);
 }
 
 void time_encode_cat_bf16_forward(const float* d_a, size_t width_a, const float* d_b,
                                   size_t width_b, const float* d_t, const float* d_w,
                                   const float* d_bias, size_t n, size_t dim_time, uint16_t* d_out,
                                   int device, hipStream_t stream) {
-  GF_REQUIRE(dim_time >= 1, "time_encode_cat: dim_time must be >= 1");
-  if (n == 0) return;
-  GF_REQUIRE(d_t && d_w && d_bias && d_out, "time_encode_cat: null t, w, bias or out");
-  GF_REQUIRE((width_a == 0 || d_a) && (width_b == 0 || d_b),
-             "time_encode_cat: null part of non-zero width");
-  const size_t limit = size_t{1} << 32;
-  GF_REQUIRE(width_a < limit && width_b < limit && dim_time < limit &&
-                 width_a + width_b + dim_time < limit &&
-                 n <= (limit - 1) / (width_a + width_b + dim_time),
-             "time_encode_cat: more than 2^32 - 1 output elements");
-  // 4 bfloat16 columns are one 8-byte store
-  const bool vec = width_a % 4 == 0 && width_b % 4 == 0 && dim_time % 4 == 0 &&
-                   aligned16(d_a) && aligned16(d_b) && aligned16(d_w) && aligned16(d_bias) &&
-                   (reinterpret_cast<uintptr_t>(d_out) & 7) == 0;
-  const uint32_t v = vec ? 4 : 1;
-  const uint32_t qa = static_cast<uint32_t>(width_a / v), qb = static_cast<uint32_t>(width_b / v),
-                 qt = static_cast<uint32_t>(dim_time / v);
-  const uint32_t chunks = static_cast<uint32_t>(n * (qa + qb + qt));
-  const dim3 grid(static_cast<unsigned>((uint64_t{chunks} + kThreads - 1) / kThreads)),
-      block(kThreads);
-  DeviceGuard dg(device);
-  if (vec)
-    time_encode_cat_bf16_fwd<4><<<grid, block, 0, stream>>>(d_a, qa, d_b, qb, d_t, d_w, d_bias,
-                                                            qt, chunks, d_out);
-  else
-    time_encode_cat_bf16_fwd<1><<<grid, block, 0, stream>>>(d_a, qa, d_b, qb, d_t, d_w, d_bias,
-                                                            qt, chunks, d_out);
-  GF_HIP(hipGetLastError());
+  cat_forward(d_a, width_a, d_b, width_b, d_t, d_w, d_bias, n, dim_time, d_out, device, stream);
 }
 
 void time_encode_backward_bf16(const float* d_t, const float* d_w, const float* d_bias, size_t n,
@@ -360,32 +281,8 @@ void time_encode_backward_bf16(const float* d_t, const float* d_w, const float* 
                                size_t grad_col, float* d_partials, size_t partial_rows_given,
                                float* d_grad_w, float* d_grad_bias, int device,
                                hipStream_t stream) {
-  GF_REQUIRE(dim_time >= 1, "time_encode backward: dim_time must be >= 1");
-  GF_REQUIRE(dim_time < (size_t{1} << 30), "time_encode backward: dim_time too large");
-  if (n == 0 || (!d_grad_w && !d_grad_bias)) return;
-  GF_REQUIRE(d_t && d_w && d_bias, "time_encode backward: null t, w or bias");
-  GF_REQUIRE(d_grad_out != nullptr, "time_encode backward: null gradient");
-  GF_REQUIRE(grad_col + dim_time <= grad_pitch,
-             "time_encode backward: the time columns do not fit the gradient's row pitch");
-  GF_REQUIRE(d_partials != nullptr && partial_rows_given >= partial_rows(n),
-             "time_encode backward: partials buffer missing or smaller than "
-             "gf_time_encode_backward_partial_rows() asks for");
-  const size_t want = partial_rows(n);
-  const uint64_t rows_per_wg = (n + want - 1) / want;
-  const uint32_t groups = static_cast<uint32_t>((n + rows_per_wg - 1) / rows_per_wg);   // <= want
-  const uint32_t T = static_cast<uint32_t>(dim_time);
-  const uint16_t* g = d_grad_out + grad_col;
-  DeviceGuard dg(device);
-  if (T <= 32)
-    time_encode_bwd_partials_bf16<32><<<dim3(groups), dim3(kThreads), 0, stream>>>(
-        d_t, d_w, d_bias, n, T, g, grad_pitch, rows_per_wg, d_partials);
-  else
-    time_encode_bwd_partials_bf16<128><<<dim3(groups), dim3(kThreads), 0, stream>>>(
-        d_t, d_w, d_bias, n, T, g, grad_pitch, rows_per_wg, d_partials);
-  GF_HIP(hipGetLastError());
-  time_encode_bwd_finish<<<dim3((2 * T + 31) / 32), dim3(kFinishThreads), 0, stream>>>(
-      d_partials, groups, T, d_grad_w, d_grad_bias);
-  GF_HIP(hipGetLastError());
+  backward(d_t, d_w, d_bias, n, dim_time, d_grad_out, grad_pitch, grad_col, d_partials,
+           partial_rows_given, d_grad_w, d_grad_bias, device, stream);
 }
 
 }  // namespace gf

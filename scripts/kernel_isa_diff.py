@@ -2,6 +2,7 @@
 """Per-kernel comparison of the gfx950 device assembly of two source trees (no GPU needed).
 
     python scripts/kernel_isa_diff.py OLD_TREE NEW_TREE [--only SUBSTRING] [--quiet]
+                                      [--map 'REGEX=REPLACEMENT']...
 
 Every gnnflow_amd/csrc/*.hip of each tree is compiled with the FLAGS of gnnflow_amd/_build.py
 plus `--cuda-device-only -S`, and the output is cut into one text per `.amdhsa_kernel` symbol:
@@ -12,8 +13,11 @@ Only what a move between translation units must change is normalised:
   * the kernel's own mangled symbol (it changes when a parameter type changes namespace),
   * comments: whole lines and the trailing ones, which name basic blocks by function index.
 Registers, immediates, instruction order and descriptor values are compared as they are.
-Kernels are matched by demangled name without `(anonymous namespace)::`.  Prints `same` or a
-unified diff per kernel; exit status 1 if a kernel differs, 2 if the sets of kernels differ.
+Kernels are matched by demangled name without `(anonymous namespace)::`.  Where a change renames
+kernels on purpose (a template parameter added, a parameter type renamed), each `--map` is a
+re.sub applied, in the order given, to the demangled names of BOTH trees before they are matched.
+Prints `same` or a unified diff per kernel; exit status 1 if a kernel differs, 2 if the sets of
+kernels differ.
 """
 import argparse
 import difflib
@@ -83,7 +87,7 @@ def demangle(symbols):
     return names
 
 
-def tree_kernels(tree, hipcc):
+def tree_kernels(tree, hipcc, maps=()):
     files = sorted(glob.glob(os.path.join(tree, "gnnflow_amd", "csrc", "*.hip")))
     with ThreadPoolExecutor(max_workers=4) as ex:
         asms = list(ex.map(lambda f: device_asm(tree, f, hipcc), files))
@@ -91,6 +95,8 @@ def tree_kernels(tree, hipcc):
     for f, asm in zip(files, asms):
         ks = kernels_of(asm)
         for sym, name in zip(ks, demangle(list(ks))):
+            for pat, rep in maps:
+                name = pat.sub(rep, name)
             if name in out:   # a library template instantiated in two translation units
                 name += " [" + os.path.basename(f) + "]"
             out[name] = (os.path.basename(f), ks[sym])
@@ -103,9 +109,17 @@ def main():
     ap.add_argument("new")
     ap.add_argument("--only", default="", help="compare kernels whose name contains this")
     ap.add_argument("--quiet", action="store_true", help="no diffs, the summary only")
+    ap.add_argument("--map", action="append", default=[], metavar="REGEX=REPLACEMENT",
+                    help="rename demangled kernel names of both trees before matching (repeatable)")
     ap.add_argument("--hipcc", default=os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))
     a = ap.parse_args()
-    old, new = tree_kernels(a.old, a.hipcc), tree_kernels(a.new, a.hipcc)
+    maps = []
+    for m in a.map:
+        pat, sep, rep = m.partition("=")
+        if not sep:
+            ap.error("--map needs REGEX=REPLACEMENT, got %r" % m)
+        maps.append((re.compile(pat), rep))
+    old, new = tree_kernels(a.old, a.hipcc, maps), tree_kernels(a.new, a.hipcc, maps)
     status = 0
     if set(old) != set(new):
         for n in sorted(set(old) - set(new)):

@@ -1,4 +1,4 @@
-"""ops.block_attention on bfloat16 q, k, v (csrc/block_attention_bf16.hip) against the float32 op
+"""ops.block_attention on bfloat16 q, k, v (csrc/block_attention.hip) against the float32 op
 on the widened inputs, bit for bit, forward and backward, with and without dropout:
 
     bf16_op(x.bfloat16(), ...)  ==  fp32_op(x.bfloat16().float(), ...).to(torch.bfloat16)
@@ -200,6 +200,21 @@ def test_dropout_on_sampler_blocks(sampler_blocks, p):
 def test_dropout_with_several_columns_per_lane(H, D):
     c = A.shape_case(H, D)
     check(_block(c["row"], 40), c, dropout_p=R.P, dropout_seed=R.SEED)
+
+
+DISPATCH_ROWS = [(2, 8), (2, 16), (2, 32), (2, 64), (2, 65), (2, 129), (2, 257), (1, 513)]
+
+
+@pytest.mark.parametrize("H,D", DISPATCH_ROWS, ids=["{}x{}".format(*s) for s in DISPATCH_ROWS])
+def test_dropout_on_every_dispatch_row(H, D):
+    """A kernel template is compiled only where it is instantiated: every (G, NC) the dispatch can
+    choose, for both element types, forward and backward, with dropout, on a block with a
+    destination without in-edges and one whose 70 edges take a 64-lane group round twice.  The
+    rows without dropout are run by test_head_shapes and test_many_columns_per_lane."""
+    degs = [2, 0, 70, 1, 3]
+    c = A.make_inputs(A.rows_of(degs), len(degs), H, D, 970 + D)
+    got = check(_block(c["row"], len(degs)), c, dropout_p=R.P, dropout_seed=R.SEED)
+    assert not got["out"][1].any() and not got["gq"][1].any()
 
 
 def test_non_finite_v_on_a_dropped_edge_does_not_propagate():

@@ -1,4 +1,4 @@
-"""ops.block_gat on a bfloat16 feat (csrc/block_gat_bf16.hip) against the float32 op on the
+"""ops.block_gat on a bfloat16 feat (csrc/block_gat.hip) against the float32 op on the
 widened feat, bit for bit, forward and backward, with and without dropout:
 
     out, grad_feat:            bf16_op(x)  ==  fp32_op(x.float()).to(torch.bfloat16)

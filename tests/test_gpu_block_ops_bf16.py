@@ -1,4 +1,4 @@
-"""ops.block_reduce and ops.block_max on bfloat16 source rows (csrc/block_ops_bf16.hip) against
+"""ops.block_reduce and ops.block_max on bfloat16 source rows (csrc/block_ops.hip) against
 the float32 ops on the widened inputs, bit for bit, forward and backward:
 
     bf16_op(x, ...)  ==  fp32_op(x.float(), ...).to(torch.bfloat16)        x bfloat16

@@ -1,4 +1,4 @@
-"""ops.edge_score on bfloat16 src and dst rows (the *_bf16 kernels of csrc/edge_score.hip)
+"""ops.edge_score on bfloat16 src and dst rows (the uint16_t kernels of csrc/edge_score.hip)
 against the float32 op on the widened rows, bit for bit: the float32 scores and the float32
 gradients of weight and bias with torch.equal, the bfloat16 gradients of src and dst against the
 float32 op's rounded once, on the raw 16-bit patterns.  The float32 op is checked against float64

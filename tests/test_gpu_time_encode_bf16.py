@@ -1,4 +1,4 @@
-"""ops.time_encode_cat with out_dtype=torch.bfloat16 (the *_bf16 kernels of csrc/time_encode.hip)
+"""ops.time_encode_cat with out_dtype=torch.bfloat16 (the uint16_t kernels of csrc/time_encode.hip)
 against the float32 op, bit for bit:
 
     forward    rows == float32 rows .to(torch.bfloat16)           (raw 16-bit patterns)
