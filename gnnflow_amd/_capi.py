@@ -319,6 +319,8 @@ PROTOTYPES = {
     "gf_edge_rank_scratch": (C.c_int, [_sz, _sz, _sz, C.POINTER(_sz)]),
     "gf_edge_rank": (C.c_int, [_p, _p, _p, _p, _sz, _sz, _sz, _sz, _p, _p, _p, _sz, _p, _p, _p,
                                _p, C.c_int, _p]),
+    "gf_edge_rank_masked": (C.c_int, [_p, _p, _p, _p, _sz, _sz, _sz, _sz, _p, _p, _p, _p, _sz, _p,
+                                      _p, _p, _p, C.c_int, _p]),
     "gf_link_metrics_partial_rows": (C.c_int, [_sz, C.POINTER(_sz)]),
     "gf_link_metrics": (C.c_int, [_p, _p, _sz, _sz, _p, _sz, _p, _p, C.c_int, _p]),
     "gf_link_loss_partial_rows": (C.c_int, [_sz, _sz, C.POINTER(_sz)]),
@@ -332,6 +334,7 @@ PROTOTYPES = {
                                          C.c_uint64, C.c_uint64, _p, _p, _sz, C.c_int, _p]),
     "gf_batch_hist_negatives": (C.c_int, [_p, _p, _p, _p, _sz, _p, _sz, _sz, _sz, _sz, C.c_uint64,
                                           C.c_uint64, C.c_uint64, _p, _sz, _p, C.c_int, _p]),
+    "gf_graph_seen_mask": (C.c_int, [_p, _p, _p, _sz, _p, _p, _sz, _sz, _p, C.c_int, _p]),
     "gf_dst_set_mark": (C.c_int, [_p, _sz, _p, _sz, _p, C.c_int, _p]),
     "gf_dst_set_scratch_bytes": (C.c_int, [_sz, C.POINTER(_sz)]),
     "gf_dst_set_compact": (C.c_int, [_p, _sz, _p, _sz, _p, _p, _sz, C.c_int, _p]),

@@ -254,7 +254,9 @@ void link_metrics(const float* d_pos, const float* d_neg, size_t num_pos, size_t
 // set cand [num_cand, dim], of which only the k best candidates per source (values, indices
 // [num_src, k]: score descending, then index ascending; NaN below -inf; (-inf, -1) where fewer
 // than k are left) and the counts greater / equal [num_src] of the candidates whose score is > /
-// == d_ref_score[i] are kept; candidate d_skip[i] is left out of both.  Two launches, no atomics,
+// == d_ref_score[i] are kept; candidate d_skip[i] is left out of both, and so is every candidate
+// whose bit is set in d_exclude [num_src, ceil(num_cand / 64)] (bit c % 64 of word c / 64; null:
+// no mask; bits past num_cand are ignored).  Two launches, no atomics,
 // bit-reproducible; a pair's score is edge_score_forward's, bit for bit, unless its row holds a
 // NaN (which stays one).  d_ref_score null: no counts; k == 0: no list; d_skip null: nothing
 // skipped.  d_scratch: edge_rank_scratch_bytes() bytes, 8-byte aligned, caller-owned.
@@ -265,9 +267,9 @@ constexpr size_t kEdgeRankChunk = 256;      // candidates per workgroup pass
 size_t edge_rank_scratch_bytes(size_t num_src, size_t num_cand, size_t k);
 void edge_rank(const float* d_src, const float* d_cand, const float* d_w, const float* d_bias,
                size_t num_src, size_t num_cand, size_t dim, size_t k, const float* d_ref_score,
-               const int64_t* d_skip, void* d_scratch, size_t scratch_bytes, float* d_values,
-               int64_t* d_indices, int64_t* d_greater, int64_t* d_equal, int device,
-               hipStream_t stream);
+               const int64_t* d_skip, const uint64_t* d_exclude, void* d_scratch,
+               size_t scratch_bytes, float* d_values, int64_t* d_indices, int64_t* d_greater,
+               int64_t* d_equal, int device, hipStream_t stream);
 
 // link_loss.hip: out[1] (float32) = mean softplus(-pos) + mean softplus(neg), the reference's
 // BCEWithLogitsLoss of the positive logits against 1 plus that of the negative ones against 0,

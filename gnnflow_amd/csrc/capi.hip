@@ -472,8 +472,19 @@ int gf_edge_rank(const float* d_src, const float* d_cand, const float* d_w, cons
                  void* stream) {
   return guarded([&] {
     gf::edge_rank(d_src, d_cand, d_w, d_bias, num_src, num_cand, dim, k, d_ref_score, d_skip,
-                  d_scratch, scratch_bytes, d_values, d_indices, d_greater, d_equal, device,
-                  as_stream(stream));
+                  nullptr, d_scratch, scratch_bytes, d_values, d_indices, d_greater, d_equal,
+                  device, as_stream(stream));
+  });
+}
+int gf_edge_rank_masked(const float* d_src, const float* d_cand, const float* d_w,
+                        const float* d_bias, size_t num_src, size_t num_cand, size_t dim, size_t k,
+                        const float* d_ref_score, const int64_t* d_skip, const uint64_t* d_exclude,
+                        void* d_scratch, size_t scratch_bytes, float* d_values, int64_t* d_indices,
+                        int64_t* d_greater, int64_t* d_equal, int device, void* stream) {
+  return guarded([&] {
+    gf::edge_rank(d_src, d_cand, d_w, d_bias, num_src, num_cand, dim, k, d_ref_score, d_skip,
+                  d_exclude, d_scratch, scratch_bytes, d_values, d_indices, d_greater, d_equal,
+                  device, as_stream(stream));
   });
 }
 

@@ -2,6 +2,7 @@
 // batch call that reads the store, gf_batch_hist_negatives.
 #include "capi_handles.hpp"
 #include "hist_negatives.hpp"
+#include "seen_mask.hpp"
 
 extern "C" {
 
@@ -83,6 +84,16 @@ int gf_batch_hist_negatives(const gf_graph* g, const int64_t* d_src, const int64
     gf::batch_hist_negatives(g->impl.view(), d_src, d_dst, d_time, num_rows, d_borders,
                              num_batches, max_batch_rows, neg_ratio, hist_ratio, seed, epoch,
                              first_row, d_roots, capacity, d_filled, device, as_stream(stream));
+  });
+}
+// reads the store's view NOW, as gf_batch_hist_negatives does
+int gf_graph_seen_mask(const gf_graph* g, const int64_t* d_src, const float* d_ts, size_t num_rows,
+                       const int64_t* d_sorted_ids, const int64_t* d_perm, size_t num_cand,
+                       size_t max_history, uint64_t* d_mask, int device, void* stream) {
+  return guarded([&] {
+    GF_G(g);
+    gf::seen_mask(g->impl.view(), d_src, d_ts, num_rows, d_sorted_ids, d_perm, num_cand,
+                  max_history, d_mask, device, as_stream(stream));
   });
 }
 

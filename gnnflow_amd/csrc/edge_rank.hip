@@ -45,6 +45,12 @@
 // has key 0, below everything.  The workgroup writes its counts and its k keys, descending, to
 // scratch.
 //
+// Exclusion mask (MASKED).  exclude [B, W], W = ceil(C / 64): bit c % 64 of word [i, c / 64] set
+// leaves candidate c out of row i exactly as skip[i] does.  Lane l holds candidates
+// c0 + l + 64 j and c0 is a multiple of 64, so the 64 candidates of one j are one word: one
+// wave-uniform load and a bit test per lane.  Bits past C are never looked at.  The unmasked
+// instantiations are the code the kernel had before there was a mask.
+//
 // Merge pass.  One wave per source sums the chunks' counts (integers: any order) and takes the
 // k largest of the chunks' lists: k rounds of "largest key below the previous one", every lane
 // walking its chunks' descending lists up to the first key below it.  Key 0 is written as
@@ -175,13 +181,14 @@ __device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
 
 // counts[(chunk * B + i) * 2 + {0, 1}] = greater, equal of source i in the chunk (null: none);
 // lists[(i * chunks + chunk) * k + t] = its t-th largest key (k == 0: none)
-template <bool VEC>
+template <bool VEC, bool MASKED>
 __global__ void __launch_bounds__(kThreads)
 edge_rank_score(const float* __restrict__ src, const float* __restrict__ cand,
                 const float* __restrict__ w, const float* __restrict__ bias, uint32_t B,
                 uint32_t C, uint32_t D, uint32_t k, uint32_t chunks,
                 const float* __restrict__ ref, const int64_t* __restrict__ skip,
-                uint32_t* __restrict__ counts, uint64_t* __restrict__ lists) {
+                const uint64_t* __restrict__ exclude, uint32_t* __restrict__ counts,
+                uint64_t* __restrict__ lists) {
   __shared__ __align__(16) float s_src[kTileSrc][kStride];
   __shared__ __align__(16) float s_cand[kTileCand][kStride];
   __shared__ __align__(16) float s_w[kPass];
@@ -248,12 +255,17 @@ edge_rank_score(const float* __restrict__ src, const float* __restrict__ cand,
     if (i >= B) break;      // uniform over the wave
     const int64_t skipped = skip ? skip[i] : -1;
     const float x = counts ? ref[i] : 0.f;
+    const uint32_t W = (C + kWave - 1) / kWave, w0 = c0 / kWave;
     uint64_t key[kPerLane];
     uint32_t gt = 0, eq = 0;
 #pragma unroll
     for (int j = 0; j < kPerLane; ++j) {
       const uint32_t cl = lane + j * kWave, c = c0 + cl;
-      const bool valid = c < C && static_cast<int64_t>(c) != skipped;
+      bool valid = c < C && static_cast<int64_t>(c) != skipped;
+      if (MASKED) {      // the word of candidates c0 + 64 j ..: uniform over the wave
+        const uint64_t word = w0 + j < W ? exclude[static_cast<uint64_t>(i) * W + w0 + j] : 0ull;
+        valid = valid && !((word >> lane) & 1ull);
+      }
       const float v = valid ? s_score[r][cl] : 0.f;      // past C the tile was never written
       key[j] = valid ? (static_cast<uint64_t>(ordered(v)) << 32) | static_cast<uint32_t>(~c) : 0ull;
       if (counts) {
@@ -359,9 +371,9 @@ size_t edge_rank_scratch_bytes(size_t num_src, size_t num_cand, size_t k) {
 
 void edge_rank(const float* d_src, const float* d_cand, const float* d_w, const float* d_bias,
                size_t num_src, size_t num_cand, size_t dim, size_t k, const float* d_ref_score,
-               const int64_t* d_skip, void* d_scratch, size_t scratch_bytes, float* d_values,
-               int64_t* d_indices, int64_t* d_greater, int64_t* d_equal, int device,
-               hipStream_t stream) {
+               const int64_t* d_skip, const uint64_t* d_exclude, void* d_scratch,
+               size_t scratch_bytes, float* d_values, int64_t* d_indices, int64_t* d_greater,
+               int64_t* d_equal, int device, hipStream_t stream) {
   GF_REQUIRE(dim >= 1, "edge_rank: dim must be >= 1");
   GF_REQUIRE(dim < (size_t{1} << 30), "edge_rank: dim too large");
   check_shape(num_src, num_cand, k);
@@ -384,14 +396,10 @@ void edge_rank(const float* d_src, const float* d_cand, const float* d_w, const 
   const bool vec = dim % 4 == 0 && aligned16(d_src) && aligned16(d_cand) && aligned16(d_w);
   const dim3 grid(tiles * chunks), block(kThreads);
   DeviceGuard dg(device);
-  if (vec)
-    edge_rank_score<true><<<grid, block, 0, stream>>>(d_src, d_cand, d_w, d_bias, B, C, D, K,
-                                                      chunks, d_ref_score, d_skip,
-                                                      count ? counts : nullptr, lists);
-  else
-    edge_rank_score<false><<<grid, block, 0, stream>>>(d_src, d_cand, d_w, d_bias, B, C, D, K,
-                                                       chunks, d_ref_score, d_skip,
-                                                       count ? counts : nullptr, lists);
+  auto* const score = d_exclude ? (vec ? edge_rank_score<true, true> : edge_rank_score<false, true>)
+                                : (vec ? edge_rank_score<true, false> : edge_rank_score<false, false>);
+  score<<<grid, block, 0, stream>>>(d_src, d_cand, d_w, d_bias, B, C, D, K, chunks, d_ref_score,
+                                    d_skip, d_exclude, count ? counts : nullptr, lists);
   GF_HIP(hipGetLastError());
   edge_rank_merge<<<dim3((B + kWaves - 1) / kWaves), block, 0, stream>>>(
       counts, lists, B, chunks, K, d_values, d_indices, count ? d_greater : nullptr,

@@ -23,6 +23,7 @@
 // workgroup and added with one atomicAdd per workgroup.
 #include "hist_negatives.hpp"
 #include "common.hpp"
+#include "history_window.hpp"
 
 #include "../../include/gnnflow_rng.h"
 
@@ -55,17 +56,6 @@ struct HistArgs {
   uint64_t capacity;         // elements roots can hold
   unsigned long long* filled;
 };
-
-// elements of the ascending run ts[0:n) that are < t (float <: a NaN t gives 0)
-__device__ __forceinline__ uint32_t count_before(const float* __restrict__ ts, uint32_t n,
-                                                 float t) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = lo + (hi - lo) / 2;      // < n
-    if (ts[mid] < t) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
 
 __global__ void __launch_bounds__(kThreads) hist_negatives_kernel(const HistArgs a) {
   __shared__ uint64_t s_start[kTileRows];

@@ -5,12 +5,44 @@ import ctypes as C
 from typing import Optional, Tuple
 
 import numpy as np
+import torch
 
 from . import _capi
 
 
 def _i64(a):
     return np.ascontiguousarray(a, dtype=np.int64)
+
+
+def check_seen_mask_args(src, ts, cand_ids, max_history=0):
+    """Arguments of DynamicGraph.seen_mask, checked before anything is launched: the kernel takes
+    raw pointers and trusts them.  Needs no device.  Returns (B, C)."""
+    for name, x, dtype in (("src", src, torch.int64), ("ts", ts, torch.float32),
+                           ("cand_ids", cand_ids, torch.int64)):
+        if not isinstance(x, torch.Tensor):
+            raise TypeError("{} must be a tensor, got {}".format(name, type(x).__name__))
+        if x.dtype != dtype:
+            raise TypeError("{} must be {}, got {}".format(name, dtype, x.dtype))
+    if isinstance(max_history, bool) or not isinstance(max_history, int):
+        raise TypeError("max_history must be an int, got {}".format(type(max_history).__name__))
+    for name, x in (("src", src), ("ts", ts), ("cand_ids", cand_ids)):
+        if x.dim() != 1:
+            raise ValueError("{} must be 1-D, got shape {}".format(name, tuple(x.shape)))
+    B, Cn = int(src.shape[0]), int(cand_ids.shape[0])
+    if int(ts.shape[0]) != B:
+        raise ValueError("src has {} rows, ts has {}".format(B, int(ts.shape[0])))
+    if Cn == 0:
+        raise ValueError("seen_mask needs at least one candidate")
+    if Cn >= 2 ** 31:
+        raise ValueError("seen_mask takes fewer than 2**31 candidates, got {}".format(Cn))
+    if B >= 2 ** 31:
+        raise ValueError("seen_mask takes fewer than 2**31 rows, got {}".format(B))
+    if max_history < 0:
+        raise ValueError("max_history must be >= 0, got {}".format(max_history))
+    for name, x in (("ts", ts), ("cand_ids", cand_ids)):
+        if x.device != src.device:
+            raise ValueError("{} is on {}, src on {}".format(name, x.device, src.device))
+    return B, Cn
 
 
 class DynamicGraph:
@@ -170,6 +202,50 @@ class DynamicGraph:
                 self._h, int(vertex), d.ctypes.data, t.ctypes.data, e.ctypes.data,
                 n.value, C.byref(n)))
         return d, t, e
+
+    def seen_mask(self, src: torch.Tensor, ts: torch.Tensor, cand_ids: torch.Tensor,
+                  max_history: int = 0) -> torch.Tensor:
+        """Which of the candidates has each source already met: an int64 tensor [B, W],
+        W = (C + 63) // 64, in which bit c % 64 of word [i, c // 64] is set iff one of the
+        considered edges of src[i] leads to cand_ids[c].  The considered edges are the live edges
+        of src[i] in the store whose timestamp is strictly below ts[i] (float <: a NaN time gives
+        no bits) and, when max_history > 0, only the newest max_history of them.  "Strictly
+        before" and "live" as for DeviceBatchStream's historical negatives: edges that
+        offload_old_blocks took are gone, and on a graph built with reverse edges the history
+        includes the nodes that pointed at the source.  Bits at positions >= C are 0; a source
+        that is negative, past the node table or without live edges gives a zero row.
+
+        src: int64 [B], ts: float32 [B], cand_ids: int64 [C] in any order, duplicates and ids
+        unknown to the graph allowed; all on the graph's device.  B == 0 returns [0, W];
+        C == 0 is a ValueError.  The result is ops.edge_rank's `exclude`
+        (EdgePredictor.rank(..., exclude=)): recommendation without the nodes already known,
+        filtered MRR / Hits@k.
+
+        One sort of the candidates and one kernel (csrc/seen_mask.hip) on the current stream,
+        memory from torch, never synchronises.  Edges added to the graph are seen by calls made
+        after add_edges returns; add_edges and offload_old_blocks move and free segments:
+        synchronise the streams that calls were launched on before calling either, as for
+        DeviceBatchStream(hist_ratio=).
+
+        The cost is proportional to the histories considered: a wave reads every considered edge
+        of its row and looks it up among the sorted candidates, so a hub with 10^6 earlier edges
+        is 10^6 record reads for its row.  max_history is what bounds it."""
+        B, Cn = check_seen_mask_args(src, ts, cand_ids, max_history)
+        dev = src.device
+        if dev.type != "cuda" or (dev.index is not None and dev.index != self._device):
+            raise ValueError("the graph is on device cuda:{}, the inputs on {}".format(
+                self._device, dev))
+        W = (Cn + 63) // 64
+        with torch.cuda.device(self._device):
+            mask = torch.zeros((B, W), dtype=torch.int64, device=dev)
+            if B:
+                sorted_ids, perm = torch.sort(cand_ids.detach())
+                s, t = src.detach().contiguous(), ts.detach().contiguous()
+                _capi.check(self._lib.gf_graph_seen_mask(
+                    self._h, s.data_ptr(), t.data_ptr(), B, sorted_ids.data_ptr(),
+                    perm.data_ptr(), Cn, max_history, mask.data_ptr(), self._device,
+                    _capi.current_stream(torch.device("cuda", self._device))))
+        return mask
 
     def _float(self, fn) -> float:
         v = C.c_float(0)

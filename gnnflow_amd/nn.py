@@ -566,7 +566,8 @@ class EdgePredictor(nn.Module):
 
     @torch.no_grad()
     def rank(self, h_src: torch.Tensor, h_cand: torch.Tensor, k: int = 0,
-             target: Optional[torch.Tensor] = None) -> "ops.EdgeRank":
+             target: Optional[torch.Tensor] = None,
+             exclude: Optional[torch.Tensor] = None) -> "ops.EdgeRank":
         """Ranks the candidates h_cand [C, dim_embed] for every source h_src [B, dim_embed]:
         the score of forward() for every (source, candidate) pair, of which the k best
         candidates per source (ops.EdgeRank.values / .indices, [B, k]) are kept and, with
@@ -574,6 +575,14 @@ class EdgePredictor(nn.Module):
         all in range, not checked), the counts .greater / .equal of the OTHER candidates that
         beat / tie the target's score; .rank is 1 + greater + equal / 2.  The target is left
         out of its own row's list too (the filtered setting).  No gradient, no state.
+
+        `exclude` (int64 [B, (C + 63) // 64], ops.edge_rank's bit layout, what
+        DynamicGraph.seen_mask returns) leaves a per-source set of candidates out of the list and
+        the counts as well.  The target's score is still taken from its own row of h_cand, so
+        with `target` the rank is the target's rank among the candidates that are neither
+        excluded nor the target, also when the target's own bit is set -- the usual case on a
+        stream with repeat interactions, and the filtered setting of the temporal
+        link-prediction protocols.
 
         float32 rows on the GPU with `fused_score` take ops.edge_rank, whose scores are those of
         ops.edge_score bit for bit: the target's score is ops.edge_score's and is compared
@@ -587,17 +596,22 @@ class EdgePredictor(nn.Module):
             ref = None
             if target is not None:
                 ref = ops.edge_score(src_p, cand_p[target], w, b)
-            return ops.edge_rank(src_p, cand_p, w, b, k=k, ref_score=ref, skip=target)
+            return ops.edge_rank(src_p, cand_p, w, b, k=k, ref_score=ref, skip=target,
+                                 exclude=exclude)
         return _rank_torch(src_p.float(), cand_p.float(), w.float().reshape(-1), b.float(), k,
-                           target, self._RANK_TORCH_CHUNK)
+                           target, self._RANK_TORCH_CHUNK, exclude)
 
 
-def _rank_torch(src, cand, w, b, k, target, step):
+def _rank_torch(src, cand, w, b, k, target, step, exclude=None):
     """ops.edge_rank's semantics as a torch expression, `step` candidates at a time."""
     (B, D), Cn = src.shape, cand.shape[0]
     if not 0 <= k <= min(Cn, ops.EDGE_RANK_MAX_K):
         raise ValueError("k must be in [0, min(C, {})] with C = {}, got {}".format(
             ops.EDGE_RANK_MAX_K, Cn, k))
+    if exclude is not None and (exclude.dtype != torch.int64 or
+                                tuple(exclude.shape) != (B, (Cn + 63) // 64)):
+        raise ValueError("exclude must be int64 [B, (C + 63) // 64] = [{}, {}], got {} {}".format(
+            B, (Cn + 63) // 64, exclude.dtype, tuple(exclude.shape)))
     dev = src.device
     ref = None
     if target is not None:
@@ -614,6 +628,8 @@ def _rank_torch(src, cand, w, b, k, target, step):
         ids = torch.arange(a, a + c.shape[0], device=dev).expand(B, -1)
         keep = torch.ones_like(ids, dtype=torch.bool) if target is None \
             else ids != target[:, None]
+        if exclude is not None:
+            keep = keep & (((exclude[:, ids[0] >> 6] >> (ids[0] & 63)) & 1) == 0)
         if ref is not None:
             greater += ((score > ref[:, None]) & keep).sum(1)
             equal += ((score == ref[:, None]) & keep).sum(1)

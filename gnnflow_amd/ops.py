@@ -848,7 +848,8 @@ class EdgeRank(NamedTuple):
 
 def edge_rank(src: torch.Tensor, cand: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
               k: int = 0, ref_score: Optional[torch.Tensor] = None,
-              skip: Optional[torch.Tensor] = None) -> EdgeRank:
+              skip: Optional[torch.Tensor] = None,
+              exclude: Optional[torch.Tensor] = None) -> EdgeRank:
     """Scores every source against ONE shared candidate set and keeps, per source, the k best
     candidates and the number of candidates that beat or tie a reference score:
 
@@ -862,20 +863,25 @@ def edge_rank(src: torch.Tensor, cand: torch.Tensor, weight: torch.Tensor, bias:
     relu turns it into 0).
 
     src: [B, D]; cand: [C, D]; weight: [D] or [1, D]; bias: [1]; ref_score: [B] or [B, 1] or
-    None; all float32 on one GPU.  skip: int64 [B] or None.  0 <= k <= min(C, EDGE_RANK_MAX_K),
-    D >= 1, 1 <= C < 2**31.  Inputs are detached: there is no autograd.  Row slices are taken as
+    None; all float32 on one GPU.  skip: int64 [B] or None.  exclude: int64 [B, W] with
+    W = (C + 63) // 64, or None.  0 <= k <= min(C, EDGE_RANK_MAX_K), D >= 1, 1 <= C < 2**31.  Inputs are detached: there is no autograd.  Row slices are taken as
     they are; any other non-contiguous input is copied.
 
     Returns EdgeRank(values, indices, greater, equal):
       values, indices [B, k]  the k best candidates of each source, score descending, then
           candidate index ascending among equal scores.  A NaN score sorts below -inf (by
           ascending index among NaNs) and is returned as NaN.  A row with fewer than k candidates
-          left (k == C with a valid skip) ends in (-inf, -1).  [B, 0] when k == 0.
+          left (k == C with a valid skip, or exclusions) ends in (-inf, -1).  [B, 0] when k == 0.
       greater, equal [B]  the candidates with score > / == ref_score[i]; a NaN score is neither,
           and a NaN ref_score gives two zeros.  None without ref_score.  .rank is
           1 + greater + equal / 2.
     Candidate skip[i] is left out of row i's counts and list (the "filtered" setting: the true
     destination); a value outside [0, C) excludes nothing.  skip works without ref_score too.
+    Candidate c is left out of row i in exactly the same way when bit c % 64 of
+    exclude[i, c // 64] is set: a per-source SET of candidates, such as the nodes the source has
+    already interacted with (DynamicGraph.seen_mask returns this layout).  skip and exclude may
+    both be given; bits at positions >= C are ignored; a row with every candidate excluded gets a
+    list of (-inf, -1) and, with ref_score, zero counts.
 
     Runs on the current stream and never synchronises; selection under a total order and
     integer counts: the same inputs give the same bits.
@@ -883,18 +889,21 @@ def edge_rank(src: torch.Tensor, cand: torch.Tensor, weight: torch.Tensor, bias:
     A candidate set too large for one call is cut into shards cand[a:b]: the counts of the
     shards add, and the lists (indices + a) are concatenated and go through one
     torch.topk(values, k) -- after which equal scores are no longer in index order across
-    shards, unless the shards' lists are merged by (value, index) instead."""
+    shards, unless the shards' lists are merged by (value, index) instead.  A shard cand[a:b]
+    with a % 64 == 0 takes exclude[:, a // 64:(b + 63) // 64]."""
     named = (("src", src), ("cand", cand), ("weight", weight), ("bias", bias))
     if ref_score is not None:
         named += (("ref_score", ref_score),)
-    for name, x in named + ((("skip", skip),) if skip is not None else ()):
+    ints = tuple((name, x) for name, x in (("skip", skip), ("exclude", exclude)) if x is not None)
+    for name, x in named + ints:
         if not isinstance(x, torch.Tensor):
             raise TypeError("{} must be a tensor, got {}".format(name, type(x).__name__))
     for name, x in named:
         if x.dtype != torch.float32:
             raise TypeError("edge_rank computes in float32, {} is {}".format(name, x.dtype))
-    if skip is not None and skip.dtype != torch.int64:
-        raise TypeError("skip must be int64, got {}".format(skip.dtype))
+    for name, x in ints:
+        if x.dtype != torch.int64:
+            raise TypeError("{} must be int64, got {}".format(name, x.dtype))
     if isinstance(k, bool) or not isinstance(k, int):
         raise TypeError("k must be an int, got {}".format(type(k).__name__))
     if src.dim() != 2 or cand.dim() != 2:
@@ -922,7 +931,10 @@ def edge_rank(src: torch.Tensor, cand: torch.Tensor, weight: torch.Tensor, bias:
             B, tuple(ref_score.shape)))
     if skip is not None and tuple(skip.shape) != (B,):
         raise ValueError("skip must be [B] with B = {}, got {}".format(B, tuple(skip.shape)))
-    for name, x in named[1:] + ((("skip", skip),) if skip is not None else ()):
+    if exclude is not None and tuple(exclude.shape) != (B, (Cn + 63) // 64):
+        raise ValueError("exclude must be [B, (C + 63) // 64] = [{}, {}], got {}".format(
+            B, (Cn + 63) // 64, tuple(exclude.shape)))
+    for name, x in named[1:] + ints:
         if x.device != src.device:
             raise ValueError("{} is on {}, src on {}".format(name, x.device, src.device))
     if src.device.type != "cuda":
@@ -932,6 +944,7 @@ def edge_rank(src: torch.Tensor, cand: torch.Tensor, weight: torch.Tensor, bias:
     w, b = weight.detach().reshape(D).contiguous(), bias.detach().contiguous()
     ref = None if ref_score is None else ref_score.detach().reshape(B).contiguous()
     sk = None if skip is None else skip.detach().contiguous()
+    ex = None if exclude is None else exclude.detach().contiguous()
     values = torch.empty((B, k), dtype=torch.float32, device=dev)
     indices = torch.empty((B, k), dtype=torch.int64, device=dev)
     greater = equal = None
@@ -944,10 +957,10 @@ def edge_rank(src: torch.Tensor, cand: torch.Tensor, weight: torch.Tensor, bias:
         _capi.check(lib.gf_edge_rank_scratch(B, Cn, k, C.byref(nbytes)))
         scratch = torch.empty((nbytes.value + 7) // 8, dtype=torch.int64, device=dev)
         with torch.cuda.device(dev):
-            _capi.check(lib.gf_edge_rank(
+            _capi.check(lib.gf_edge_rank_masked(
                 s.data_ptr(), c.data_ptr(), w.data_ptr(), b.data_ptr(), B, Cn, D, k, _ptr(ref),
-                _ptr(sk), scratch.data_ptr(), scratch.numel() * 8, _ptr(values), _ptr(indices),
-                _ptr(greater), _ptr(equal), dev.index, _stream(dev)))
+                _ptr(sk), _ptr(ex), scratch.data_ptr(), scratch.numel() * 8, _ptr(values),
+                _ptr(indices), _ptr(greater), _ptr(equal), dev.index, _stream(dev)))
     return EdgeRank(values, indices, greater, equal)
 
 

@@ -1202,6 +1202,19 @@ GF_API int gf_edge_rank(const float* d_src, const float* d_cand, const float* d_
                         const float* d_ref_score, const int64_t* d_skip, void* d_scratch,
                         size_t scratch_bytes, float* d_values, int64_t* d_indices,
                         int64_t* d_greater, int64_t* d_equal, int device, void* stream);
+/* gf_edge_rank with a per-source set of candidates to leave out.  d_exclude: uint64
+ * [num_src, W], W = ceil(num_cand / 64), row-major, contiguous; candidate c is left out of row
+ * i's counts and list, exactly as d_skip[i] is, when bit c % 64 of word [i, c / 64] is set.
+ * Bits at positions >= num_cand are ignored.  d_skip and d_exclude may both be given.  A row
+ * with every candidate excluded gets a list of (-inf, -1) and zero counts.  d_exclude NULL is
+ * gf_edge_rank, which forwards here with NULL; the scratch is gf_edge_rank_scratch's.  What
+ * gf_graph_seen_mask writes is a d_exclude. */
+GF_API int gf_edge_rank_masked(const float* d_src, const float* d_cand, const float* d_w,
+                               const float* d_bias, size_t num_src, size_t num_cand, size_t dim,
+                               size_t k, const float* d_ref_score, const int64_t* d_skip,
+                               const uint64_t* d_exclude, void* d_scratch, size_t scratch_bytes,
+                               float* d_values, int64_t* d_indices, int64_t* d_greater,
+                               int64_t* d_equal, int device, void* stream);
 
 /* The loss of a link-prediction step from the logits d_pos [num_pos] of its true edges and
  * d_neg [num_neg] of its negative ones: BCE-with-logits of d_pos against 1 plus that of d_neg
@@ -1373,6 +1386,33 @@ GF_API int gf_batch_hist_negatives(const gf_graph* g, const int64_t* d_src, cons
                                    uint64_t seed, uint64_t epoch, uint64_t first_row,
                                    int64_t* d_roots, size_t capacity, uint64_t* d_filled,
                                    int device, void* stream);
+
+/* Which of num_cand candidate nodes has each of num_rows sources already met.  Row i has source
+ * s = d_src[i] and time t = d_ts[i].  Its considered edges:
+ * - e = table[s]; c = the number of x in ts_pool[e.start .. e.start + e.size) with x < t, strict
+ *   and with the float < operator (a NaN t gives c = 0), over the live range only, as in
+ *   gf_batch_hist_negatives;
+ * - n = c, or min(c, max_history) when max_history > 0: the NEWEST n of those c edges,
+ *   nbr_pool[e.start + c - n .. e.start + c).
+ * The candidates are given sorted: d_sorted_ids [num_cand] ascending (duplicates allowed, ids
+ * unknown to the graph allowed) and d_perm [num_cand], the position of each in the caller's own
+ * order (what a sort returns as its permutation; an entry outside [0, num_cand) sets nothing).
+ * For every considered edge and every j with d_sorted_ids[j] == its dst, bit d_perm[j] % 64 of
+ * word d_mask[i * W + d_perm[j] / 64] is set, W = ceil(num_cand / 64).  d_mask is uint64
+ * [num_rows, W] and must be ZEROED by the caller: bits are ORed in (atomic OR on the words, the
+ * only atomic; the same inputs give the same bits) and bits at positions >= num_cand are never
+ * set.  s < 0, s >= table_len or c == 0: the row is not touched.  On a graph built with reverse
+ * edges the history includes nodes that pointed at s.  The layout is gf_edge_rank_masked's
+ * d_exclude.
+ * One launch on `stream`, plain loads, a wave per row; the cost is proportional to the edges
+ * considered (a hub's whole history when max_history == 0).  Ordering against
+ * gf_graph_add_edges / gf_graph_offload_old_blocks: as gf_batch_hist_negatives.
+ * A NULL graph, a NULL buffer with num_rows > 0, num_cand == 0 or >= 2^31, num_rows >= 2^31:
+ * GF_ERR_INVALID_ARGUMENT, nothing launched.  num_rows == 0: GF_OK, nothing launched. */
+GF_API int gf_graph_seen_mask(const gf_graph* g, const int64_t* d_src, const float* d_ts,
+                              size_t num_rows, const int64_t* d_sorted_ids, const int64_t* d_perm,
+                              size_t num_cand, size_t max_history, uint64_t* d_mask, int device,
+                              void* stream);
 
 /* ---- measurement support (bench.py) ---------------------------------------- */
 /* Accumulated device time of a kernel family since the last reset, measured with
