@@ -16,7 +16,8 @@
 // blockIdx.y selects the context, so the node and edge caches advance in the same launches.
 // The parts, each a translation unit of its own around feature_cache_ctx.hpp:
 //   gather.hip         the gather (the kernel that moves ~all the bytes)
-//   cache_lru.hip      LRU: the eviction order as a list (one or two launches) or a queue
+//   cache_lru.hip      LRU: the eviction order as a list (two launches; cache_lru_fused.hip:
+//                      one) or a queue (cache_lru_queue.hip), the host side of that list
 //   cache_select.hip   LFU / FIFO: histogram select of the victims
 //   cache_staging.hip  staging ring for host-resident tables
 //   cache_pull.hip     sharded feature tables: plan, serve, fetch
@@ -75,29 +76,6 @@ inline bool pointer_on_device(const void* p) {
     return false;
   }
   return attr.type == hipMemoryTypeDevice;
-}
-
-// chunks of kRowTile queue entries the victim walk covers behind the head: twice the rows
-// of the block (at most that many victims are needed) + 2
-inline size_t victim_chunks(size_t n) { return (2 * n + kRowTile - 1) / kRowTile + 2; }
-
-// entries of the victim staging arrays: list form — the tiles at the front of the list (at most
-// the whole list, at most kMaxStageTiles); queue form — the chunks behind the head
-inline size_t stage_entries(size_t n, size_t capacity) {
-  const size_t list_tiles = (capacity + kRowTile - 1) / kRowTile;
-  const size_t list_form = std::min<size_t>(std::min(list_tiles, victim_chunks(n)), kMaxStageTiles);
-  return std::max(list_form, victim_chunks(n)) * kRowTile + n;
-}
-
-// fused list update: entries of the staged front tiles (the ids they hold; the slots share
-// the v_slot / v_pos arrays): at most min(capacity, rows) list positions, in whole tiles
-inline size_t fuse_stage_entries(size_t n, size_t capacity) {
-  return (std::min(n, capacity) / kFuseTile + 2) * kFuseTile;
-}
-
-inline bool lru_fused_enabled() {
-  const char* e = std::getenv("GNNFLOW_LRU_FUSED");   // 0: list scan + list install (A/B, tests)
-  return e ? std::atoi(e) != 0 : true;
 }
 
 }  // namespace
@@ -329,49 +307,7 @@ void FeatureCache::resize(size_t new_num_ids, size_t new_capacity, const float* 
     if (table_on_device_) set_staging(0, 0);
     else set_staging(gens, rows);
   }
-  if (policy_ == GF_CACHE_LRU && new_capacity > old_capacity) {
-    // the new (empty) slots are the first to be refilled, in slot order: they go to the front
-    // of the list, the old entries follow in their order
-    QueueState qs;
-    GF_HIP(hipMemcpyAsync(&qs, qstate_.data(), sizeof(qs), hipMemcpyDeviceToHost, stream));
-    GF_HIP(hipStreamSynchronize(stream));
-    DeviceBuffer& cur = (qs.parity & 1u) ? queue_alt_ : queue_;
-    queue_form_ = new_capacity >= queue_min_capacity();
-    queue_cap_ = queue_form_ ? new_capacity + new_capacity / 2 + 64 : new_capacity;
-    DeviceBuffer na, nb;
-    na.reserve((queue_cap_ + 16) * sizeof(uint32_t));
-    nb.reserve((queue_cap_ + 16) * sizeof(uint32_t));
-    lru_list_fill(na.as<uint32_t>(), static_cast<uint32_t>(old_capacity),
-                  static_cast<uint32_t>(new_capacity - old_capacity), cur.as<uint32_t>(),
-                  static_cast<uint32_t>(old_capacity), stream);
-    const QueueState fresh{0u, 0u, 0u, static_cast<uint32_t>(new_capacity), 0u, 0u};
-    GF_HIP(hipMemcpyAsync(qstate_.data(), &fresh, sizeof(fresh), hipMemcpyHostToDevice, stream));
-    GF_HIP(hipStreamSynchronize(stream));
-    std::swap(queue_, na);
-    std::swap(queue_alt_, nb);
-    tail_bound_ = new_capacity;
-    {
-      DeviceBuffer np;
-      np.reserve(new_capacity * sizeof(uint32_t));
-      std::swap(qpos_, np);
-    }
-    if (queue_form_) {
-      GF_REQUIRE(queue_cap_ < (size_t{1} << 30), "LRU queue form: more than 2^30 queue positions");
-      DeviceBuffer nh, nc, nbits;
-      nh.reserve(2 * qbits_bytes(queue_cap_));
-      nbits.reserve(qbits_bytes(queue_cap_));
-      GF_HIP(hipMemsetAsync(nbits.data(), 0, qbits_bytes(queue_cap_), stream));
-      std::swap(qbits_, nbits);
-      const size_t tiles = (queue_cap_ + kRowTile - 1) / kRowTile + 1;
-      const size_t groups = (tiles + kQGroup - 1) / kQGroup + 1;
-      nc.reserve(align_up(tiles * (kRowTile / 64) * 8, 256) + align_up(tiles * 4, 256) +
-                 align_up(groups * 4, 256) + 256);
-      std::swap(wsnap_, nh);
-      std::swap(compact_, nc);
-    }
-    index_queue(stream);
-    GF_HIP(hipStreamSynchronize(stream));
-  }
+  if (policy_ == GF_CACHE_LRU && new_capacity > old_capacity) grow_queue(old_capacity, stream);
 }
 
 void FeatureCache::reserve_workspace(size_t n, hipStream_t stream) {
@@ -440,84 +376,7 @@ void FeatureCache::prepare(const int64_t* d_ids, size_t n, float* d_out, bool up
   c.ctr_next = state_.as<Counters>() + ((ring_pos_ + 1) % kRing);
   ring_pos_++;
   c.stats = d_stats;
-  if (c.update && policy_ == GF_CACHE_LRU) {
-    const size_t row_tiles = (n + kLruRows - 1) / kLruRows;
-    c.tiles_per_wg = static_cast<uint32_t>((row_tiles + kMaxRowTiles - 1) / kMaxRowTiles);
-    c.inst_rows = n >= 65536 ? kWide : kInstRows;
-    c.queue[0] = queue_.as<uint32_t>();
-    c.queue[1] = queue_alt_.as<uint32_t>();
-    c.qstate = qstate_.as<QueueState>();
-    {
-      const size_t stage = align_up(stage_entries(ws_rows_, capacity_) * 4, 256);
-      c.v_slot = reinterpret_cast<uint32_t*>(qscratch);
-      c.v_pos = reinterpret_cast<uint32_t*>(qscratch + stage);
-      c.v_count = reinterpret_cast<uint32_t*>(qscratch + 2 * stage);
-      const size_t vc = align_up((victim_chunks(ws_rows_) + 2) * 4, 256) + 256;
-      const size_t fst = align_up(fuse_stage_entries(ws_rows_, capacity_) * 8, 256);
-      c.v_old = reinterpret_cast<long long*>(qscratch + 2 * stage + vc);
-      c.v_hold = reinterpret_cast<long long*>(qscratch + 2 * stage + vc + fst);
-      // list form: the tiles at the front of the list that stage their entries
-      const size_t list_tiles = (capacity_ + kRowTile - 1) / kRowTile;
-      const size_t st = std::min(list_tiles, (2 * n + kRowTile - 1) / kRowTile + 2);
-      // more tiles than kMaxStageTiles (the install kernel keeps the tile prefix in LDS): the
-      // one-workgroup walk
-      c.stage_tiles = st <= kMaxStageTiles ? static_cast<uint32_t>(st) : 0u;
-      c.stage_min = kStageMinWant;
-      c.stage_hits = st == list_tiles ? 1 : 0;
-    }
-    c.qpos = qpos_.as<uint32_t>();
-    if (queue_form_) {
-      if (n <= capacity_ / 4 && victim_chunks(n) + 1 <= kMaxVChunks) {
-        // appends at most n entries (#distinct hit slots + #victims <= rows)
-        if (tail_bound_ + n > queue_cap_) compact_queue(stream);
-        tail_bound_ += n;
-        c.qmode = 1;
-        c.qbits = qbits_.as<uint32_t>();
-        c.wsnap = wsnap_.as<uint2>();
-        const size_t bit_tiles = ((queue_cap_ + 64) / 32 + kBitTile - 1) / kBitTile + 1;
-        c.q_group = static_cast<uint32_t>((bit_tiles + kMaxBitGroups - 1) / kMaxBitGroups);
-        static const uint32_t forced_group = [] {
-          const char* e = std::getenv("GNNFLOW_LRU_QUEUE_GROUP");   // tests: the > 89 M-slot path
-          return e ? static_cast<uint32_t>(std::atoi(e)) : 0u;
-        }();
-        c.q_group = std::max(c.q_group, forced_group);
-        c.v_chunks = static_cast<uint32_t>(victim_chunks(n));
-        c.stage_tiles = 0;
-      } else {
-        // a block this large is cheaper in the list form, on the dense list (whose install
-        // leaves qpos[] = the new list positions, which is what the queue form expects)
-        compact_queue(stream);
-        ++list_form_updates_;
-      }
-    }
-    // list form in one launch (lru_list_fused_kernel) where its LDS tables and granule arrays fit
-    // 256 block rows per row workgroup while that gives <= kFuseMaxRowWgs of them: the rows a
-    // small cache installs belong to the FIRST representatives, i.e. to the first few row
-    // workgroups, which then copy all of its rows (GDELT-scale node cache, 3 336 slots, 218 k-row
-    // blocks: 57 us per update with 1 024 rows per workgroup — four workgroups copied 5.5 MB)
-    // Without a row mirror nothing is copied, and 1 024 rows per workgroup keep the launch small
-    // enough for every count and row workgroup to be resident from the start (1 024-thread
-    // workgroups: one per CU; with 256 rows the headline's row workgroups entered 2.6 us into the
-    // launch, behind the count workgroups — profiles/r06_lru_hop_trace.txt).
-    c.fuse_rows = (n > size_t{kInstRows} * kFuseMaxRowWgs || !mirror_) ? kWide : kInstRows;
-    if (!c.qmode && lru_fused_enabled() &&
-        (capacity_ + kFuseTile - 1) / kFuseTile <= kFuseMaxTiles &&
-        (n + c.fuse_rows - 1) / c.fuse_rows <= kFuseMaxRowWgs) {
-      if (!granules_.data()) {
-        granules_.reserve((kFuseMaxTiles + kFuseMaxRowWgs) * sizeof(unsigned long long), 0, stream);
-        GF_HIP(hipMemsetAsync(granules_.data(), 0, granules_.bytes(), stream));
-      }
-      if (fuse_tag_ == 0xFFFFFFFFu) {   // the tags wrap: no granule may carry one from last time round
-        GF_HIP(hipMemsetAsync(granules_.data(), 0, granules_.bytes(), stream));
-        fuse_tag_ = 0;
-      }
-      c.fused = 1;
-      c.trace = trace_.data() ? trace_.as<unsigned long long>() : nullptr;
-      c.fuse_tag = ++fuse_tag_;
-      c.g_cnt = granules_.as<unsigned long long>();
-      c.g_row = c.g_cnt + kFuseMaxTiles;
-    }
-  }
+  if (c.update && policy_ == GF_CACHE_LRU) fill_lru_ctx(c, n, qscratch, stream);
 }
 
 // One block of Cache.fetch_feature (cache.py:269-323 / :326-400)

@@ -49,7 +49,7 @@ void gather_rows_indexed(const float* d_rows, size_t num_local_rows, size_t dim,
                          float* d_out, uint32_t* d_flag, int device, hipStream_t stream);
 void fetch_blocks_pulled(FeatureCache* node, FeatureCache* edge, const gf_fetch_pulled_desc* descs,
                          size_t n, hipStream_t stream);
-// Granules of the fused LRU list update that a waiter had to recompute itself (cache_lru.hip)
+// Granules of the fused LRU list update that a waiter had to recompute itself (cache_lru_fused.hip)
 uint64_t lru_recounts();
 
 // One fetch round over sharded feature tables as one native call (gf_pull_round): the buffers
@@ -126,7 +126,12 @@ class FeatureCache {
   // the host-side epoch / counter ring (LRU: schedules a queue compaction when due)
   void prepare(const int64_t* d_ids, size_t n, float* d_out, bool update, uint32_t* d_stats,
                Ctx* ctx_out, hipStream_t stream);
-  void init_queue(hipStream_t stream);   // LRU list (cache_lru.hip header)
+  // LRU list, host side (cache_lru.hip): a fresh list in slot order; the list after Cache.resize;
+  // the list's buffers (the one place that sizes them); the LRU part of prepare()'s context
+  void init_queue(hipStream_t stream);
+  void grow_queue(size_t old_capacity, hipStream_t stream);
+  void alloc_queue(size_t capacity, hipStream_t stream, DeviceBuffer* old_lists);
+  void fill_lru_ctx(Ctx& c, size_t n, char* qscratch, hipStream_t stream);
 
   size_t num_ids_, capacity_, dim_;
   const float* feats_;
@@ -144,7 +149,7 @@ class FeatureCache {
                                      // first; two buffers, the device knows which is current
   DeviceBuffer qstate_;    // LRU: parity of the current list buffer (+ head / tail of the
                            // queue form), device resident
-  // LRU of a large cache is kept as a queue with dead entries (cache_lru.hip, "LRU as a
+  // LRU of a large cache is kept as a queue with dead entries (cache_lru_queue.hip, "LRU as a
   // queue"): updates cost O(block rows), not O(capacity)
   DeviceBuffer qpos_;      // uint32[capacity]  position of the slot's (live) list / queue entry
   DeviceBuffer wsnap_;     // uint2 per word of qbits_: {word, hit entries before it in its tile}
@@ -162,7 +167,7 @@ class FeatureCache {
   DeviceBuffer ws_;        // per-fetch scratch
   size_t ws_rows_ = 0;
   DeviceBuffer granules_;  // LRU list form in one launch: {launch tag, count} per list tile / row
-                           // workgroup (cache_lru.hip, lru_list_fused_kernel)
+                           // workgroup (cache_lru_fused.hip, lru_list_fused_kernel)
   uint32_t fuse_tag_ = 0;  // tag of the last such launch: unique per cache, never reset
   DeviceBuffer trace_;     // gf_debug_lru_trace
   uint32_t epoch_ = 0;     // fetches with update so far (host side; kernel argument)

@@ -1,5 +1,5 @@
 // What the translation units of the feature cache share (gather.hip, cache_staging.hip,
-// cache_pull.hip, cache_select.hip, cache_lru.hip, feature_cache.hip): the kernel-argument
+// cache_pull.hip, cache_select.hip, cache_lru*.hip, feature_cache.hip): the kernel-argument
 // structs, the tile / bin / ring constants, the device helpers more than one of them uses and
 // the launch function of each part.  Private to those files.
 #pragma once
@@ -36,7 +36,7 @@ constexpr uint32_t kMaxStageTiles = 1024;   // LRU list form: list tiles that st
 constexpr uint32_t kBitTile = 4096;         // LRU queue form: words of the hit bitmap per tile (kWide x 4)
 constexpr uint32_t kMaxBitGroups = 1024;    // ... entries of the install kernel's LDS prefix over the tiles
 constexpr uint32_t kMaxVChunks = 2048;      // LRU queue form: victim chunks (+ the walk's) the LDS prefix holds
-// LRU list form in one launch (cache_lru.hip, lru_list_fused_kernel)
+// LRU list form in one launch (cache_lru_fused.hip, lru_list_fused_kernel)
 constexpr uint32_t kFuseTile = kWide;         // list entries per count / write tile
 constexpr uint32_t kFuseMaxTiles = 2048;      // list tiles (LDS prefix arrays): <= 2 M slots
 constexpr uint32_t kFuseMaxRowWgs = 1024;     // row workgroups: <= 1 M block rows
@@ -124,7 +124,7 @@ struct Ctx {
   QueueState* qstate;       // LRU: which buffer is current, device resident
   uint32_t tiles_per_wg;    // LRU: row tiles per scan workgroup (1 unless > 1M rows)
   uint32_t inst_rows;       // LRU: block rows per install workgroup (kInstRows or kWide)
-  // LRU of a LARGE cache (queue form, see "LRU as a queue" below); qmode == 0: list form
+  // LRU of a LARGE cache (queue form, see "LRU as a queue", cache_lru_queue.hip); qmode == 0: list form
   int qmode;                // this update appends to the queue instead of rewriting the list
   uint32_t* qpos;           // [capacity] position of the slot's live queue entry
   uint32_t* qbits;          // one bit per queue position: entry of a slot hit by this block
@@ -323,10 +323,57 @@ inline size_t queue_min_capacity() {
   return v ? static_cast<size_t>(std::atoll(v)) : (size_t{1} << 19);
 }
 
+// entries per list buffer: the list itself, or the queue with room for dead entries
+// (FeatureCache::alloc_queue)
+inline size_t lru_queue_cap(size_t capacity, bool queue_form) {
+  return queue_form ? capacity + capacity / 2 + 64 : capacity;
+}
+
 // bitmap over the queue positions, in whole tiles of kRowTile words (+ one tile)
 inline size_t qbits_bytes(size_t queue_cap) {
   const size_t words = (queue_cap + 64 + 31) / 32;
   return ((words + kRowTile - 1) / kRowTile + 1) * kRowTile * sizeof(uint32_t);
+}
+
+// Queue form: tiles of kBitTile words of that bitmap (32 queue positions per word; the tail is
+// below queue_cap + 64).  Of the capacity alone: the launch sizes its grid from the contexts,
+// which carry the capacity and not queue_cap, and must cover what the context fill laid out.
+inline size_t lru_bit_tiles(size_t capacity) {
+  return ((lru_queue_cap(capacity, true) + 64) / 32 + kBitTile - 1) / kBitTile + 1;
+}
+
+// Scratch of the queue compaction (cache_lru_queue.hip), byte offsets: one live bit per queue
+// position, the live entries per tile of kRowTile positions and per group of kQGroup tiles, the
+// kernels' state.  FeatureCache::alloc_queue reserves `bytes`, compact_queue walks the offsets.
+struct CompactLayout { size_t live_bits, tile_cnt, group_sum, state, bytes; };
+inline CompactLayout compact_layout(size_t queue_cap) {
+  const size_t tiles = (queue_cap + kRowTile - 1) / kRowTile + 1;
+  const size_t groups = (tiles + kQGroup - 1) / kQGroup + 1;
+  CompactLayout l;
+  l.live_bits = 0;
+  l.tile_cnt = l.live_bits + align_up(tiles * (kRowTile / 64) * 8, 256);
+  l.group_sum = l.tile_cnt + align_up(tiles * 4, 256);
+  l.state = l.group_sum + align_up(groups * 4, 256);
+  l.bytes = l.state + 256;
+  return l;
+}
+
+// chunks of kRowTile queue entries the victim walk covers behind the head: twice the rows
+// of the block (at most that many victims are needed) + 2
+inline size_t victim_chunks(size_t n) { return (2 * n + kRowTile - 1) / kRowTile + 2; }
+
+// entries of the victim staging arrays: list form — the tiles at the front of the list (at most
+// the whole list, at most kMaxStageTiles); queue form — the chunks behind the head
+inline size_t stage_entries(size_t n, size_t capacity) {
+  const size_t list_tiles = (capacity + kRowTile - 1) / kRowTile;
+  const size_t list_form = std::min<size_t>(std::min(list_tiles, victim_chunks(n)), kMaxStageTiles);
+  return std::max(list_form, victim_chunks(n)) * kRowTile + n;
+}
+
+// fused list update: entries of the staged front tiles (the ids they hold; the slots share
+// the v_slot / v_pos arrays): at most min(capacity, rows) list positions, in whole tiles
+inline size_t fuse_stage_entries(size_t n, size_t capacity) {
+  return (std::min(n, capacity) / kFuseTile + 2) * kFuseTile;
 }
 
 // rows per wave: 64 for big blocks; fewer for small ones so the block still spreads
@@ -347,13 +394,12 @@ inline uint32_t pick_tile_rows(size_t n) {
 Ctx plain_ctx(const float* feats, size_t num_rows, size_t dim, const int64_t* ids, size_t n,
               float* out);
 void launch_gather(Round& r, hipStream_t stream);
-// cache_lru.hip: the LRU contexts' update (list form in one or two launches, queue form);
+// cache_lru.hip: the LRU contexts' update (list form in one or two launches, queue form: it
+// dispatches to cache_lru_fused.hip and cache_lru_queue.hip through cache_lru_dev.hpp);
 // own_events: the round's only update launch is the fused one, which then carries the profile's
 // dispatch events itself
 void launch_lru_update(const Round& r, hipStream_t stream, bool own_events);
-void lru_fuse_spins_from_env(int device);
-void lru_list_fill(uint32_t* list, uint32_t first, uint32_t prefix, const uint32_t* old,
-                   uint32_t old_n, hipStream_t stream);
+void lru_fuse_spins_from_env(int device);   // cache_lru_fused.hip
 // cache_select.hip: the LFU / FIFO contexts' update
 void launch_select_update(const Round& r, hipStream_t stream);
 // feature_cache.hip: one round — the gather, then the updates
