@@ -5,7 +5,7 @@ Drop-in for the hot path of jasperzhong/GNNFlow: `DynamicGraph`, `TemporalSample
 kernels (gfx950) behind the C ABI of include/gnnflow_hip.h.
 """
 from .data import DeviceBatchStream, DeviceDstSet
-from .dynamic_graph import DynamicGraph
+from .dynamic_graph import DynamicGraph, TemporalWalks
 from .metrics import LinkMetrics
 from .mfg import MFGBlock
 from .nn import (MLP, EdgePredictor, GATConv, GRUMemeoryUpdater, GRUMemoryUpdater, LinkLoss,
@@ -15,4 +15,4 @@ from .temporal_sampler import SamplingResult, TemporalSampler
 __all__ = ["DynamicGraph", "TemporalSampler", "SamplingResult", "MFGBlock", "SAGEConv", "GATConv",
            "TimeEncode", "TemporalAttentionLayer", "TransfomerAttentionLayer", "GRUMemoryUpdater",
            "GRUMemeoryUpdater", "EdgePredictor", "MLP", "LinkMetrics", "LinkLoss",
-           "DeviceDstSet", "DeviceBatchStream"]
+           "DeviceDstSet", "DeviceBatchStream", "TemporalWalks"]

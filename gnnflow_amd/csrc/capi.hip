@@ -1,10 +1,11 @@
 // extern "C" entry points of include/gnnflow_hip.h: thin, exception-free shims.  Here: the error
 // slot they all report through, the pid behind foreign_process(), the shims over free functions
-// (block ops, time encoding, edge score, link metrics, batch stream, debug counters).  Those over a handle: capi_{graph,sampler,cache,comm}.
+// (block ops, time encoding, edge score, link metrics, batch stream, walk encoding, debug counters).  Those over a handle: capi_{graph,sampler,cache,comm}.
 #include "batch_stream.hpp"
 #include "block_ops.hpp"
 #include "capi_handles.hpp"
 #include "partition.hpp"
+#include "temporal_walk.hpp"
 
 namespace gf {
 
@@ -574,6 +575,15 @@ int gf_dst_set_compact(const uint64_t* d_bitmap, size_t num_nodes, int64_t* d_id
   return guarded([&] {
     gf::dst_set_compact(d_bitmap, num_nodes, d_ids, ids_capacity, d_count, d_scratch,
                         scratch_bytes, device, as_stream(stream));
+  });
+}
+
+int gf_walk_position_counts(const int64_t* d_nodes, const int64_t* d_ref, size_t rows,
+                            size_t walks, size_t len1, size_t ref_walks, size_t ref_len1,
+                            int32_t* d_out, int device, void* stream) {
+  return guarded([&] {
+    gf::walk_position_counts(d_nodes, d_ref, rows, walks, len1, ref_walks, ref_len1, d_out,
+                             device, as_stream(stream));
   });
 }
 

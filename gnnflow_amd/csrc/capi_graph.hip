@@ -3,6 +3,7 @@
 #include "capi_handles.hpp"
 #include "hist_negatives.hpp"
 #include "seen_mask.hpp"
+#include "temporal_walk.hpp"
 
 extern "C" {
 
@@ -94,6 +95,19 @@ int gf_graph_seen_mask(const gf_graph* g, const int64_t* d_src, const float* d_t
     GF_G(g);
     gf::seen_mask(g->impl.view(), d_src, d_ts, num_rows, d_sorted_ids, d_perm, num_cand,
                   max_history, d_mask, device, as_stream(stream));
+  });
+}
+// reads the store's view NOW, as gf_batch_hist_negatives does
+int gf_graph_temporal_walks(const gf_graph* g, const int64_t* d_src, const float* d_ts,
+                            size_t num_rows, size_t num_walks, size_t length, size_t recency,
+                            size_t max_history, uint64_t seed, uint64_t epoch, uint64_t first_row,
+                            int64_t* d_nodes, int64_t* d_eids, float* d_times, int device,
+                            void* stream) {
+  return guarded([&] {
+    GF_G(g);
+    gf::temporal_walks(g->impl.view(), d_src, d_ts, num_rows, num_walks, length, recency,
+                       max_history, seed, epoch, first_row, d_nodes, d_eids, d_times, device,
+                       as_stream(stream));
   });
 }
 

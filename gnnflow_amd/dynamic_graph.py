@@ -2,7 +2,7 @@
 error behaviour as the reference's Python wrapper (gnnflow/dynamic_graph.py:8-204),
 over the C ABI (include/gnnflow_hip.h) instead of the `libgnnflow` pybind module."""
 import ctypes as C
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -43,6 +43,57 @@ def check_seen_mask_args(src, ts, cand_ids, max_history=0):
         if x.device != src.device:
             raise ValueError("{} is on {}, src on {}".format(name, x.device, src.device))
     return B, Cn
+
+
+WALK_MAX_LENGTH = 32      # GF_WALK_MAX_LENGTH
+WALK_MAX_RECENCY = 8      # GF_WALK_MAX_RECENCY
+
+
+class TemporalWalks(NamedTuple):
+    """What DynamicGraph.temporal_random_walk returns: B roots, W walks each, L steps.  Slots from
+    the step a walk ends on hold nodes = -1, eids = -1, times = 0."""
+    nodes: torch.Tensor      # int64 [B, W, L + 1]; nodes[:, :, 0] is the root
+    eids: torch.Tensor       # int64 [B, W, L]; the edge step j took
+    times: torch.Tensor      # float32 [B, W, L]; its timestamp
+
+
+def _int_arg(value, name, lo, hi):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+        raise TypeError("{} must be an int, got {}".format(name, type(value).__name__))
+    value = int(value)
+    if not lo <= value < hi:
+        raise ValueError("{} must be in [{}, {}), got {}".format(name, lo, hi, value))
+    return value
+
+
+def check_temporal_walk_args(src, ts, length, num_walks=1, recency=1, max_history=0, seed=0,
+                             epoch=0, first_row=0):
+    """Arguments of DynamicGraph.temporal_random_walk, checked before anything is launched or
+    allocated: the kernel takes raw pointers and trusts them.  Needs no device.
+    Returns (B, W, L)."""
+    for name, x, dtype in (("src", src, torch.int64), ("ts", ts, torch.float32)):
+        if not isinstance(x, torch.Tensor):
+            raise TypeError("{} must be a tensor, got {}".format(name, type(x).__name__))
+        if x.dtype != dtype:
+            raise TypeError("{} must be {}, got {}".format(name, dtype, x.dtype))
+    L = _int_arg(length, "length", 1, WALK_MAX_LENGTH + 1)
+    W = _int_arg(num_walks, "num_walks", 1, 2 ** 16)
+    _int_arg(recency, "recency", 1, WALK_MAX_RECENCY + 1)
+    _int_arg(max_history, "max_history", 0, 2 ** 64)
+    for name, x in (("seed", seed), ("epoch", epoch), ("first_row", first_row)):
+        _int_arg(x, name, 0, 2 ** 64)
+    for name, x in (("src", src), ("ts", ts)):
+        if x.dim() != 1:
+            raise ValueError("{} must be 1-D, got shape {}".format(name, tuple(x.shape)))
+    B = int(src.shape[0])
+    if int(ts.shape[0]) != B:
+        raise ValueError("src has {} rows, ts has {}".format(B, int(ts.shape[0])))
+    if B * W >= 2 ** 31:
+        raise ValueError("temporal_random_walk takes fewer than 2**31 walks per call, got "
+                         "{} x {}".format(B, W))
+    if ts.device != src.device:
+        raise ValueError("ts is on {}, src on {}".format(ts.device, src.device))
+    return B, W, L
 
 
 class DynamicGraph:
@@ -246,6 +297,66 @@ class DynamicGraph:
                     perm.data_ptr(), Cn, max_history, mask.data_ptr(), self._device,
                     _capi.current_stream(torch.device("cuda", self._device))))
         return mask
+
+    def temporal_random_walk(self, src: torch.Tensor, ts: torch.Tensor, length: int,
+                             num_walks: int = 1, *, recency: int = 1, max_history: int = 0,
+                             seed: int = 0, epoch: int = 0, first_row: int = 0) -> TemporalWalks:
+        """W = num_walks backward-in-time random walks of L = length steps from each root:
+        TemporalWalks(nodes int64 [B, W, L + 1], eids int64 [B, W, L], times float32 [B, W, L]).
+
+        Walk (i, w) starts at src[i] at time ts[i]; nodes[i, w, 0] = src[i] always.  A step goes
+        from the current node v at the current time t over one of the considered edges of v: its
+        live edges in the store whose timestamp is strictly below t (float <) and, when
+        max_history > 0, only the newest max_history of them.  The step writes the edge's
+        destination to nodes[i, w, j + 1], its id to eids[i, w, j] and its timestamp to
+        times[i, w, j], which become the next v and t.  A walk ends where v is negative or past
+        the node table or has no considered edge; every slot from that step on holds nodes = -1,
+        eids = -1, times = 0.  The exact rule, draws included, is in include/gnnflow_hip.h
+        (gf_graph_temporal_walks) and restated in numpy in tests/temporal_walk_ref.py.
+
+        - Time strictly decreases along a walk: no edge is taken twice, an edge at the current
+          time (a tie) is never followed, and a NaN time ends the walk at once.
+        - recency = 1 draws uniformly from the n considered edges.  recency = p (1 .. 8) takes
+          the maximum of p uniform draws, P(index <= k) = ((k + 1) / n) ** p counted from the
+          oldest: a power-law preference for recent edges.  Integer arithmetic only, so the
+          kernel is checked bit for bit.
+        - Draws are Philox words keyed by (seed, the root's global row first_row + i, w, epoch,
+          step), not by the root's place in the call: walking rows [a, b) with first_row = a
+          gives rows a .. b of walking everything; another seed or epoch gives other walks.  A
+          seed tag of their own keeps them independent of DeviceBatchStream's draws.  The p
+          draws of a step are keyed seed ^ (tag + a), a < p, so seeds that differ only in their
+          low five bits can key the same draws: tell seeds apart above those bits.
+        - "Live" and reverse edges as for seen_mask: edges that offload_old_blocks took are gone,
+          and on a graph built with reverse edges a walk also follows edges that pointed at its
+          node.
+
+        src: int64 [B], ts: float32 [B], on the graph's device; 1 <= length <= 32,
+        1 <= num_walks < 2**16, B * num_walks < 2**31, recency in 1 .. 8, max_history >= 0;
+        seed, epoch and first_row in [0, 2**64).  B == 0 returns empty tensors of these shapes
+        without a launch; a graph without nodes gives walks that all end on step 0.
+
+        One kernel (csrc/temporal_walk.hip, a lane per walk) on the current stream, memory from
+        torch, never synchronises.  Synchronise the streams that calls were launched on before
+        add_edges or offload_old_blocks, as for seen_mask.  ops.walk_position_counts encodes the
+        result for CAWN-style models."""
+        B, W, L = check_temporal_walk_args(src, ts, length, num_walks, recency, max_history,
+                                           seed, epoch, first_row)
+        dev = src.device
+        if dev.type != "cuda" or (dev.index is not None and dev.index != self._device):
+            raise ValueError("the graph is on device cuda:{}, the inputs on {}".format(
+                self._device, dev))
+        with torch.cuda.device(self._device):
+            nodes = torch.empty((B, W, L + 1), dtype=torch.int64, device=dev)
+            eids = torch.empty((B, W, L), dtype=torch.int64, device=dev)
+            times = torch.empty((B, W, L), dtype=torch.float32, device=dev)
+            if B:
+                s, t = src.detach().contiguous(), ts.detach().contiguous()
+                _capi.check(self._lib.gf_graph_temporal_walks(
+                    self._h, s.data_ptr(), t.data_ptr(), B, W, L, int(recency),
+                    int(max_history), int(seed), int(epoch), int(first_row),
+                    nodes.data_ptr(), eids.data_ptr(), times.data_ptr(), self._device,
+                    _capi.current_stream(torch.device("cuda", self._device))))
+        return TemporalWalks(nodes, eids, times)
 
     def _float(self, fn) -> float:
         v = C.c_float(0)

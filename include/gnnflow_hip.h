@@ -1414,6 +1414,78 @@ GF_API int gf_graph_seen_mask(const gf_graph* g, const int64_t* d_src, const flo
                               size_t num_cand, size_t max_history, uint64_t* d_mask, int device,
                               void* stream);
 
+/* Backward-in-time random walks over the temporal edge store: W = num_walks walks of L = length
+ * steps from each of num_rows roots.  Walk (i, w) starts at v_0 = d_src[i], t_0 = d_ts[i];
+ * d_nodes[i, w, 0] = d_src[i] always.  Step j = 0 .. L - 1:
+ * - v_j outside [0, table_len): the walk has ended.
+ * - e = table[v_j]; c = the number of x in ts_pool[e.start .. e.start + e.size) with x < t_j,
+ *   strict and with the float < operator (a NaN t_j gives c = 0), over the live range only, as in
+ *   gf_batch_hist_negatives.
+ * - n = c, or min(c, max_history) when max_history > 0: the NEWEST n of those c edges.  n == 0:
+ *   the walk has ended.
+ * - u_a = gf_philox4x32_10_first(seed ^ (GF_WALK_SEED_TAG + a), tid, (epoch << 8) + j) for
+ *   a < recency, tid = (first_row + i) * W + w; both words wrap mod 2^64.
+ * - x = the maximum over a of (uint64(u_a) * n) >> 32, so 0 <= x < n.
+ * - r = nbr_pool[e.start + (c - n) + x]: index 0 is the oldest edge considered, as in
+ *   gf_batch_hist_negatives (the reverse of get_temporal_neighbors' order).
+ * - d_nodes[i, w, j + 1] = r.dst, d_eids[i, w, j] = r.eid, d_times[i, w, j] = r.ts;
+ *   v_{j+1} = r.dst, t_{j+1} = r.ts.
+ * Every slot from the step a walk ends on holds d_nodes = -1, d_eids = -1, d_times = 0.  Every
+ * element of d_nodes (int64 [num_rows, W, L + 1]), d_eids (int64 [num_rows, W, L]) and d_times
+ * (float32 [num_rows, W, L]), row-major and contiguous, is written: they need no initialisation.
+ *
+ * Documented consequences.
+ * - Time strictly decreases along a walk: no edge is taken twice, an edge at the current time
+ *   (a tie) is never followed, and a walk from a NaN time ends on step 0.
+ * - recency == 1 is a uniform draw from the n edges considered; recency == p is the maximum of
+ *   p uniform draws, P(x <= k) = ((k + 1) / n)^p: a power-law preference for recent edges, in
+ *   integer arithmetic only.
+ * - A walk is keyed by its root's GLOBAL row first_row + i, not by its place in the call: rows
+ *   [a, b) walked with first_row = a are rows a .. b of everything walked with first_row = 0.
+ * - GF_WALK_SEED_TAG keeps the draws independent of gf_batch_assemble's and
+ *   gf_batch_hist_negatives' draws of the same tid.
+ * - The recency draws of a step are keyed seed ^ (GF_WALK_SEED_TAG + a).  Two seeds whose XOR is
+ *   the XOR of two of those tags (it fits the low five bits) key the same draws in another order,
+ *   and the maximum does not see the order: seeds that are meant to give independent walks must
+ *   differ above their low five bits.
+ * - On a graph built with reverse edges a walk also follows edges that pointed at its node.
+ * - A store without a node gives walks that all end on step 0.
+ *
+ * One launch on `stream`, one lane per walk, plain loads and stores, no atomics: the same inputs
+ * give the same bits.  Ordering against gf_graph_add_edges / gf_graph_offload_old_blocks: as
+ * gf_batch_hist_negatives.
+ * A NULL graph, a NULL buffer with num_rows > 0, length outside [1, GF_WALK_MAX_LENGTH],
+ * num_walks outside [1, 65535], recency outside [1, GF_WALK_MAX_RECENCY], num_rows * num_walks
+ * >= 2^31: GF_ERR_INVALID_ARGUMENT, nothing launched.  num_rows == 0: GF_OK, nothing launched. */
+#define GF_WALK_MAX_LENGTH 32
+#define GF_WALK_MAX_RECENCY 8
+#define GF_WALK_SEED_TAG 0x54454D5057414C4BULL /* "TEMPWALK" */
+GF_API int gf_graph_temporal_walks(const gf_graph* g, const int64_t* d_src, const float* d_ts,
+                                   size_t num_rows, size_t num_walks, size_t length,
+                                   size_t recency, size_t max_history, uint64_t seed,
+                                   uint64_t epoch, uint64_t first_row, int64_t* d_nodes,
+                                   int64_t* d_eids, float* d_times, int device, void* stream);
+
+/* The position-count ("anonymous") encoding of walks.  d_nodes is int64 [rows, walks, len1], the
+ * walks to encode (len1 = L + 1 nodes each); d_ref is int64 [rows, ref_walks, ref_len1], the walks
+ * to count in, which may be d_nodes itself; d_out is int32 [rows, walks, len1, ref_len1]; all
+ * row-major and contiguous:
+ *   d_out[i, w, j, p] = #{w' < ref_walks : d_ref[i, w', p] == d_nodes[i, w, j]}
+ *                       when d_nodes[i, w, j] >= 0, else 0.
+ * A negative entry (an ended slot of gf_graph_temporal_walks) encodes to zeros and is never
+ * counted.  Every element of d_out is written.  One launch on `stream`: a workgroup per row
+ * holds d_ref[i] in LDS (ref_walks * ref_len1 <= GF_WALK_MAX_REF_ENTRIES ids, 32 KB) and compares
+ * every entry of d_nodes[i] with every entry of it, walks * len1 * ref_walks * ref_len1 compares
+ * per row.  No atomics: the same inputs give the same bits.
+ * len1 or ref_len1 outside [1, GF_WALK_MAX_LENGTH + 1], ref_walks * ref_len1 >
+ * GF_WALK_MAX_REF_ENTRIES, rows >= 2^31, walks * len1 * ref_len1 >= 2^31, a NULL buffer that is
+ * needed: GF_ERR_INVALID_ARGUMENT, nothing launched.  rows == 0 or walks == 0: GF_OK, nothing
+ * launched. */
+#define GF_WALK_MAX_REF_ENTRIES 4096
+GF_API int gf_walk_position_counts(const int64_t* d_nodes, const int64_t* d_ref, size_t rows,
+                                   size_t walks, size_t len1, size_t ref_walks, size_t ref_len1,
+                                   int32_t* d_out, int device, void* stream);
+
 /* ---- measurement support (bench.py) ---------------------------------------- */
 /* Accumulated device time of a kernel family since the last reset, measured with
  * HIP events recorded around each launch on the launching stream.
