@@ -14,6 +14,10 @@
 // with the reference's exact allocation policy so that offload_old_blocks,
 // avg_linked_list_length and the memory counters keep their observable
 // block-granular behaviour.
+//
+// Implementation: edge_store_ingest.hip is add_edges (its phases, the block policy, the kernels
+// that write edges); edge_store.hip is everything else (lifetime, pools and fences, the node
+// table, offload, accessors); edge_store_internal.hpp is what the two share.
 #pragma once
 
 #include <atomic>
@@ -250,17 +254,31 @@ class EdgeStore {
  private:
   struct Move { uint64_t src, dst, count; };
 
+  // edge_store.hip
   void add_nodes(int64_t max_node);
-  void bump_eids(const int64_t* eids, size_t n);
   void drop_eid(int64_t eid);
-  uint64_t seg_alloc(uint64_t cap);
   void seg_free(uint64_t start, uint64_t cap);
   void ensure_pool(uint64_t elems);
-  struct BlockDelta { size_t bytes_added = 0, bytes_removed = 0, blocks_added = 0; };
-  void simulate_blocks(NodeState& st, const float* ts, size_t n, BlockDelta* delta);
-  LogicalBlock new_block(size_t size, BlockDelta* delta);
   void upload_entries(const std::vector<int64_t>& ids);
   void publish_entries(const PinnedBuffer& prepared, size_t k);
+
+  // edge_store_ingest.hip: the block policy, and add_edges' phases in call order
+  struct BlockStep;    // what the block policy does with one vertex's new edges
+  struct BlockDelta;   // byte / block counter changes, summed per thread
+  struct IngestBatch;  // one add_edges call, carried between its phases
+  BlockStep block_step(const LogicalBlock* tail, uint64_t num_edges, uint64_t num_insertions,
+                       size_t cnt) const;
+  void simulate_blocks(NodeState& st, const float* ts, size_t n, BlockDelta* delta);
+  void bump_eids(const int64_t* eids, size_t n);
+  void scan_batch(IngestBatch& b);
+  void order_on_device(IngestBatch& b);
+  void order_on_host(IngestBatch& b);
+  void validate_batch(const IngestBatch& b);
+  void update_sets(const IngestBatch& b);
+  void plan_blocks(IngestBatch& b);
+  void plan_segments(IngestBatch& b);
+  void plan_bases(IngestBatch& b);
+  void run_device_phase(IngestBatch& b);
 
   // config
   size_t initial_pool_size_, maximum_pool_size_, minimum_block_size_;

@@ -1,5 +1,6 @@
 // Device-side ordering of an ingest batch by (source, timestamp, input position); see
-// ingest_sort.hip.  Used by EdgeStore::add_edges for batches worth a device sort.
+// ingest_sort.hip.  Used by EdgeStore::add_edges (edge_store_ingest.hip: order_on_device and the
+// device phase) for batches worth a device sort.
 #pragma once
 
 #include <cstdint>

@@ -113,6 +113,72 @@ def test_rejected_batch_leaves_the_same_graph_intact(policy):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("adaptive", [True, False])
+@pytest.mark.parametrize("policy", ["insert", "replace"])
+def test_pool_limit_is_exact_to_the_byte(policy, adaptive):
+    """The dry run that rejects a batch and the planning pass that applies it compute the same
+    bytes: a batch that ends exactly at maximum_pool_size is accepted, the same batch against a
+    limit one byte lower is rejected and leaves the graph as the first batch left it."""
+    from gnnflow_amd import DynamicGraph
+    from oracle import oracle as O
+    from tests import synth
+    N = 60
+    src, dst, ts, eid = synth.powerlaw_graph(N, 1800, seed=5, tie_levels=200)
+    # the second batch: tails with room to fill, full tails, and vertices never seen
+    new = np.array([60, 61, 61, 75])
+    src = np.concatenate([src, new])
+    dst = np.concatenate([dst, [0, 1, 2, 60]])
+    ts = np.concatenate([ts, np.full(len(new), ts[-1], np.float32)])
+    eid = np.arange(len(src))
+    first, second = slice(0, 1500), slice(1500, None)
+
+    def oracle():
+        return O.OracleGraph(minimum_block_size=8, insertion_policy=policy,
+                             adaptive_block_size=adaptive)
+
+    def graph(limit):
+        return DynamicGraph(1024, int(limit), "cuda", 8, 1, policy, adaptive_block_size=adaptive)
+
+    def add(gr, sl):
+        gr.add_edges(src[sl], dst[sl], ts[sl], eid[sl])
+
+    def same(g, o, upto):
+        assert g.get_graph_memory_usage() == o.get_graph_memory_usage()
+        assert (g.num_edges(), g.num_vertices(), g.num_source_vertices()) == \
+               (o.num_edges(), o.num_vertices(), o.num_source_vertices())
+        assert np.array_equal(g.out_degree(np.arange(upto)), o.out_degree(np.arange(upto)))
+        for v in (0, 7, 31, N - 1, 60, 61, 75):
+            for a, b in zip(g.get_temporal_neighbors(v), o.get_temporal_neighbors(v)):
+                assert np.array_equal(a, b)
+
+    o0, o1 = oracle(), oracle()           # saw the first batch / both
+    add(o0, first)
+    add(o1, first)
+    m0 = o0.get_graph_memory_usage()
+    add(o1, second)
+    m1 = o1.get_graph_memory_usage()
+    assert m1 > m0 and m1 == int(m1)
+
+    g = graph(m1)                         # fits exactly
+    add(g, first)
+    add(g, second)
+    assert g.get_graph_memory_usage() == m1
+    same(g, o1, 76)
+
+    g = graph(m1 - 1)                     # one byte short
+    add(g, first)
+    with pytest.raises(MemoryError):
+        add(g, second)
+    assert g.get_graph_memory_usage() == m0
+    same(g, o0, N)
+    # ... and it keeps ingesting what fits: one block of the minimum size for a new vertex
+    assert m0 + 8 * 20 <= m1 - 1
+    for gr in (g, o0):
+        gr.add_edges(np.array([90]), np.array([3]), ts[-1:], np.array([len(src)]))
+    same(g, o0, 91)
+
+
+@pytest.mark.gpu
 def test_pool_limit_is_a_memory_error_not_an_abort():
     from gnnflow_amd import DynamicGraph
     g = DynamicGraph(1024, 4096, "cuda", 64, 1, "insert")       # 4 KiB of logical edge blocks
