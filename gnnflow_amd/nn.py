@@ -32,7 +32,7 @@ class SAGEConv(nn.Module):
     Under torch.autocast('cuda', dtype=torch.bfloat16) every aggregator runs on either side of
     `lin_before_mp`, with and without edge weights.  fc_neigh / fc_pool return bfloat16, and
     ops.block_reduce / ops.block_max take the rows as they come, float32 features or bfloat16
-    Linear outputs: float32 arithmetic inside, one rounding on store (ops.py).  Edge weights stay
+    Linear outputs: float32 arithmetic inside, one rounding on store (ops/).  Edge weights stay
     float32.  Two small operands are brought to the large one's dtype so that torch's promotion
     does not widen a [num_dst, out_feats] tensor only for the next Linear to narrow it again (the
     h_dst.to(agg.dtype) of TemporalAttentionLayer): the bias, and in 'gcn' the degrees, where
@@ -142,7 +142,7 @@ class GATConv(nn.Module):
     returns bfloat16; el and er come out float32 (bfloat16 * float32 parameter promotes, and sum
     is on autocast's float32 list), so ops.edge_softmax sees float32 as always, and
     ops.block_reduce / ops.block_gat take the bfloat16 rows with the float32 attention: float32
-    arithmetic inside, one rounding on store (ops.py).  The bias and the residual (float32 when
+    arithmetic inside, one rounding on store (ops/).  The bias and the residual (float32 when
     res_fc is the identity) are brought to the aggregate's dtype, as TemporalAttentionLayer does
     with h_dst.to(agg.dtype), so that promotion does not widen the [num_dst, H, D] result only for
     the next Linear to narrow it again; the output is bfloat16, and the attention
@@ -315,7 +315,7 @@ class TemporalAttentionLayer(nn.Module):
 
     Under torch.autocast('cuda', dtype=torch.bfloat16) every flag combination runs.  The Linear
     layers return bfloat16, and ops.block_attention takes q, k, v as they come: float32
-    arithmetic inside, one rounding on store (ops.py).  With `fused_time_encode` the rows are
+    arithmetic inside, one rounding on store (ops/).  With `fused_time_encode` the rows are
     asked for in bfloat16 (out_dtype), the type w_q / w_k / w_v want, so autocast has nothing to
     cast in front of them.  The bfloat16 aggregate is concatenated with h_dst.to(bfloat16): one
     cast of the [R, dim_node] side and a bfloat16 cat, one kernel fewer than letting torch.cat

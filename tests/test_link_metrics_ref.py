@@ -102,8 +102,9 @@ def test_accumulator_counts_batches_mrr_batches_and_non_finite():
 def test_python_constants_are_the_header_s():
     text = open(os.path.join(ROOT, "include", "gnnflow_hip.h")).read()
     macro = {k: int(v) for k, v in re.findall(r"#define (GF_LINK_METRICS_[A-Z_]+) (\d+)", text)}
-    src = open(os.path.join(ROOT, "gnnflow_amd", "ops.py")).read()
-    const = {k: int(v) for k, v in re.findall(r"^(_?LINK_METRICS_[A-Z_]+) = (\d+)", src, re.M)}
+    from gnnflow_amd import ops
+    const = {k: getattr(ops, k) for k in ("LINK_METRICS_MAX_SCORES", "LINK_METRICS_TILE",
+                                          "_LINK_METRICS_PARTIAL_WORDS")}
     assert macro == {"GF_LINK_METRICS_MAX_SCORES": 65536, "GF_LINK_METRICS_TILE": const["LINK_METRICS_TILE"],
                      "GF_LINK_METRICS_PARTIAL_WORDS": const["_LINK_METRICS_PARTIAL_WORDS"]}
     assert const["LINK_METRICS_MAX_SCORES"] == 65536
