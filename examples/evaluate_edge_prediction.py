@@ -6,13 +6,17 @@ GPU until the one `compute()` at the end.  Synthetic REDDIT-shaped data and an u
 by default; a usage example, not a benchmark.
 
     python examples/evaluate_edge_prediction.py [--batches 20] [--train-batches 0]
-                                                [--hist-negatives N]
+                                                [--hist-negatives N] [--edge-bank]
 
 --hist-negatives N takes the validation batches from a `gnnflow_amd.DeviceBatchStream` with N
 negatives per edge, all of them historical where the source has a history (`hist_ratio=N`:
 destinations the source interacted with before the edge's time, drawn on the GPU from the
 graph's edge store), and prints the share of negative slots that hold one.  The graph is built
 with reverse edges, so a source's history includes the nodes that pointed at it.
+
+--edge-bank scores the same batches, negatives included, with `gnnflow_amd.EdgeBank` as well
+("the pair has interacted strictly before the edge's time", read from the graph's edge store by
+`graph.pair_history`) and prints the baseline's AP / AUC / MRR beside the model's.
 """
 import argparse
 import os
@@ -46,9 +50,11 @@ def scores(model, mfgs, neg_ratio):
     return planes[0][0], torch.cat([neg for _, neg in planes])
 
 
-def evaluate(loader, sampler, model, cache, metrics, num_batches, neg_ratio=1):
+def evaluate(loader, sampler, model, cache, metrics, num_batches, neg_ratio=1, bank=None,
+             bank_metrics=None):
     """One validation pass: returns (ap, auc) as the reference does, and leaves the other
-    fields in `metrics`."""
+    fields in `metrics`.  With `bank` (an EdgeBank) every batch is scored by it too, into
+    `bank_metrics`."""
     model.eval()
     metrics.reset()
     with torch.no_grad():
@@ -59,12 +65,14 @@ def evaluate(loader, sampler, model, cache, metrics, num_batches, neg_ratio=1):
             cache.fetch_feature(mfgs, eid)
             pred_pos, pred_neg = scores(model, mfgs, neg_ratio)
             metrics.update(pred_pos, pred_neg)      # sigmoid, then AP / AUC / MRR; no sync
+            if bank is not None:
+                bank_metrics.update(*bank.predict(roots, ts, neg_ratio), sigmoid=False)
     result = metrics.compute()                      # the one sync of the pass
     return result["ap"], result["auc"]
 
 
 def main(num_batches=20, batch_size=600, train_batches=0, seed=0, verbose=True,
-         hist_negatives=0):
+         hist_negatives=0, edge_bank=False):
     import pandas as pd
     torch.manual_seed(seed)
     dev = torch.device("cuda", 0)
@@ -107,9 +115,13 @@ def main(num_batches=20, batch_size=600, train_batches=0, seed=0, verbose=True,
         loader = gnnflow_amd.DeviceBatchStream.from_dataframe(
             df.iloc[:num_batches * batch_size], batch_size, dst_set, neg_ratio=hist_negatives,
             seed=seed, graph=graph, hist_ratio=hist_negatives)
+    bank = gnnflow_amd.EdgeBank(graph) if edge_bank else None
+    bank_metrics = gnnflow_amd.LinkMetrics(dev) if edge_bank else None
     ap, auc = evaluate(loader, sampler, model, cache, metrics, num_batches,
-                       neg_ratio=hist_negatives or 1)
+                       neg_ratio=hist_negatives or 1, bank=bank, bank_metrics=bank_metrics)
     result = metrics.compute()
+    if edge_bank:
+        result["edge_bank"] = bank_metrics.compute()
     if hist_negatives:
         # read once per pass, like the metrics
         slots = int(loader.borders[-1] - loader.borders[0]) * hist_negatives
@@ -119,6 +131,10 @@ def main(num_batches=20, batch_size=600, train_batches=0, seed=0, verbose=True,
             ap, auc, result["mrr"], result["batches"], result["nonfinite"]) +
             (" historical negatives {:.1%} of {} per edge".format(
                 result["hist_share"], hist_negatives) if hist_negatives else ""))
+        if edge_bank:
+            print("EdgeBank (unlimited memory) on the same batches: ap {:.4f} auc {:.4f} "
+                  "mrr {:.4f}".format(result["edge_bank"]["ap"], result["edge_bank"]["auc"],
+                                      result["edge_bank"]["mrr"]))
     return result
 
 
@@ -129,5 +145,8 @@ if __name__ == "__main__":
     ap.add_argument("--hist-negatives", type=int, default=0,
                     help="N historical negatives per edge from a DeviceBatchStream (0: the "
                          "host loader's one random negative)")
+    ap.add_argument("--edge-bank", action="store_true",
+                    help="print the EdgeBank baseline's metrics on the same batches as well")
     a = ap.parse_args()
-    main(a.batches, train_batches=a.train_batches, hist_negatives=a.hist_negatives)
+    main(a.batches, train_batches=a.train_batches, hist_negatives=a.hist_negatives,
+         edge_bank=a.edge_bank)

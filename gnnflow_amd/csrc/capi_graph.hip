@@ -2,6 +2,7 @@
 // batch call that reads the store, gf_batch_hist_negatives.
 #include "capi_handles.hpp"
 #include "hist_negatives.hpp"
+#include "pair_history.hpp"
 #include "seen_mask.hpp"
 #include "temporal_walk.hpp"
 
@@ -95,6 +96,17 @@ int gf_graph_seen_mask(const gf_graph* g, const int64_t* d_src, const float* d_t
     GF_G(g);
     gf::seen_mask(g->impl.view(), d_src, d_ts, num_rows, d_sorted_ids, d_perm, num_cand,
                   max_history, d_mask, device, as_stream(stream));
+  });
+}
+// reads the store's view NOW, as gf_batch_hist_negatives does
+int gf_graph_pair_history(const gf_graph* g, const int64_t* d_src, const int64_t* d_dst,
+                          const float* d_ts, const float* d_since, size_t num_rows,
+                          size_t max_history, int64_t* d_count, float* d_last_ts,
+                          int64_t* d_last_eid, int device, void* stream) {
+  return guarded([&] {
+    GF_G(g);
+    gf::pair_history(g->impl.view(), d_src, d_dst, d_ts, d_since, num_rows, max_history, d_count,
+                     d_last_ts, d_last_eid, device, as_stream(stream));
   });
 }
 // reads the store's view NOW, as gf_batch_hist_negatives does

@@ -45,6 +45,47 @@ def check_seen_mask_args(src, ts, cand_ids, max_history=0):
     return B, Cn
 
 
+class PairHistory(NamedTuple):
+    """What DynamicGraph.pair_history returns, one entry per (src, dst, ts) row."""
+    count: torch.Tensor      # int64 [N]; considered edges of src that lead to dst
+    last_ts: torch.Tensor    # float32 [N]; time of the latest of them, -inf where count == 0
+    last_eid: torch.Tensor   # int64 [N]; its edge id, -1 where count == 0
+
+
+def check_pair_history_args(src, dst, ts, since=None, max_history=0):
+    """Arguments of DynamicGraph.pair_history, checked before anything is launched: the kernel
+    takes raw pointers and trusts them.  Needs no device.  Returns N."""
+    tensors = [("src", src, torch.int64), ("dst", dst, torch.int64), ("ts", ts, torch.float32)]
+    if isinstance(since, torch.Tensor):
+        tensors.append(("since", since, torch.float32))
+    for name, x, dtype in tensors:
+        if not isinstance(x, torch.Tensor):
+            raise TypeError("{} must be a tensor, got {}".format(name, type(x).__name__))
+        if x.dtype != dtype:
+            raise TypeError("{} must be {}, got {}".format(name, dtype, x.dtype))
+    if since is not None and not isinstance(since, torch.Tensor) and (
+            isinstance(since, bool) or not isinstance(since, (int, float))):
+        raise TypeError("since must be None, a float or a tensor, got {}".format(
+            type(since).__name__))
+    if isinstance(max_history, bool) or not isinstance(max_history, int):
+        raise TypeError("max_history must be an int, got {}".format(type(max_history).__name__))
+    for name, x, _ in tensors:
+        if x.dim() != 1:
+            raise ValueError("{} must be 1-D, got shape {}".format(name, tuple(x.shape)))
+    N = int(src.shape[0])
+    for name, x, _ in tensors[1:]:
+        if int(x.shape[0]) != N:
+            raise ValueError("src has {} rows, {} has {}".format(N, name, int(x.shape[0])))
+    if N >= 2 ** 31:
+        raise ValueError("pair_history takes fewer than 2**31 rows, got {}".format(N))
+    if max_history < 0:
+        raise ValueError("max_history must be >= 0, got {}".format(max_history))
+    for name, x, _ in tensors[1:]:
+        if x.device != src.device:
+            raise ValueError("{} is on {}, src on {}".format(name, x.device, src.device))
+    return N
+
+
 WALK_MAX_LENGTH = 32      # GF_WALK_MAX_LENGTH
 WALK_MAX_RECENCY = 8      # GF_WALK_MAX_RECENCY
 
@@ -297,6 +338,62 @@ class DynamicGraph:
                     perm.data_ptr(), Cn, max_history, mask.data_ptr(), self._device,
                     _capi.current_stream(torch.device("cuda", self._device))))
         return mask
+
+    def pair_history(self, src: torch.Tensor, dst: torch.Tensor, ts: torch.Tensor, *,
+                     since=None, max_history: int = 0) -> PairHistory:
+        """Has each pair interacted before, how often, and when last:
+        PairHistory(count int64 [N], last_ts float32 [N], last_eid int64 [N]).
+
+        The considered edges of row i are the live edges of src[i] in the store whose timestamp
+        is strictly below ts[i] (float <: a NaN time gives none) and, with `since`, not below
+        since[i] -- the lower end is inclusive, and a NaN since[i] is no lower end -- and, when
+        max_history > 0, only the newest max_history of that window (the bound comes after
+        `since`).  count[i] is the number of them that lead to dst[i]; last_ts[i] and last_eid[i]
+        are the timestamp and the edge id of the latest of those in the store's order, the first
+        match in get_temporal_neighbors' newest-first list, so that equal timestamps are told
+        apart; -inf and -1 where count[i] == 0.  "Strictly before" and "live" as for seen_mask:
+        edges that offload_old_blocks took are gone, and on a graph built with reverse edges the
+        history includes the edges that pointed at the source.  Any dst is legal (negative,
+        unknown to the graph) and matches nothing; a source that is negative, past the node table
+        or without live edges gives (0, -inf, -1).  The exact rule is in include/gnnflow_hip.h
+        (gf_graph_pair_history) and restated in numpy in tests/pair_history_ref.py.
+
+        src, dst: int64 [N], ts: float32 [N]; since: None, a float (the same lower end for every
+        row) or a float32 tensor [N]; all tensors on the graph's device.  N == 0 returns three
+        empty tensors without a launch.  These are EdgeBank's inputs (gnnflow_amd.EdgeBank) and
+        the usual pair features: times seen, time since the last contact, the last edge's id.
+
+        One kernel (csrc/pair_history.hip, a wave per row) on the current stream, memory from
+        torch, never synchronises.  Edges added to the graph are seen by calls made after
+        add_edges returns; add_edges and offload_old_blocks move and free segments: synchronise
+        the streams that calls were launched on before calling either, as for seen_mask.
+
+        The cost is proportional to the edges considered: a wave reads every considered edge of
+        its row, so a hub with 10^6 earlier edges is 10^6 record reads for each of its rows.
+        max_history and since are what bound it."""
+        N = check_pair_history_args(src, dst, ts, since, max_history)
+        dev = src.device
+        if dev.type != "cuda" or (dev.index is not None and dev.index != self._device):
+            raise ValueError("the graph is on device cuda:{}, the inputs on {}".format(
+                self._device, dev))
+        with torch.cuda.device(self._device):
+            count = torch.empty(N, dtype=torch.int64, device=dev)
+            last_ts = torch.empty(N, dtype=torch.float32, device=dev)
+            last_eid = torch.empty(N, dtype=torch.int64, device=dev)
+            if N:
+                s, d, t = (x.detach().contiguous() for x in (src, dst, ts))
+                if since is None:
+                    lo = None
+                elif isinstance(since, torch.Tensor):
+                    lo = since.detach().contiguous()
+                else:
+                    lo = torch.full((N,), float(since), dtype=torch.float32, device=dev)
+                _capi.check(self._lib.gf_graph_pair_history(
+                    self._h, s.data_ptr(), d.data_ptr(), t.data_ptr(),
+                    None if lo is None else lo.data_ptr(), N, max_history, count.data_ptr(),
+                    last_ts.data_ptr(), last_eid.data_ptr(), self._device,
+                    _capi.current_stream(torch.device("cuda", self._device))))
+        return PairHistory(count, last_ts, last_eid)
 
     def temporal_random_walk(self, src: torch.Tensor, ts: torch.Tensor, length: int,
                              num_walks: int = 1, *, recency: int = 1, max_history: int = 0,

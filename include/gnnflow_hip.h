@@ -1414,6 +1414,41 @@ GF_API int gf_graph_seen_mask(const gf_graph* g, const int64_t* d_src, const flo
                               size_t num_cand, size_t max_history, uint64_t* d_mask, int device,
                               void* stream);
 
+/* Has each of num_rows (source, destination) pairs interacted before the row's time, how often,
+ * and when last.  Row i has source s = d_src[i], destination d = d_dst[i], time t = d_ts[i] and,
+ * when d_since is not NULL, lower end lo = d_since[i].  Its considered edges:
+ * - e = table[s]; c = the number of x in ts_pool[e.start .. e.start + e.size) with x < t, strict
+ *   and with the float < operator (a NaN t gives c = 0), over the live range only, as in
+ *   gf_batch_hist_negatives;
+ * - c0 = 0, or with d_since min(c, the number of x with x < lo), the same operator: a NaN lo
+ *   gives c0 = 0, no lower end, and the lower end is inclusive (lo equal to an edge's time keeps
+ *   that edge);
+ * - n = c - c0, or min(c - c0, max_history) when max_history > 0: the NEWEST n edges of the
+ *   window, nbr_pool[e.start + c - n .. e.start + c), that is lo <= ts < t.
+ * Then
+ *   d_count[i]    = the number of considered edges whose dst == d              int64
+ *   p             = the largest pool position among them
+ *   d_last_ts[i]  = nbr_pool[p].ts,  -infinity when d_count[i] == 0            float32
+ *   d_last_eid[i] = nbr_pool[p].eid, -1 when d_count[i] == 0                   int64
+ * Among matching edges with the same timestamp the last is the latest in the store's order, the
+ * first match in gf_graph_get_temporal_neighbors' newest-first list.  Any d is legal (negative,
+ * unknown to the graph): it matches nothing.  s < 0, s >= table_len, no live edge, c == 0 or a
+ * store without a node: 0, -infinity, -1.  Every element of the three outputs ([num_rows] each)
+ * is written: they need no initialisation.  On a graph built with reverse edges the history
+ * includes edges that pointed at s, so without max_history the answer is symmetric in (s, d).
+ * One launch on `stream`, plain loads and stores, a wave per row, integer cross-lane reductions,
+ * no atomics: the same inputs give the same bits.  The cost is proportional to the edges
+ * considered (a hub's whole history when max_history == 0 and d_since == NULL); max_history
+ * > 2^32 - 1 is no bound.  Ordering against gf_graph_add_edges / gf_graph_offload_old_blocks: as
+ * gf_batch_hist_negatives.
+ * A NULL graph, a NULL buffer other than d_since with num_rows > 0, num_rows >= 2^31:
+ * GF_ERR_INVALID_ARGUMENT, nothing launched.  num_rows == 0: GF_OK, nothing launched. */
+GF_API int gf_graph_pair_history(const gf_graph* g, const int64_t* d_src, const int64_t* d_dst,
+                                 const float* d_ts, const float* d_since /* NULL: no lower end */,
+                                 size_t num_rows, size_t max_history,
+                                 int64_t* d_count, float* d_last_ts, int64_t* d_last_eid,
+                                 int device, void* stream);
+
 /* Backward-in-time random walks over the temporal edge store: W = num_walks walks of L = length
  * steps from each of num_rows roots.  Walk (i, w) starts at v_0 = d_src[i], t_0 = d_ts[i];
  * d_nodes[i, w, 0] = d_src[i] always.  Step j = 0 .. L - 1:

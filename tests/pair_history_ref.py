@@ -1,0 +1,82 @@
+"""Numpy restatement of DynamicGraph.pair_history (csrc/pair_history.hip, include/gnnflow_hip.h,
+gf_graph_pair_history) and of gnnflow_amd.EdgeBank's scores on top of it.
+
+A history is (dst int64 [m], ts float32 [m], eid int64 [m]), OLDEST FIRST, the live edges of a node
+in the store's order; `from_graph` reads them with get_temporal_neighbors (which returns newest
+first) for every node a query names.  For row i with s = src[i], d = dst[i], t = ts[i] and, when
+`since` is given, lo = since[i], over h = histories[s]:
+
+    c  = #{x in h.ts : x < t}                    float32 <: a NaN t gives 0
+    c0 = min(c, #{x in h.ts : x < lo})           float32 <: a NaN lo gives 0; 0 without `since`
+    n  = min(c - c0, max_history) if max_history else c - c0
+    considered = positions c - n .. c - 1        lo <= ts < t, the newest n
+    count[i]    = #{p considered : h.dst[p] == d}
+    last_ts[i]  = h.ts[p*],  last_eid[i] = h.eid[p*]    p* the largest such p;  -inf, -1 for none
+
+A source without a history (negative, unknown, no live edges) gives (0, -inf, -1).  Pure numpy.
+"""
+import numpy as np
+
+
+def count_before(ts, t):
+    """#{x in ts : x < t} in float32; the history ascends, so these are a prefix.  NaN goes
+    through < as it is: nothing is below NaN."""
+    with np.errstate(invalid="ignore"):
+        before = np.asarray(ts, np.float32) < np.float32(t)
+    c = int(before.sum())
+    assert before[:c].all()
+    return c
+
+
+def pair_history(histories, src, dst, ts, since=None, max_history=0):
+    """(count int64 [N], last_ts float32 [N], last_eid int64 [N]).  histories: {node: (dst, ts,
+    eid)}, oldest first.  since: None, a scalar, or an array [N]."""
+    src, dst = np.asarray(src, np.int64), np.asarray(dst, np.int64)
+    ts = np.asarray(ts, np.float32)
+    N = len(src)
+    assert len(dst) == N and len(ts) == N and max_history >= 0
+    if since is not None:
+        since = np.broadcast_to(np.asarray(since, np.float32), (N,))
+    count = np.zeros(N, np.int64)
+    last_ts = np.full(N, -np.inf, np.float32)
+    last_eid = np.full(N, -1, np.int64)
+    for i in range(N):
+        h = histories.get(int(src[i]))
+        if h is None or len(h[0]) == 0:
+            continue
+        h_dst, h_ts, h_eid = h
+        c = count_before(h_ts, ts[i])
+        c0 = min(c, count_before(h_ts, since[i])) if since is not None else 0
+        n = min(c - c0, max_history) if max_history else c - c0
+        hits = np.flatnonzero(np.asarray(h_dst[c - n:c], np.int64) == dst[i]) + (c - n)
+        count[i] = len(hits)
+        if len(hits):
+            last_ts[i] = np.float32(h_ts[hits[-1]])
+            last_eid[i] = int(h_eid[hits[-1]])
+    return count, last_ts, last_eid
+
+
+def edge_bank_scores(histories, src, dst, ts, mode="unlimited", window=None, min_count=1,
+                     max_history=0, score="seen"):
+    """float32 [N]: EdgeBank.score_pairs.  time_window: since = ts - window, in float32."""
+    ts = np.asarray(ts, np.float32)
+    since = None
+    if mode == "time_window":
+        since = ts - np.float32(window)
+    else:
+        assert mode == "unlimited"
+    count = pair_history(histories, src, dst, ts, since, max_history)[0]
+    if score == "seen":
+        return (count >= min_count).astype(np.float32)
+    assert score == "count"
+    return count.astype(np.float32)
+
+
+def from_graph(graph, nodes):
+    """{node: (dst, ts, eid)} oldest first, for every distinct valid node of `nodes`."""
+    out = {}
+    for v in np.unique(np.asarray(nodes, np.int64)):
+        if 0 <= v <= graph.max_vertex_id():
+            d, t, e = graph.get_temporal_neighbors(int(v))
+            out[int(v)] = (d[::-1].copy(), t[::-1].copy(), e[::-1].copy())
+    return out
