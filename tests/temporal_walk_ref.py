@@ -17,7 +17,8 @@ Every slot from the step a walk ends on holds nodes = -1, eids = -1, times = 0.
 
 A history is (dst int64 [m], ts float32 [m], eid int64 [m]), OLDEST FIRST, the live edges of the
 node in the store's order; `from_graph` reads them with get_temporal_neighbors (which returns
-newest first), `from_edges` builds them from the edge arrays the graph was given.
+newest first), `from_edges` builds them from the edge arrays the graph was given in one call,
+`from_chunks` from those of successive calls.
 
     position_counts:  out[i, w, j, p] = #{w' : ref[i, w', p] == nodes[i, w, j]} if nodes[i, w, j] >= 0 else 0
 """
@@ -141,4 +142,29 @@ def from_edges(src, dst, ts, eid=None, add_reverse=False):
         idx = np.flatnonzero(src == v)
         idx = idx[np.argsort(ts[idx], kind="stable")]
         out[v] = (dst[idx], ts[idx], eid[idx])
+    return out, table_len
+
+
+def from_chunks(src, dst, ts, eid, chunk, add_reverse=False):
+    """The same from the edge arrays given to an empty graph in successive add_edges calls of
+    `chunk` edges each (tests/synth.py ingest_chunks), under either block policy and before any
+    offload, where no call holds a time below an earlier call's: a node's edges call after call,
+    inside a call stable-sorted by time in the order given (with add_reverse a call's reversed
+    copies follow all its forward edges).  Only the nodes that have an edge are in the result, so
+    that a sparse far id costs nothing."""
+    src, dst = np.asarray(src, dtype=np.int64), np.asarray(dst, dtype=np.int64)
+    ts, eid = np.asarray(ts, dtype=np.float32), np.asarray(eid, dtype=np.int64)
+    call = np.arange(len(src)) // chunk
+    given = np.arange(len(src))
+    if add_reverse:
+        src, dst = np.concatenate([src, dst]), np.concatenate([dst, src])
+        ts, eid, call = np.concatenate([ts, ts]), np.concatenate([eid, eid]), np.tile(call, 2)
+        given = np.concatenate([given, given + len(given)])
+    table_len = int(max(src.max(), dst.max())) + 1 if len(src) else 0
+    order = np.lexsort((given, ts, call, src))      # by node, then call, then time, then as given
+    starts = np.flatnonzero(np.append(True, src[order][1:] != src[order][:-1]))
+    out = {}
+    for a, b in zip(starts, np.append(starts[1:], len(order))):
+        idx = order[a:b]
+        out[int(src[idx[0]])] = (dst[idx], ts[idx], eid[idx])
     return out, table_len
