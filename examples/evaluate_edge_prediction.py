@@ -7,6 +7,7 @@ by default; a usage example, not a benchmark.
 
     python examples/evaluate_edge_prediction.py [--batches 20] [--train-batches 0]
                                                 [--hist-negatives N] [--edge-bank]
+                                                [--neighbor-overlap SCORE]
 
 --hist-negatives N takes the validation batches from a `gnnflow_amd.DeviceBatchStream` with N
 negatives per edge, all of them historical where the source has a history (`hist_ratio=N`:
@@ -17,6 +18,10 @@ with reverse edges, so a source's history includes the nodes that pointed at it.
 --edge-bank scores the same batches, negatives included, with `gnnflow_amd.EdgeBank` as well
 ("the pair has interacted strictly before the edge's time", read from the graph's edge store by
 `graph.pair_history`) and prints the baseline's AP / AUC / MRR beside the model's.
+
+--neighbor-overlap SCORE (cn, jaccard, aa, ra or pa) does the same with
+`gnnflow_amd.NeighborOverlap`: the overlap of the two ends' temporal neighbourhoods strictly
+before the edge's time, read by `graph.common_neighbors`.
 """
 import argparse
 import os
@@ -51,10 +56,10 @@ def scores(model, mfgs, neg_ratio):
 
 
 def evaluate(loader, sampler, model, cache, metrics, num_batches, neg_ratio=1, bank=None,
-             bank_metrics=None):
+             bank_metrics=None, overlap=None, overlap_metrics=None):
     """One validation pass: returns (ap, auc) as the reference does, and leaves the other
     fields in `metrics`.  With `bank` (an EdgeBank) every batch is scored by it too, into
-    `bank_metrics`."""
+    `bank_metrics`; with `overlap` (a NeighborOverlap) likewise into `overlap_metrics`."""
     model.eval()
     metrics.reset()
     with torch.no_grad():
@@ -67,12 +72,14 @@ def evaluate(loader, sampler, model, cache, metrics, num_batches, neg_ratio=1, b
             metrics.update(pred_pos, pred_neg)      # sigmoid, then AP / AUC / MRR; no sync
             if bank is not None:
                 bank_metrics.update(*bank.predict(roots, ts, neg_ratio), sigmoid=False)
+            if overlap is not None:
+                overlap_metrics.update(*overlap.predict(roots, ts, neg_ratio), sigmoid=False)
     result = metrics.compute()                      # the one sync of the pass
     return result["ap"], result["auc"]
 
 
 def main(num_batches=20, batch_size=600, train_batches=0, seed=0, verbose=True,
-         hist_negatives=0, edge_bank=False):
+         hist_negatives=0, edge_bank=False, neighbor_overlap=None):
     import pandas as pd
     torch.manual_seed(seed)
     dev = torch.device("cuda", 0)
@@ -117,11 +124,16 @@ def main(num_batches=20, batch_size=600, train_batches=0, seed=0, verbose=True,
             seed=seed, graph=graph, hist_ratio=hist_negatives)
     bank = gnnflow_amd.EdgeBank(graph) if edge_bank else None
     bank_metrics = gnnflow_amd.LinkMetrics(dev) if edge_bank else None
+    overlap = gnnflow_amd.NeighborOverlap(graph, neighbor_overlap) if neighbor_overlap else None
+    overlap_metrics = gnnflow_amd.LinkMetrics(dev) if neighbor_overlap else None
     ap, auc = evaluate(loader, sampler, model, cache, metrics, num_batches,
-                       neg_ratio=hist_negatives or 1, bank=bank, bank_metrics=bank_metrics)
+                       neg_ratio=hist_negatives or 1, bank=bank, bank_metrics=bank_metrics,
+                       overlap=overlap, overlap_metrics=overlap_metrics)
     result = metrics.compute()
     if edge_bank:
         result["edge_bank"] = bank_metrics.compute()
+    if neighbor_overlap:
+        result["neighbor_overlap"] = overlap_metrics.compute()
     if hist_negatives:
         # read once per pass, like the metrics
         slots = int(loader.borders[-1] - loader.borders[0]) * hist_negatives
@@ -135,6 +147,11 @@ def main(num_batches=20, batch_size=600, train_batches=0, seed=0, verbose=True,
             print("EdgeBank (unlimited memory) on the same batches: ap {:.4f} auc {:.4f} "
                   "mrr {:.4f}".format(result["edge_bank"]["ap"], result["edge_bank"]["auc"],
                                       result["edge_bank"]["mrr"]))
+        if neighbor_overlap:
+            r = result["neighbor_overlap"]
+            print("NeighborOverlap ({}, the newest {} edges of each end) on the same batches: "
+                  "ap {:.4f} auc {:.4f} mrr {:.4f}".format(neighbor_overlap, overlap.max_history,
+                                                           r["ap"], r["auc"], r["mrr"]))
     return result
 
 
@@ -147,6 +164,9 @@ if __name__ == "__main__":
                          "host loader's one random negative)")
     ap.add_argument("--edge-bank", action="store_true",
                     help="print the EdgeBank baseline's metrics on the same batches as well")
+    ap.add_argument("--neighbor-overlap", default=None, metavar="SCORE",
+                    choices=["cn", "jaccard", "aa", "ra", "pa"],
+                    help="print a NeighborOverlap baseline's metrics on the same batches as well")
     a = ap.parse_args()
     main(a.batches, train_batches=a.train_batches, hist_negatives=a.hist_negatives,
-         edge_bank=a.edge_bank)
+         edge_bank=a.edge_bank, neighbor_overlap=a.neighbor_overlap)

@@ -4,9 +4,9 @@ Drop-in for the hot path of jasperzhong/GNNFlow: `DynamicGraph`, `TemporalSample
 `cache.LRUCache` keep the reference's Python API; the work runs in hand-written HIP
 kernels (gfx950) behind the C ABI of include/gnnflow_hip.h.
 """
-from .baselines import EdgeBank
+from .baselines import EdgeBank, NeighborOverlap
 from .data import DeviceBatchStream, DeviceDstSet
-from .dynamic_graph import DynamicGraph, PairHistory, TemporalWalks
+from .dynamic_graph import CommonNeighbors, DynamicGraph, PairHistory, TemporalWalks
 from .metrics import LinkMetrics
 from .mfg import MFGBlock
 from .nn import (MLP, EdgePredictor, GATConv, GRUMemeoryUpdater, GRUMemoryUpdater, LinkLoss,
@@ -16,4 +16,5 @@ from .temporal_sampler import SamplingResult, TemporalSampler
 __all__ = ["DynamicGraph", "TemporalSampler", "SamplingResult", "MFGBlock", "SAGEConv", "GATConv",
            "TimeEncode", "TemporalAttentionLayer", "TransfomerAttentionLayer", "GRUMemoryUpdater",
            "GRUMemeoryUpdater", "EdgePredictor", "MLP", "LinkMetrics", "LinkLoss",
-           "DeviceDstSet", "DeviceBatchStream", "TemporalWalks", "PairHistory", "EdgeBank"]
+           "DeviceDstSet", "DeviceBatchStream", "TemporalWalks", "PairHistory", "EdgeBank",
+           "CommonNeighbors", "NeighborOverlap"]

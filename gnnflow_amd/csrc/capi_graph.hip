@@ -1,6 +1,7 @@
 // extern "C" entry points of include/gnnflow_hip.h over EdgeStore: gf_graph_* and the one
 // batch call that reads the store, gf_batch_hist_negatives.
 #include "capi_handles.hpp"
+#include "common_neighbors.hpp"
 #include "hist_negatives.hpp"
 #include "pair_history.hpp"
 #include "seen_mask.hpp"
@@ -107,6 +108,30 @@ int gf_graph_pair_history(const gf_graph* g, const int64_t* d_src, const int64_t
     GF_G(g);
     gf::pair_history(g->impl.view(), d_src, d_dst, d_ts, d_since, num_rows, max_history, d_count,
                      d_last_ts, d_last_eid, device, as_stream(stream));
+  });
+}
+// reads the store's view NOW, as gf_batch_hist_negatives does
+int gf_graph_common_neighbors(const gf_graph* g, const int64_t* d_src, const int64_t* d_dst,
+                              const float* d_ts, const float* d_since, size_t num_rows,
+                              size_t max_history, size_t max_common, int32_t* d_n_src,
+                              int32_t* d_n_dst, int32_t* d_u_src, int32_t* d_u_dst,
+                              int32_t* d_common, int64_t* d_nodes, int32_t* d_cnt_src,
+                              int32_t* d_cnt_dst, int device, void* stream) {
+  return guarded([&] {
+    GF_G(g);
+    gf::common_neighbors(g->impl.view(), d_src, d_dst, d_ts, d_since, num_rows, max_history,
+                         max_common, d_n_src, d_n_dst, d_u_src, d_u_dst, d_common, d_nodes,
+                         d_cnt_src, d_cnt_dst, device, as_stream(stream));
+  });
+}
+// reads the store's view NOW, as gf_batch_hist_negatives does
+int gf_graph_temporal_degree(const gf_graph* g, const int64_t* d_nodes, const float* d_ts,
+                             const float* d_since, size_t num, int64_t* d_out, int device,
+                             void* stream) {
+  return guarded([&] {
+    GF_G(g);
+    gf::temporal_degree(g->impl.view(), d_nodes, d_ts, d_since, num, d_out, device,
+                        as_stream(stream));
   });
 }
 // reads the store's view NOW, as gf_batch_hist_negatives does

@@ -52,10 +52,10 @@ class PairHistory(NamedTuple):
     last_eid: torch.Tensor   # int64 [N]; its edge id, -1 where count == 0
 
 
-def check_pair_history_args(src, dst, ts, since=None, max_history=0):
-    """Arguments of DynamicGraph.pair_history, checked before anything is launched: the kernel
-    takes raw pointers and trusts them.  Needs no device.  Returns N."""
-    tensors = [("src", src, torch.int64), ("dst", dst, torch.int64), ("ts", ts, torch.float32)]
+def _typed_tensors(tensors, since):
+    """The (name, tensor, dtype) triples, `since` appended when it is a tensor, after the type
+    checks the history readers share."""
+    tensors = list(tensors)
     if isinstance(since, torch.Tensor):
         tensors.append(("since", since, torch.float32))
     for name, x, dtype in tensors:
@@ -67,23 +67,88 @@ def check_pair_history_args(src, dst, ts, since=None, max_history=0):
             isinstance(since, bool) or not isinstance(since, (int, float))):
         raise TypeError("since must be None, a float or a tensor, got {}".format(
             type(since).__name__))
-    if isinstance(max_history, bool) or not isinstance(max_history, int):
-        raise TypeError("max_history must be an int, got {}".format(type(max_history).__name__))
+    return tensors
+
+
+def _pair_rows(tensors, what):
+    """N of 1-D tensors of one length, the first of them src; fewer than 2**31."""
     for name, x, _ in tensors:
         if x.dim() != 1:
             raise ValueError("{} must be 1-D, got shape {}".format(name, tuple(x.shape)))
-    N = int(src.shape[0])
+    N = int(tensors[0][1].shape[0])
     for name, x, _ in tensors[1:]:
         if int(x.shape[0]) != N:
             raise ValueError("src has {} rows, {} has {}".format(N, name, int(x.shape[0])))
     if N >= 2 ** 31:
-        raise ValueError("pair_history takes fewer than 2**31 rows, got {}".format(N))
+        raise ValueError("{} takes fewer than 2**31 rows, got {}".format(what, N))
+    return N
+
+
+def _same_device(tensors):
+    first, x0, _ = tensors[0]
+    for name, x, _ in tensors[1:]:
+        if x.device != x0.device:
+            raise ValueError("{} is on {}, {} on {}".format(name, x.device, first, x0.device))
+
+
+def _pair_tensors(src, dst, ts):
+    return [("src", src, torch.int64), ("dst", dst, torch.int64), ("ts", ts, torch.float32)]
+
+
+def check_pair_history_args(src, dst, ts, since=None, max_history=0):
+    """Arguments of DynamicGraph.pair_history, checked before anything is launched: the kernel
+    takes raw pointers and trusts them.  Needs no device.  Returns N."""
+    tensors = _typed_tensors(_pair_tensors(src, dst, ts), since)
+    if isinstance(max_history, bool) or not isinstance(max_history, int):
+        raise TypeError("max_history must be an int, got {}".format(type(max_history).__name__))
+    N = _pair_rows(tensors, "pair_history")
     if max_history < 0:
         raise ValueError("max_history must be >= 0, got {}".format(max_history))
-    for name, x, _ in tensors[1:]:
-        if x.device != src.device:
-            raise ValueError("{} is on {}, src on {}".format(name, x.device, src.device))
+    _same_device(tensors)
     return N
+
+
+CN_MAX_HISTORY = 512      # GF_CN_MAX_HISTORY
+
+
+class CommonNeighbors(NamedTuple):
+    """What DynamicGraph.common_neighbors returns, one row per (src, dst, ts) row; A and B are the
+    considered edges of src and of dst."""
+    n_src: torch.Tensor      # int32 [N]; |A|, multi-edges counted
+    n_dst: torch.Tensor      # int32 [N]; |B|
+    u_src: torch.Tensor      # int32 [N]; distinct neighbours in A
+    u_dst: torch.Tensor      # int32 [N]; distinct neighbours in B
+    common: torch.Tensor     # int32 [N]; neighbours in both, not capped by max_common
+    nodes: torch.Tensor      # int64 [N, K]; the common ones, src's most recent first, then -1
+    cnt_src: torch.Tensor    # int32 [N, K]; edges of A that lead to nodes[i, k], 0 in the padding
+    cnt_dst: torch.Tensor    # int32 [N, K]; edges of B that lead to nodes[i, k], 0 in the padding
+
+
+def check_common_neighbors_args(src, dst, ts, since=None, max_history=64, max_common=32):
+    """Arguments of DynamicGraph.common_neighbors, checked before anything is launched or
+    allocated: the kernel takes raw pointers and trusts them.  Needs no device.
+    Returns (N, H, K)."""
+    tensors = _typed_tensors(_pair_tensors(src, dst, ts), since)
+    H = _int_arg(max_history, "max_history", 1, CN_MAX_HISTORY + 1)
+    K = _int_arg(max_common, "max_common", 0, CN_MAX_HISTORY + 1)
+    N = _pair_rows(tensors, "common_neighbors")
+    _same_device(tensors)
+    return N, H, K
+
+
+def check_temporal_degree_args(nodes, ts, since=None):
+    """Arguments of DynamicGraph.temporal_degree, checked before anything is launched.  Needs no
+    device.  Returns the number of elements."""
+    tensors = _typed_tensors([("nodes", nodes, torch.int64), ("ts", ts, torch.float32)], since)
+    for name, x, _ in tensors[1:]:
+        if tuple(x.shape) != tuple(nodes.shape):
+            raise ValueError("nodes has shape {}, {} has {}".format(
+                tuple(nodes.shape), name, tuple(x.shape)))
+    if nodes.numel() >= 2 ** 31:
+        raise ValueError("temporal_degree takes fewer than 2**31 elements, got {}".format(
+            nodes.numel()))
+    _same_device(tensors)
+    return int(nodes.numel())
 
 
 WALK_MAX_LENGTH = 32      # GF_WALK_MAX_LENGTH
@@ -394,6 +459,106 @@ class DynamicGraph:
                     last_ts.data_ptr(), last_eid.data_ptr(), self._device,
                     _capi.current_stream(torch.device("cuda", self._device))))
         return PairHistory(count, last_ts, last_eid)
+
+    def _check_on_device(self, dev):
+        if dev.type != "cuda" or (dev.index is not None and dev.index != self._device):
+            raise ValueError("the graph is on device cuda:{}, the inputs on {}".format(
+                self._device, dev))
+
+    @staticmethod
+    def _since_tensor(since, shape, dev):
+        if since is None:
+            return None
+        if isinstance(since, torch.Tensor):
+            return since.detach().contiguous()
+        return torch.full(shape, float(since), dtype=torch.float32, device=dev)
+
+    def common_neighbors(self, src: torch.Tensor, dst: torch.Tensor, ts: torch.Tensor, *,
+                         since=None, max_history: int = 64,
+                         max_common: int = 32) -> CommonNeighbors:
+        """Which nodes have both ends of each pair met before the row's time:
+        CommonNeighbors(n_src, n_dst, u_src, u_dst, common int32 [N]; nodes int64 [N, K];
+        cnt_src, cnt_dst int32 [N, K]), K = max_common.
+
+        The considered edges of a node are pair_history's: its live edges in the store whose
+        timestamp is strictly below ts[i] (float <: a NaN time gives none) and, with `since`, not
+        below since[i] -- the lower end is inclusive, a NaN since[i] is no lower end -- and of
+        that window only the newest max_history.  max_history is required here, 1 .. 512: it
+        bounds the table a row is intersected in.  A is that set for src[i], B for dst[i], both
+        at the same time and lower end.  An edge whose stored destination is negative counts as
+        an edge but is nobody's neighbour.
+
+        - n_src, n_dst: the edges in A and in B, multi-edges counted.
+        - u_src, u_dst: the distinct neighbours in A and in B.
+        - common: the neighbours in both, not capped by max_common; the union is
+          u_src + u_dst - common.
+        - nodes[i]: the common neighbours, the one src[i] met most recently first (by the latest
+          position in A that leads to it), the first min(common[i], K) of them, then -1.
+        - cnt_src[i, k], cnt_dst[i, k]: how many edges of A and of B lead to nodes[i, k]; what
+          pair_history(src, nodes[:, k], ...).count gives under the same window.  0 in the padding.
+
+        src[i] == dst[i] is legal: every neighbour is then common.  The endpoints themselves are
+        NOT removed from the sets: on a graph built with reverse edges a pair that has interacted
+        has dst[i] among src[i]'s neighbours (and the other way round), and dst[i] is a common
+        neighbour if it also has a loop.  A node that is negative, past the node table or without
+        live edges has no considered edge.  "Strictly before" and "live" as for seen_mask.  The
+        exact rule is in include/gnnflow_hip.h (gf_graph_common_neighbors) and restated in numpy
+        in tests/common_neighbors_ref.py.
+
+        src, dst: int64 [N], ts: float32 [N]; since: None, a float or a float32 tensor [N]; all
+        tensors on the graph's device; 0 <= max_common <= 512.  N == 0 returns empty tensors of
+        these shapes without a launch; a graph without nodes gives zeros and -1.
+
+        One kernel (csrc/common_neighbors.hip: a row's two windows hashed into a table in LDS,
+        integers only, the same inputs give the same bits) on the current stream, memory from
+        torch, never synchronises.  Synchronise the streams that calls were launched on before
+        add_edges or offload_old_blocks, as for seen_mask.  The cost is the 2 * max_history
+        records read per row."""
+        N, H, K = check_common_neighbors_args(src, dst, ts, since, max_history, max_common)
+        dev = src.device
+        self._check_on_device(dev)
+        with torch.cuda.device(self._device):
+            n_src, n_dst, u_src, u_dst, common = (
+                torch.empty(N, dtype=torch.int32, device=dev) for _ in range(5))
+            nodes = torch.empty((N, K), dtype=torch.int64, device=dev)
+            cnt_src = torch.empty((N, K), dtype=torch.int32, device=dev)
+            cnt_dst = torch.empty((N, K), dtype=torch.int32, device=dev)
+            if N:
+                s, d, t = (x.detach().contiguous() for x in (src, dst, ts))
+                lo = self._since_tensor(since, (N,), dev)
+                _capi.check(self._lib.gf_graph_common_neighbors(
+                    self._h, s.data_ptr(), d.data_ptr(), t.data_ptr(),
+                    None if lo is None else lo.data_ptr(), N, H, K, n_src.data_ptr(),
+                    n_dst.data_ptr(), u_src.data_ptr(), u_dst.data_ptr(), common.data_ptr(),
+                    nodes.data_ptr() if K else None, cnt_src.data_ptr() if K else None,
+                    cnt_dst.data_ptr() if K else None, self._device,
+                    _capi.current_stream(torch.device("cuda", self._device))))
+        return CommonNeighbors(n_src, n_dst, u_src, u_dst, common, nodes, cnt_src, cnt_dst)
+
+    def temporal_degree(self, nodes: torch.Tensor, ts: torch.Tensor, *,
+                        since=None) -> torch.Tensor:
+        """int64 of nodes' shape: the number of live edges of nodes[...] whose timestamp is
+        strictly below ts[...] and, with `since`, not below since[...] -- common_neighbors'
+        window without max_history.  A node that is negative (the -1 padding of
+        CommonNeighbors.nodes), past the node table or without live edges gives 0, so padded
+        lists need no mask.
+
+        nodes: int64 of any shape, ts: float32 of the same shape; since: None, a float or a
+        float32 tensor of that shape; all on the graph's device.  One kernel, a lane per element,
+        on the current stream; never synchronises; an empty `nodes` launches nothing."""
+        n = check_temporal_degree_args(nodes, ts, since)
+        dev = nodes.device
+        self._check_on_device(dev)
+        with torch.cuda.device(self._device):
+            out = torch.empty(nodes.shape, dtype=torch.int64, device=dev)
+            if n:
+                v, t = nodes.detach().contiguous(), ts.detach().contiguous()
+                lo = self._since_tensor(since, nodes.shape, dev)
+                _capi.check(self._lib.gf_graph_temporal_degree(
+                    self._h, v.data_ptr(), t.data_ptr(), None if lo is None else lo.data_ptr(),
+                    n, out.data_ptr(), self._device,
+                    _capi.current_stream(torch.device("cuda", self._device))))
+        return out
 
     def temporal_random_walk(self, src: torch.Tensor, ts: torch.Tensor, length: int,
                              num_walks: int = 1, *, recency: int = 1, max_history: int = 0,

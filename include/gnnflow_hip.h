@@ -1449,6 +1449,65 @@ GF_API int gf_graph_pair_history(const gf_graph* g, const int64_t* d_src, const 
                                  int64_t* d_count, float* d_last_ts, int64_t* d_last_eid,
                                  int device, void* stream);
 
+/* Which nodes have BOTH ends of each of num_rows pairs met before the row's time.  Row i has
+ * source s = d_src[i], destination d = d_dst[i], time t = d_ts[i] and, when d_since is not NULL,
+ * lower end lo = d_since[i].  The window of a node v is gf_graph_pair_history's:
+ * - e = table[v]; c = the number of x in ts_pool[e.start .. e.start + e.size) with x < t, strict
+ *   and with the float < operator (a NaN t gives c = 0), over the live range only;
+ * - c0 = 0, or with d_since min(c, the number of x with x < lo), the same operator: a NaN lo
+ *   gives c0 = 0, and the lower end is inclusive;
+ * - n = min(c - c0, H), H = max_history, which is REQUIRED here, 1 <= H <= GF_CN_MAX_HISTORY: it
+ *   bounds the table a row is intersected in;
+ * - the window's records are nbr_pool[e.start + c - n .. e.start + c), at positions 0 .. n - 1,
+ *   oldest first;
+ * - v < 0, v >= table_len, no live edge or a store without a node: the window is empty.
+ * A is the window of s, B the window of d, both at the same t and lo.  A record whose dst is
+ * negative counts as an edge but is nobody's neighbour.  For z >= 0, a(z) and b(z) are the
+ * numbers of records of A and of B with dst == z, and pa(z) is the largest position in A that
+ * holds z.  With K = max_common, 0 <= K <= GF_CN_MAX_HISTORY:
+ *   d_n_src[i], d_n_dst[i] = |A|, |B|: edges, multi-edges counted               int32 [num_rows]
+ *   d_u_src[i], d_u_dst[i] = #{z : a(z) > 0}, #{z : b(z) > 0}                   int32 [num_rows]
+ *   d_common[i]            = #{z : a(z) > 0 and b(z) > 0}, not capped by K      int32 [num_rows]
+ *   d_nodes[i, :]          = those z by DESCENDING pa(z) -- the one the source met most recently
+ *                            first --, the first min(d_common[i], K), then -1   int64 [num_rows, K]
+ *   d_cnt_src[i, k], d_cnt_dst[i, k] = a(z), b(z) of z = d_nodes[i, k]; 0 in the padding
+ *                                                                               int32 [num_rows, K]
+ * Every element of the eight outputs, row-major and contiguous, is written: they need no
+ * initialisation.  s == d is legal: every neighbour is then common.  The endpoints themselves are
+ * not removed from the sets: on a graph built with reverse edges a pair that has interacted has
+ * d among the neighbours of s.
+ * One launch on `stream`: a row's two windows are inserted into an open-addressing table in LDS
+ * (at most 2H keys in >= 4H slots; a probe that finds no place after as many trips as there are
+ * slots drops its record, which cannot happen at that load) with LDS atomics on integers, counted
+ * with integer cross-lane sums, and the common nodes are placed by their rank among A's
+ * positions, one writer per element, no atomics on global memory: the same inputs give the same
+ * bits.  The cost is the 2H records read per row.  Ordering against gf_graph_add_edges /
+ * gf_graph_offload_old_blocks: as gf_batch_hist_negatives.
+ * A NULL graph, a NULL buffer other than d_since with num_rows > 0 (d_nodes, d_cnt_src and
+ * d_cnt_dst may be NULL when K == 0), max_history outside [1, GF_CN_MAX_HISTORY], max_common >
+ * GF_CN_MAX_HISTORY, num_rows >= 2^31: GF_ERR_INVALID_ARGUMENT, nothing launched.
+ * num_rows == 0: GF_OK, nothing launched. */
+#define GF_CN_MAX_HISTORY 512
+GF_API int gf_graph_common_neighbors(const gf_graph* g, const int64_t* d_src, const int64_t* d_dst,
+                                     const float* d_ts,
+                                     const float* d_since /* NULL: no lower end */,
+                                     size_t num_rows, size_t max_history, size_t max_common,
+                                     int32_t* d_n_src, int32_t* d_n_dst, int32_t* d_u_src,
+                                     int32_t* d_u_dst, int32_t* d_common, int64_t* d_nodes,
+                                     int32_t* d_cnt_src, int32_t* d_cnt_dst, int device,
+                                     void* stream);
+
+/* d_out[i] = c - c0 of the window of node d_nodes[i] at time d_ts[i] and lower end d_since[i]
+ * (NULL: none) as defined for gf_graph_common_neighbors, without max_history: the number of live
+ * edges of the node with lo <= ts < t, int64 [num].  A node that is negative (the -1 padding of
+ * d_nodes above), past the node table or without live edges gives 0.  Every element is written.
+ * One launch on `stream`, a lane per element, plain loads and stores.
+ * A NULL graph, a NULL buffer other than d_since with num > 0, num >= 2^31:
+ * GF_ERR_INVALID_ARGUMENT, nothing launched.  num == 0: GF_OK, nothing launched. */
+GF_API int gf_graph_temporal_degree(const gf_graph* g, const int64_t* d_nodes, const float* d_ts,
+                                    const float* d_since /* NULL: no lower end */, size_t num,
+                                    int64_t* d_out, int device, void* stream);
+
 /* Backward-in-time random walks over the temporal edge store: W = num_walks walks of L = length
  * steps from each of num_rows roots.  Walk (i, w) starts at v_0 = d_src[i], t_0 = d_ts[i];
  * d_nodes[i, w, 0] = d_src[i] always.  Step j = 0 .. L - 1:
