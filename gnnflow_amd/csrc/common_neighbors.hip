@@ -1,11 +1,8 @@
 // Which nodes have both ends of a pair met before the row's time: for row i with source
 // s = src[i], destination d = dst[i], time t = ts[i] and, when `since` is given, lo = since[i],
 //
-//   window(v): e = table[v]                 v < 0, v >= table_len, e.size == 0: empty
-//              c  = #{x in ts_pool[e.start .. e.start + e.size) : x < t}    float <: NaN t gives 0
-//              c0 = since ? min(c, #{x : x < lo}) : 0                       float <: NaN lo gives 0
-//              n  = min(c - c0, H)                                    H = max_history, 1 .. 512
-//              records nbr_pool[e.start + c - n .. e.start + c), positions 0 .. n - 1 oldest first
+//   window(v) = the considered records of v at (t, lo, H) as history_window.hpp defines them,
+//               H = max_history, 1 .. 512; positions 0 .. n - 1 oldest first
 //   A = window(s), B = window(d)            pair_history's window, both at the same t and lo
 //   a(z), b(z) = records of A, of B with .dst == z, for z >= 0 (a negative .dst is no neighbour)
 //   pa(z)      = the largest position in A that holds z
@@ -55,7 +52,7 @@
 // is written while that is < K.  One writer per output element, no atomics on global memory.  The
 // same wave writes the padding [min(common, K), K).  Rows past the grid limit are grid-strided.
 //
-// temporal_degree is c - c0 of one window, a lane per element, no LDS.
+// temporal_degree is c - c0 of one window (window_counts), a lane per element, no LDS.
 #include "common_neighbors.hpp"
 #include "common.hpp"
 #include "history_window.hpp"
@@ -72,10 +69,7 @@ constexpr uint32_t kMaxGrid = 4096;      // workgroups; the rows past a pass are
 constexpr int64_t kEmpty = -1;
 
 struct CnArgs {
-  const NodeEntry* table;
-  uint64_t table_len;        // 0: a store without a node, every window is empty
-  const float* ts_pool;
-  const EdgePair* nbr_pool;
+  StoreView store;
   const int64_t* src;
   const int64_t* dst;
   const float* ts;
@@ -94,41 +88,6 @@ struct CnArgs {
   int32_t* cnt_src;
   int32_t* cnt_dst;
 };
-
-struct Window {
-  const EdgePair* seg;       // seg[0 .. n) is inside the node's run, oldest first
-  uint32_t n;
-};
-
-// c and c0 of node v's window; false for a node without one
-__device__ __forceinline__ bool window_counts(const NodeEntry* table, uint64_t table_len,
-                                              const float* ts_pool, int64_t v, float t,
-                                              const float* since, uint64_t row, NodeEntry& e,
-                                              uint32_t& c, uint32_t& c0) {
-  c = c0 = 0;
-  if (v < 0 || static_cast<uint64_t>(v) >= table_len) return false;
-  e = table[v];
-  if (e.size == 0) return false;
-  const float* const run = ts_pool + e.start;
-  c = t > __uint_as_float(e.last_ts_bits) ? e.size : count_before(run, e.size, t);   // <= e.size
-  if (since != nullptr && c != 0) {
-    c0 = count_before(run, e.size, since[row]);
-    if (c0 > c) c0 = c;
-  }
-  return true;
-}
-
-__device__ __forceinline__ Window window_of(const CnArgs& a, int64_t v, float t, uint64_t row) {
-  NodeEntry e;
-  uint32_t c, c0;
-  Window w = {nullptr, 0};
-  if (window_counts(a.table, a.table_len, a.ts_pool, v, t, a.since, row, e, c, c0)) {
-    w.n = c - c0;
-    if (a.max_history < w.n) w.n = a.max_history;
-    w.seg = a.nbr_pool + e.start + (c - w.n);
-  }
-  return w;
-}
 
 template <int CAP>
 struct Table {
@@ -195,12 +154,13 @@ __global__ void __launch_bounds__(kThreads) common_neighbors_kernel(const CnArgs
   const uint32_t rl = threadIdx.x % TPR;      // the thread's place among those of its row
   const uint32_t lane = threadIdx.x % kWave;
   const uint32_t K = a.max_common, cap = a.cap, shift = a.shift;
+  __builtin_assume(a.max_history != 0);      // 1 .. kCnMaxHistory: window_of's "no bound" is dead
   const uint64_t step = static_cast<uint64_t>(gridDim.x) * kRows;
   for (uint64_t row = static_cast<uint64_t>(blockIdx.x) * kRows + threadIdx.x / TPR; row < a.rows;
        row += step) {      // uniform over the row's waves; over the workgroup when kRows == 1
     const float t = a.ts[row];
-    const Window A = window_of(a, a.src[row], t, row);
-    const Window B = window_of(a, a.dst[row], t, row);
+    const Window A = window_of(a.store, a.src[row], t, a.since, row, a.max_history);
+    const Window B = window_of(a.store, a.dst[row], t, a.since, row, a.max_history);
     int64_t* const out_nodes = a.nodes + row * K;
     int32_t* const out_a = a.cnt_src + row * K;
     int32_t* const out_b = a.cnt_dst + row * K;
@@ -301,9 +261,7 @@ __global__ void __launch_bounds__(kThreads) common_neighbors_kernel(const CnArgs
 }
 
 struct DegArgs {
-  const NodeEntry* table;
-  uint64_t table_len;
-  const float* ts_pool;
+  StoreView store;
   const int64_t* nodes;
   const float* ts;
   const float* since;
@@ -317,7 +275,7 @@ __global__ void __launch_bounds__(kThreads) temporal_degree_kernel(const DegArgs
        i += step) {
     NodeEntry e;
     uint32_t c, c0;
-    window_counts(a.table, a.table_len, a.ts_pool, a.nodes[i], a.ts[i], a.since, i, e, c, c0);
+    (void)window_counts(a.store, a.nodes[i], a.ts[i], a.since, i, e, c, c0);
     a.out[i] = static_cast<int64_t>(c - c0);
   }
 }
@@ -326,14 +284,8 @@ template <int CAP, int TPR>
 void launch(const CnArgs& a, hipStream_t stream) {
   constexpr int kRows = kThreads / TPR;
   static_assert(sizeof(Table<CAP>) * kRows <= 64 * 1024, "static LDS of a workgroup");
-  const uint64_t groups = (a.rows + kRows - 1) / kRows;
   common_neighbors_kernel<CAP, TPR>
-      <<<dim3(static_cast<uint32_t>(std::min<uint64_t>(groups, kMaxGrid))), dim3(kThreads), 0,
-         stream>>>(a);
-}
-
-bool store_is_empty(const GraphView& g) {
-  return g.table_len == 0 || g.table == nullptr || g.ts_pool == nullptr || g.nbr_pool == nullptr;
+      <<<strided_grid(a.rows, kRows, kMaxGrid), dim3(kThreads), 0, stream>>>(a);
 }
 
 }  // namespace
@@ -357,10 +309,10 @@ void common_neighbors(const GraphView& g, const int64_t* d_src, const int64_t* d
              w + ": null nodes, cnt_src or cnt_dst");
   uint32_t cap = 4, log2cap = 2;
   while (cap < 4 * max_history) cap <<= 1, ++log2cap;      // <= 2048
-  CnArgs a = {g.table, store_is_empty(g) ? 0 : g.table_len, g.ts_pool, g.nbr_pool, d_src, d_dst,
-              d_ts, d_since, num_rows, static_cast<uint32_t>(max_history),
-              static_cast<uint32_t>(max_common), cap, 64 - log2cap, d_n_src, d_n_dst, d_u_src,
-              d_u_dst, d_common, d_nodes, d_cnt_src, d_cnt_dst};
+  CnArgs a = {store_view(g), d_src, d_dst, d_ts, d_since, num_rows,
+              static_cast<uint32_t>(max_history), static_cast<uint32_t>(max_common), cap,
+              64 - log2cap, d_n_src, d_n_dst, d_u_src, d_u_dst, d_common, d_nodes, d_cnt_src,
+              d_cnt_dst};
   DeviceGuard dg(device);
   if (max_history <= 32) launch<128, kWave>(a, stream);
   else if (max_history <= 128) launch<512, kWave>(a, stream);
@@ -375,12 +327,9 @@ void temporal_degree(const GraphView& g, const int64_t* d_nodes, const float* d_
   GF_REQUIRE(num < (size_t{1} << 31), w + ": 2^31 elements or more");
   if (num == 0) return;
   GF_REQUIRE(d_nodes && d_ts && d_out, w + ": null nodes, ts or out");
-  DegArgs a = {g.table, store_is_empty(g) ? 0 : g.table_len, g.ts_pool, d_nodes, d_ts, d_since,
-               num, d_out};
+  DegArgs a = {store_view(g), d_nodes, d_ts, d_since, num, d_out};
   DeviceGuard dg(device);
-  const uint64_t groups = (static_cast<uint64_t>(num) + kThreads - 1) / kThreads;
-  temporal_degree_kernel<<<dim3(static_cast<uint32_t>(std::min<uint64_t>(groups, kMaxGrid))),
-                           dim3(kThreads), 0, stream>>>(a);
+  temporal_degree_kernel<<<strided_grid(num, kThreads, kMaxGrid), dim3(kThreads), 0, stream>>>(a);
   GF_HIP(hipGetLastError());
 }
 

@@ -4,23 +4,22 @@
 // node).  One launch goes over batches that batch_stream.hip has already assembled and
 // overwrites the first Kh of their K negative planes where such a destination exists:
 //
-//   e    = table[s]                        s < 0, s >= table_len: the slot is kept
-//   c    = #{x in ts_pool[e.start .. e.start + e.size) : x < t}      c == 0: kept
+//   seg[0 .. c) = the window of s at (t, no lower end, no bound), as history_window.hpp
+//          defines it                                                c == 0: the slot is kept
 //   u_a  = gf_philox4x32_10_first(seed ^ (GF_HIST_NEG_SEED_TAG + a), tid, epoch)   a < 4
-//   cand = nbr_pool[e.start + ((uint64(u_a) * c) >> 32)].dst         tid = g * K + k  (wraps)
+//   cand = seg[(uint64(u_a) * c) >> 32].dst                          tid = g * K + k  (wraps)
 //   roots[2B + k*B + i] = the first cand != d;  none in four attempts: kept
 //
 // A kept slot holds the random draw gf_batch_assemble wrote, so no slot is undefined and the
 // fall-back costs nothing.  The tag keeps these draws independent of the random ones of the
 // same tid.  Everything else in roots and all of ts is not touched.
 //
-// A workgroup takes tiles of kTileRows rows.  Its first wave resolves c ONCE per row (node
-// entry, then the last_ts_bits shortcut — t later than the node's newest edge: c = size — or
-// a binary search over the timestamps) into LDS; then all lanes take the tile's Kh x rows
-// slots, consecutive lanes consecutive rows of one plane, and issue a slot's four candidate
-// reads together: independent 32-byte sectors, selected afterwards.  Plain loads and stores,
-// no waiting on another workgroup; the optional count of overwritten slots is reduced in the
-// workgroup and added with one atomicAdd per workgroup.
+// A workgroup takes tiles of kTileRows rows.  Its first wave resolves the window ONCE per
+// row into LDS; then all lanes take the tile's Kh x rows slots, consecutive lanes consecutive
+// rows of one plane, and issue a slot's four candidate reads together: independent 32-byte
+// sectors, selected afterwards.  Plain loads and stores, no waiting on another workgroup; the
+// optional count of overwritten slots is reduced in the workgroup and added with one atomicAdd
+// per workgroup.
 #include "hist_negatives.hpp"
 #include "common.hpp"
 #include "history_window.hpp"
@@ -41,10 +40,7 @@ static_assert(kHistNegAttempts == GF_HIST_NEG_ATTEMPTS,
 static_assert(kTileRows <= kThreads, "one lane per row of a tile");
 
 struct HistArgs {
-  const NodeEntry* table;
-  uint64_t table_len;
-  const float* ts_pool;
-  const EdgePair* nbr_pool;
+  StoreView store;
   const int64_t* src;
   const int64_t* dst;
   const float* time;
@@ -58,7 +54,7 @@ struct HistArgs {
 };
 
 __global__ void __launch_bounds__(kThreads) hist_negatives_kernel(const HistArgs a) {
-  __shared__ uint64_t s_start[kTileRows];
+  __shared__ const EdgePair* s_seg[kTileRows];
   __shared__ int64_t s_dst[kTileRows];
   __shared__ uint32_t s_c[kTileRows];
   __shared__ uint32_t s_filled[kWaves];
@@ -78,20 +74,10 @@ __global__ void __launch_bounds__(kThreads) hist_negatives_kernel(const HistArgs
     const uint32_t n = B - i0 < kTileRows ? static_cast<uint32_t>(B - i0) : kTileRows;
     if (threadIdx.x < n) {
       const uint64_t row = lo + i0 + threadIdx.x;             // < hi <= rows
-      const int64_t s = a.src[row];
-      const float t = a.time[row];
-      uint64_t start = 0;
-      uint32_t c = 0;
-      if (s >= 0 && static_cast<uint64_t>(s) < a.table_len) {
-        const NodeEntry e = a.table[s];
-        start = e.start;
-        if (e.size)
-          c = t > __uint_as_float(e.last_ts_bits) ? e.size
-                                                  : count_before(a.ts_pool + start, e.size, t);
-      }
-      s_start[threadIdx.x] = start;
+      const Window win = window_of(a.store, a.src[row], a.time[row], nullptr, 0, 0);
+      s_seg[threadIdx.x] = win.seg;
       s_dst[threadIdx.x] = a.dst[row];
-      s_c[threadIdx.x] = c;                                   // <= e.size
+      s_c[threadIdx.x] = win.n;
     }
     __syncthreads();
     const uint32_t slots = a.Kh * n;                          // < 2^16 * 64
@@ -99,7 +85,7 @@ __global__ void __launch_bounds__(kThreads) hist_negatives_kernel(const HistArgs
       const uint32_t k = w / n, r = w - k * n;                // k < Kh, r < n
       const uint64_t c = s_c[r];
       if (c == 0) continue;
-      const EdgePair* const seg = a.nbr_pool + s_start[r];
+      const EdgePair* const seg = s_seg[r];
       const int64_t d = s_dst[r];
       const uint64_t tid = (a.first_row + lo + i0 + r) * a.K + k;      // wraps mod 2^64
       int64_t cand[kHistNegAttempts];
@@ -107,7 +93,7 @@ __global__ void __launch_bounds__(kThreads) hist_negatives_kernel(const HistArgs
       for (int t = 0; t < kHistNegAttempts; ++t) {
         const uint64_t u = gf_philox4x32_10_first(
             a.seed ^ (GF_HIST_NEG_SEED_TAG + static_cast<uint64_t>(t)), tid, a.epoch);
-        cand[t] = seg[(u * c) >> 32].dst;                     // (u * c) >> 32 < c <= e.size
+        cand[t] = seg[(u * c) >> 32].dst;                     // (u * c) >> 32 < c: in the window
       }
       int hit = -1;
 #pragma unroll
@@ -153,13 +139,11 @@ void batch_hist_negatives(const GraphView& g, const int64_t* d_src, const int64_
   GF_REQUIRE(d_src && d_dst && d_time, w + ": null src, dst or time");
   GF_REQUIRE(d_borders != nullptr, w + ": null borders");
   GF_REQUIRE(d_roots != nullptr, w + ": null roots");
-  // a store without a node has no history: every slot keeps its random draw
-  if (g.table_len == 0 || g.table == nullptr || g.ts_pool == nullptr || g.nbr_pool == nullptr)
-    return;
-  HistArgs a = {g.table, g.table_len, g.ts_pool, g.nbr_pool, d_src, d_dst, d_time, num_rows,
-                d_borders, static_cast<uint32_t>(neg_ratio), static_cast<uint32_t>(hist_ratio),
-                seed, epoch, first_row, d_roots, capacity,
-                reinterpret_cast<unsigned long long*>(d_filled)};
+  const StoreView store = store_view(g);
+  if (store.table_len == 0) return;      // no history: every slot keeps its random draw
+  HistArgs a = {store, d_src, d_dst, d_time, num_rows, d_borders,
+                static_cast<uint32_t>(neg_ratio), static_cast<uint32_t>(hist_ratio), seed, epoch,
+                first_row, d_roots, capacity, reinterpret_cast<unsigned long long*>(d_filled)};
   DeviceGuard dg(device);
   const uint64_t tiles = (static_cast<uint64_t>(max_batch_rows) + kTileRows - 1) / kTileRows;
   const dim3 grid(static_cast<uint32_t>(num_batches),

@@ -1,29 +1,23 @@
 // Has this pair interacted before, how often, and when last: for row i with source s = src[i],
 // destination d = dst[i], time t = ts[i] and, when `since` is given, lower end lo = since[i],
 //
-//   e  = table[s]                        s < 0, s >= table_len, e.size == 0: no considered edge
-//   c  = #{x in ts_pool[e.start .. e.start + e.size) : x < t}       float <: NaN t gives 0
-//   c0 = since ? min(c, #{x : x < lo}) : 0                          float <: NaN lo gives 0
-//   n  = max_history ? min(c - c0, max_history) : c - c0            the newest n of the window
-//   considered = nbr_pool[e.start + c - n .. e.start + c)           lo <= ts < t, newest n
+//   considered  = the window of s at (t, lo, max_history), as history_window.hpp defines it
 //   count[i]    = #{considered records with .dst == d}
 //   p           = the largest pool position among them
 //   last_ts[i]  = nbr_pool[p].ts,  -inf when count == 0
 //   last_eid[i] = nbr_pool[p].eid, -1   when count == 0
 //
-// "strictly before" and "live" as in hist_negatives.hip and seen_mask.hip (history_window.hpp).
 // Every row's three outputs are written, the rows without a considered edge too.
 //
 // A wave takes a row at a time, four rows per workgroup, rows past the grid limit grid-strided.
-// All lanes resolve the node entry, c and c0 together (the same addresses: one request; the
-// last_ts_bits shortcut — t later than the node's newest edge: c = size — or a binary search over
-// the timestamps), then stride over the n records, one 32-byte record per lane, of which .dst is
-// read.  A lane keeps its match count and its largest matching index; the wave sums the one and
-// takes the maximum of the other with cross-lane shuffles, integers both: the result does not
-// depend on the lane order.  Lane 0 reads .ts / .eid of the winner and stores the three values.
-// Plain loads and stores, no LDS, no atomics, no waiting on another workgroup.  The cost is the
-// records read: a hub with 10^6 earlier edges is 10^6 record reads for its row, by one wave;
-// max_history and since are what bound it.
+// All lanes resolve the window together (the same addresses: one request), then stride over the
+// n records, one 32-byte record per lane, of which .dst is read.  A lane keeps its match count
+// and its largest matching index; the wave sums the one and takes the maximum of the other with
+// cross-lane shuffles, integers both: the result does not depend on the lane order.  Lane 0 reads
+// .ts / .eid of the winner and stores the three values.  Plain loads and stores, no LDS, no
+// atomics, no waiting on another workgroup.  The cost is the records read: a hub with 10^6
+// earlier edges is 10^6 record reads for its row, by one wave; max_history and since are what
+// bound it.
 #include "pair_history.hpp"
 #include "common.hpp"
 #include "history_window.hpp"
@@ -37,10 +31,7 @@ constexpr int kWaves = kThreads / kWave;      // rows a workgroup works on at a 
 constexpr uint32_t kMaxGrid = 4096;           // rows past kMaxGrid * kWaves are grid-strided
 
 struct PairArgs {
-  const NodeEntry* table;
-  uint64_t table_len;        // 0: a store without a node, every row gets the empty answer
-  const float* ts_pool;
-  const EdgePair* nbr_pool;
+  StoreView store;           // without a node: every row gets the empty answer
   const int64_t* src;
   const int64_t* dst;
   const float* ts;
@@ -57,27 +48,9 @@ __global__ void __launch_bounds__(kThreads) pair_history_kernel(const PairArgs a
   const uint64_t step = static_cast<uint64_t>(gridDim.x) * kWaves;
   for (uint64_t row = static_cast<uint64_t>(blockIdx.x) * kWaves + wave; row < a.rows;
        row += step) {                                          // uniform over the wave
-    const int64_t s = a.src[row];
-    const float t = a.ts[row];
-    uint32_t n = 0;
-    const EdgePair* seg = nullptr;
-    if (s >= 0 && static_cast<uint64_t>(s) < a.table_len) {
-      const NodeEntry e = a.table[s];
-      if (e.size != 0) {
-        const float* const run = a.ts_pool + e.start;
-        const uint32_t c = t > __uint_as_float(e.last_ts_bits)
-                               ? e.size
-                               : count_before(run, e.size, t);      // <= e.size
-        uint32_t c0 = 0;
-        if (a.since != nullptr && c != 0) {
-          c0 = count_before(run, e.size, a.since[row]);
-          if (c0 > c) c0 = c;
-        }
-        n = c - c0;
-        if (a.max_history && a.max_history < n) n = a.max_history;
-        seg = a.nbr_pool + e.start + (c - n);      // seg[0 .. n) is inside the run
-      }
-    }
+    const Window win = window_of(a.store, a.src[row], a.ts[row], a.since, row, a.max_history);
+    const EdgePair* const seg = win.seg;
+    const uint32_t n = win.n;
     // n is the same in every lane: the wave takes the branches below as one
     uint32_t cnt = 0, best = 0;      // best: 1 + the largest matching index, 0 for none (n < 2^32)
     if (n != 0) {
@@ -113,17 +86,10 @@ void pair_history(const GraphView& g, const int64_t* d_src, const int64_t* d_dst
   if (num_rows == 0) return;
   GF_REQUIRE(d_src && d_dst && d_ts, w + ": null src, dst or ts");
   GF_REQUIRE(d_count && d_last_ts && d_last_eid, w + ": null count, last_ts or last_eid");
-  // a store without a node has no history: table_len == 0 sends every row to the empty answer
-  const bool empty = g.table_len == 0 || g.table == nullptr || g.ts_pool == nullptr ||
-                     g.nbr_pool == nullptr;
-  // a node's run holds fewer than 2^32 edges: a larger bound is no bound
-  const uint32_t mh = max_history > 0xFFFFFFFFull ? 0u : static_cast<uint32_t>(max_history);
-  PairArgs a = {g.table, empty ? 0 : g.table_len, g.ts_pool, g.nbr_pool, d_src, d_dst, d_ts,
-                d_since, num_rows, mh, d_count, d_last_ts, d_last_eid};
+  PairArgs a = {store_view(g), d_src, d_dst, d_ts, d_since, num_rows, history_bound(max_history),
+                d_count, d_last_ts, d_last_eid};
   DeviceGuard dg(device);
-  const uint64_t groups = (static_cast<uint64_t>(num_rows) + kWaves - 1) / kWaves;
-  pair_history_kernel<<<dim3(static_cast<uint32_t>(std::min<uint64_t>(groups, kMaxGrid))),
-                        dim3(kThreads), 0, stream>>>(a);
+  pair_history_kernel<<<strided_grid(num_rows, kWaves, kMaxGrid), dim3(kThreads), 0, stream>>>(a);
   GF_HIP(hipGetLastError());
 }
 

@@ -1,24 +1,19 @@
 // Which candidates has each source already met: for row i with source s = src[i] and time
 // t = ts[i], and a candidate list of C node ids (any order, duplicates allowed),
 //
-//   e    = table[s]                        s < 0, s >= table_len: the row stays zero
-//   c    = #{x in ts_pool[e.start .. e.start + e.size) : x < t}      float <: NaN t gives 0
-//   n    = max_history ? min(c, max_history) : c                     the newest n of them
-//   mask[i, p / 64] |= 1 << (p % 64)       for every p with cand_ids[p] == nbr_pool[x].dst,
-//                                          x in [e.start + c - n, e.start + c)
+//   considered = the window of s at (t, no lower end, max_history), as history_window.hpp
+//                defines it; empty: the row stays zero
+//   mask[i, p / 64] |= 1 << (p % 64)       for every p with cand_ids[p] == r.dst, r considered
 //
-// "strictly before" and "live" as in hist_negatives.hip (history_window.hpp).  The candidates
-// arrive sorted with the permutation that sorted them (sorted_ids, perm), so that a destination
-// is found with one lower bound and its duplicates are the equal entries behind it.
+// The candidates arrive sorted with the permutation that sorted them (sorted_ids, perm), so that
+// a destination is found with one lower bound and its duplicates are the equal entries behind it.
 //
 // A wave takes a row at a time, four rows per workgroup, rows past the grid limit grid-strided.
-// All lanes resolve the node entry and c together (the same addresses: one request; the
-// last_ts_bits shortcut — t later than the node's newest edge: c = size — or a binary search
-// over the timestamps), then stride over the n records, one 32-byte record per lane.  Plain
-// loads, no waiting on another workgroup, no LDS; atomicOr on the mask's 64-bit words is the
-// only atomic, and OR is commutative and idempotent: the same inputs give the same bits.  The
-// cost is the records read: a hub with 10^6 earlier edges is 10^6 record reads and lower bounds
-// for its row, by one wave; max_history bounds it.
+// All lanes resolve the window together (the same addresses: one request), then stride over the
+// n records, one 32-byte record per lane.  Plain loads, no waiting on another workgroup, no LDS;
+// atomicOr on the mask's 64-bit words is the only atomic, and OR is commutative and idempotent:
+// the same inputs give the same bits.  The cost is the records read: a hub with 10^6 earlier
+// edges is 10^6 record reads and lower bounds for its row, by one wave; max_history bounds it.
 #include "seen_mask.hpp"
 #include "common.hpp"
 #include "history_window.hpp"
@@ -32,10 +27,7 @@ constexpr int kWaves = kThreads / kWave;      // rows a workgroup works on at a 
 constexpr uint32_t kMaxGrid = 4096;           // rows past kMaxGrid * kWaves are grid-strided
 
 struct SeenArgs {
-  const NodeEntry* table;
-  uint64_t table_len;
-  const float* ts_pool;
-  const EdgePair* nbr_pool;
+  StoreView store;
   const int64_t* src;
   const float* ts;
   uint64_t rows;
@@ -62,19 +54,11 @@ __global__ void __launch_bounds__(kThreads) seen_mask_kernel(const SeenArgs a) {
   const uint64_t step = static_cast<uint64_t>(gridDim.x) * kWaves;
   for (uint64_t row = static_cast<uint64_t>(blockIdx.x) * kWaves + wave; row < a.rows;
        row += step) {                                          // uniform over the wave
-    const int64_t s = a.src[row];
-    const float t = a.ts[row];
-    if (s < 0 || static_cast<uint64_t>(s) >= a.table_len) continue;
-    const NodeEntry e = a.table[s];
-    if (e.size == 0) continue;
-    const uint32_t c = t > __uint_as_float(e.last_ts_bits)
-                           ? e.size
-                           : count_before(a.ts_pool + e.start, e.size, t);      // <= e.size
-    const uint32_t n = a.max_history && a.max_history < c ? a.max_history : c;
-    const EdgePair* const seg = a.nbr_pool + e.start + (c - n);      // seg[0 .. n) is inside the run
+    const Window win = window_of(a.store, a.src[row], a.ts[row], nullptr, 0, a.max_history);
+    if (win.n == 0) continue;
     unsigned long long* const out = a.mask + row * a.W;
-    for (uint32_t x = lane; x < n; x += kWave) {
-      const int64_t d = seg[x].dst;
+    for (uint32_t x = lane; x < win.n; x += kWave) {
+      const int64_t d = win.seg[x].dst;
       for (uint32_t j = lower_bound(a.sorted_ids, a.C, d); j < a.C && a.sorted_ids[j] == d; ++j) {
         const int64_t p = a.perm[j];
         if (p < 0 || p >= static_cast<int64_t>(a.C)) continue;      // not a permutation: no bit
@@ -100,18 +84,13 @@ void seen_mask(const GraphView& g, const int64_t* d_src, const float* d_ts, size
   GF_REQUIRE(d_src && d_ts, w + ": null src or ts");
   GF_REQUIRE(d_sorted_ids && d_perm, w + ": null sorted_ids or perm");
   GF_REQUIRE(d_mask != nullptr, w + ": null mask");
-  // a store without a node has no history: every row stays zero
-  if (g.table_len == 0 || g.table == nullptr || g.ts_pool == nullptr || g.nbr_pool == nullptr)
-    return;
+  const StoreView store = store_view(g);
+  if (store.table_len == 0) return;      // no history: every row stays zero
   const uint32_t C = static_cast<uint32_t>(num_cand);
-  // a node's run holds fewer than 2^32 edges: a larger bound is no bound
-  const uint32_t mh = max_history > 0xFFFFFFFFull ? 0u : static_cast<uint32_t>(max_history);
-  SeenArgs a = {g.table, g.table_len, g.ts_pool, g.nbr_pool, d_src, d_ts, num_rows, d_sorted_ids,
-                d_perm, C, (C + 63) / 64, mh, reinterpret_cast<unsigned long long*>(d_mask)};
+  SeenArgs a = {store, d_src, d_ts, num_rows, d_sorted_ids, d_perm, C, (C + 63) / 64,
+                history_bound(max_history), reinterpret_cast<unsigned long long*>(d_mask)};
   DeviceGuard dg(device);
-  const uint64_t groups = (static_cast<uint64_t>(num_rows) + kWaves - 1) / kWaves;
-  seen_mask_kernel<<<dim3(static_cast<uint32_t>(std::min<uint64_t>(groups, kMaxGrid))),
-                     dim3(kThreads), 0, stream>>>(a);
+  seen_mask_kernel<<<strided_grid(num_rows, kWaves, kMaxGrid), dim3(kThreads), 0, stream>>>(a);
   GF_HIP(hipGetLastError());
 }
 

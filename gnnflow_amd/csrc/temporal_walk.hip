@@ -2,19 +2,18 @@
 // chronologically sorted run per node).  Walk (i, w), w < W, starts at v_0 = src[i], t_0 = ts[i];
 // nodes[i, w, 0] = src[i] always, and for step j = 0 .. L - 1:
 //
-//   v_j outside [0, table_len): the walk has ended
-//   e    = table[v_j]
-//   c    = #{x in ts_pool[e.start .. e.start + e.size) : x < t_j}     float <: NaN t_j gives 0
-//   n    = max_history ? min(c, max_history) : c                      n == 0: the walk has ended
+//   seg[0 .. n) = the window of v_j at (t_j, no lower end, max_history), as history_window.hpp
+//          defines it                                                 n == 0: the walk has ended
 //   u_a  = gf_philox4x32_10_first(seed ^ (GF_WALK_SEED_TAG + a), tid, (epoch << 8) + j)   a < recency
 //   x    = max over a of ((uint64(u_a) * n) >> 32)                    0 <= x < n
-//   r    = nbr_pool[e.start + (c - n) + x]
+//   r    = seg[x]
 //   nodes[i, w, j + 1] = r.dst;  eids[i, w, j] = r.eid;  times[i, w, j] = r.ts
 //   v_{j+1} = r.dst;  t_{j+1} = r.ts              tid = (first_row + i) * W + w  (wraps)
 //
 // Every slot from the step a walk ends on holds nodes = -1, eids = -1, times = 0, so the kernel
-// writes every element of the three outputs.  "strictly before" and "live" as in
-// hist_negatives.hip and seen_mask.hip (history_window.hpp); time strictly decreases along a walk.
+// writes every element of the three outputs.  The window is resolved again at every step, and its
+// bounds test is what checks a record's dst before it indexes the table as the next v; time
+// strictly decreases along a walk.
 //
 // One lane per walk, consecutive lanes consecutive w of one root: a walk is a chain of up to 3 L
 // dependent random reads (node entry, timestamp search, one 32-byte record), so the kernel lives
@@ -46,10 +45,7 @@ static_assert(kWalkMaxLength == GF_WALK_MAX_LENGTH && kWalkMaxRecency == GF_WALK
               "gnnflow_hip.h and temporal_walk.hpp disagree on the walk limits");
 
 struct WalkArgs {
-  const NodeEntry* table;
-  uint64_t table_len;        // 0: a store without a node, every walk ends on step 0
-  const float* ts_pool;
-  const EdgePair* nbr_pool;
+  StoreView store;           // without a node: every walk ends on step 0
   const int64_t* src;
   const float* ts;
   uint64_t walks;            // B * W < 2^31
@@ -78,35 +74,25 @@ __global__ void __launch_bounds__(kThreads) temporal_walk_kernel(const WalkArgs 
     for (uint32_t j = 0; j < a.L; ++j) {
       int64_t nd = -1, ne = -1;
       float nt = 0.0f;
-      // a record's dst is checked here, as v, before it indexes the table
-      if (alive && v >= 0 && static_cast<uint64_t>(v) < a.table_len) {
-        const NodeEntry e = a.table[v];
-        uint32_t c = 0;
-        if (e.size)
-          c = t > __uint_as_float(e.last_ts_bits)
-                  ? e.size
-                  : count_before(a.ts_pool + e.start, e.size, t);      // <= e.size
-        const uint32_t n = a.max_history && a.max_history < c ? a.max_history : c;
-        alive = n != 0;
-        if (alive) {
-          const uint64_t call = (a.epoch << 8) + j;            // wraps mod 2^64
-          uint32_t x = 0;
-          for (uint32_t p = 0; p < a.recency; ++p) {
-            const uint64_t u = gf_philox4x32_10_first(
-                a.seed ^ (GF_WALK_SEED_TAG + static_cast<uint64_t>(p)), tid, call);
-            const uint32_t xp = static_cast<uint32_t>((u * n) >> 32);      // < n
-            x = xp > x ? xp : x;
-          }
-          // c - n + x < c <= e.size: inside the node's run
-          const EdgePair* const r = a.nbr_pool + e.start + (c - n) + x;
-          nd = r->dst;
-          ne = r->eid;
-          nt = r->ts;
-          v = nd;
-          t = nt;
+      // v is a record's dst from step 1 on: window_of checks it before it indexes the table
+      const Window win = alive ? window_of(a.store, v, t, nullptr, 0, a.max_history)
+                               : Window{nullptr, 0};
+      alive = win.n != 0;
+      if (alive) {
+        const uint64_t call = (a.epoch << 8) + j;              // wraps mod 2^64
+        uint32_t x = 0;
+        for (uint32_t p = 0; p < a.recency; ++p) {
+          const uint64_t u = gf_philox4x32_10_first(
+              a.seed ^ (GF_WALK_SEED_TAG + static_cast<uint64_t>(p)), tid, call);
+          const uint32_t xp = static_cast<uint32_t>((u * win.n) >> 32);      // < n
+          x = xp > x ? xp : x;
         }
-      } else {
-        alive = false;
+        const EdgePair* const r = win.seg + x;                 // x < n: inside the window
+        nd = r->dst;
+        ne = r->eid;
+        nt = r->ts;
+        v = nd;
+        t = nt;
       }
       nodes[j + 1] = nd;                                       // j + 1 <= L
       eids[j] = ne;                                            // j < L
@@ -130,20 +116,12 @@ void temporal_walks(const GraphView& g, const int64_t* d_src, const float* d_ts,
   if (num_rows == 0) return;
   GF_REQUIRE(d_src && d_ts, w + ": null src or ts");
   GF_REQUIRE(d_nodes && d_eids && d_times, w + ": null nodes, eids or times");
-  // a store without a node has no history: every walk ends on step 0, which the kernel writes
-  const bool empty = g.table_len == 0 || g.table == nullptr || g.ts_pool == nullptr ||
-                     g.nbr_pool == nullptr;
-  // a node's run holds fewer than 2^32 edges: a larger bound is no bound
-  const uint32_t mh = max_history > 0xFFFFFFFFull ? 0u : static_cast<uint32_t>(max_history);
   const uint64_t walks = static_cast<uint64_t>(num_rows) * num_walks;
-  WalkArgs a = {g.table, empty ? 0 : g.table_len, g.ts_pool, g.nbr_pool, d_src, d_ts, walks,
-                static_cast<uint32_t>(num_walks), static_cast<uint32_t>(length),
-                static_cast<uint32_t>(recency), mh, seed, epoch, first_row, d_nodes, d_eids,
-                d_times};
+  WalkArgs a = {store_view(g), d_src, d_ts, walks, static_cast<uint32_t>(num_walks),
+                static_cast<uint32_t>(length), static_cast<uint32_t>(recency),
+                history_bound(max_history), seed, epoch, first_row, d_nodes, d_eids, d_times};
   DeviceGuard dg(device);
-  const uint64_t groups = (walks + kThreads - 1) / kThreads;
-  temporal_walk_kernel<<<dim3(static_cast<uint32_t>(std::min<uint64_t>(groups, kMaxGrid))),
-                         dim3(kThreads), 0, stream>>>(a);
+  temporal_walk_kernel<<<strided_grid(walks, kThreads, kMaxGrid), dim3(kThreads), 0, stream>>>(a);
   GF_HIP(hipGetLastError());
 }
 

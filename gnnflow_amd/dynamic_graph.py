@@ -14,45 +14,11 @@ def _i64(a):
     return np.ascontiguousarray(a, dtype=np.int64)
 
 
-def check_seen_mask_args(src, ts, cand_ids, max_history=0):
-    """Arguments of DynamicGraph.seen_mask, checked before anything is launched: the kernel takes
-    raw pointers and trusts them.  Needs no device.  Returns (B, C)."""
-    for name, x, dtype in (("src", src, torch.int64), ("ts", ts, torch.float32),
-                           ("cand_ids", cand_ids, torch.int64)):
-        if not isinstance(x, torch.Tensor):
-            raise TypeError("{} must be a tensor, got {}".format(name, type(x).__name__))
-        if x.dtype != dtype:
-            raise TypeError("{} must be {}, got {}".format(name, dtype, x.dtype))
-    if isinstance(max_history, bool) or not isinstance(max_history, int):
-        raise TypeError("max_history must be an int, got {}".format(type(max_history).__name__))
-    for name, x in (("src", src), ("ts", ts), ("cand_ids", cand_ids)):
-        if x.dim() != 1:
-            raise ValueError("{} must be 1-D, got shape {}".format(name, tuple(x.shape)))
-    B, Cn = int(src.shape[0]), int(cand_ids.shape[0])
-    if int(ts.shape[0]) != B:
-        raise ValueError("src has {} rows, ts has {}".format(B, int(ts.shape[0])))
-    if Cn == 0:
-        raise ValueError("seen_mask needs at least one candidate")
-    if Cn >= 2 ** 31:
-        raise ValueError("seen_mask takes fewer than 2**31 candidates, got {}".format(Cn))
-    if B >= 2 ** 31:
-        raise ValueError("seen_mask takes fewer than 2**31 rows, got {}".format(B))
-    if max_history < 0:
-        raise ValueError("max_history must be >= 0, got {}".format(max_history))
-    for name, x in (("ts", ts), ("cand_ids", cand_ids)):
-        if x.device != src.device:
-            raise ValueError("{} is on {}, src on {}".format(name, x.device, src.device))
-    return B, Cn
+# The checkers of the edge-history readers are built from the helpers below.  Each checker calls
+# them in the order in which its errors are reported when several arguments are wrong, which is
+# part of its contract (tests/test_history_checkers.py).
 
-
-class PairHistory(NamedTuple):
-    """What DynamicGraph.pair_history returns, one entry per (src, dst, ts) row."""
-    count: torch.Tensor      # int64 [N]; considered edges of src that lead to dst
-    last_ts: torch.Tensor    # float32 [N]; time of the latest of them, -inf where count == 0
-    last_eid: torch.Tensor   # int64 [N]; its edge id, -1 where count == 0
-
-
-def _typed_tensors(tensors, since):
+def _typed_tensors(tensors, since=None):
     """The (name, tensor, dtype) triples, `since` appended when it is a tensor, after the type
     checks the history readers share."""
     tensors = list(tensors)
@@ -70,17 +36,31 @@ def _typed_tensors(tensors, since):
     return tensors
 
 
-def _pair_rows(tensors, what):
-    """N of 1-D tensors of one length, the first of them src; fewer than 2**31."""
+def _one_dim(tensors):
     for name, x, _ in tensors:
         if x.dim() != 1:
             raise ValueError("{} must be 1-D, got shape {}".format(name, tuple(x.shape)))
+
+
+def _equal_rows(tensors):
+    """N of 1-D tensors of one length, the first of them src."""
     N = int(tensors[0][1].shape[0])
     for name, x, _ in tensors[1:]:
         if int(x.shape[0]) != N:
             raise ValueError("src has {} rows, {} has {}".format(N, name, int(x.shape[0])))
-    if N >= 2 ** 31:
-        raise ValueError("{} takes fewer than 2**31 rows, got {}".format(what, N))
+    return N
+
+
+def _below_2_31(n, what, unit):
+    if n >= 2 ** 31:
+        raise ValueError("{} takes fewer than 2**31 {}, got {}".format(what, unit, n))
+
+
+def _rows(tensors, what):
+    """N of 1-D tensors of one length, the first of them src; fewer than 2**31."""
+    _one_dim(tensors)
+    N = _equal_rows(tensors)
+    _below_2_31(N, what, "rows")
     return N
 
 
@@ -91,19 +71,63 @@ def _same_device(tensors):
             raise ValueError("{} is on {}, {} on {}".format(name, x.device, first, x0.device))
 
 
+def _int_arg(value, name, lo, hi):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+        raise TypeError("{} must be an int, got {}".format(name, type(value).__name__))
+    value = int(value)
+    if not lo <= value < hi:
+        raise ValueError("{} must be in [{}, {}), got {}".format(name, lo, hi, value))
+    return value
+
+
+# seen_mask and pair_history report max_history in two steps: its type with the other type
+# errors, ahead of the shapes, and its sign after the shapes.  A numpy integer is not an int here.
+
+def _history_type(max_history):
+    if isinstance(max_history, bool) or not isinstance(max_history, int):
+        raise TypeError("max_history must be an int, got {}".format(type(max_history).__name__))
+
+
+def _history_sign(max_history):
+    if max_history < 0:
+        raise ValueError("max_history must be >= 0, got {}".format(max_history))
+
+
 def _pair_tensors(src, dst, ts):
     return [("src", src, torch.int64), ("dst", dst, torch.int64), ("ts", ts, torch.float32)]
+
+
+def check_seen_mask_args(src, ts, cand_ids, max_history=0):
+    """Arguments of DynamicGraph.seen_mask, checked before anything is launched: the kernel takes
+    raw pointers and trusts them.  Needs no device.  Returns (B, C)."""
+    tensors = _typed_tensors([("src", src, torch.int64), ("ts", ts, torch.float32),
+                              ("cand_ids", cand_ids, torch.int64)])
+    _history_type(max_history)
+    _one_dim(tensors)
+    B, Cn = _equal_rows(tensors[:2]), int(cand_ids.shape[0])
+    if Cn == 0:
+        raise ValueError("seen_mask needs at least one candidate")
+    _below_2_31(Cn, "seen_mask", "candidates")
+    _below_2_31(B, "seen_mask", "rows")
+    _history_sign(max_history)
+    _same_device(tensors)
+    return B, Cn
+
+
+class PairHistory(NamedTuple):
+    """What DynamicGraph.pair_history returns, one entry per (src, dst, ts) row."""
+    count: torch.Tensor      # int64 [N]; considered edges of src that lead to dst
+    last_ts: torch.Tensor    # float32 [N]; time of the latest of them, -inf where count == 0
+    last_eid: torch.Tensor   # int64 [N]; its edge id, -1 where count == 0
 
 
 def check_pair_history_args(src, dst, ts, since=None, max_history=0):
     """Arguments of DynamicGraph.pair_history, checked before anything is launched: the kernel
     takes raw pointers and trusts them.  Needs no device.  Returns N."""
     tensors = _typed_tensors(_pair_tensors(src, dst, ts), since)
-    if isinstance(max_history, bool) or not isinstance(max_history, int):
-        raise TypeError("max_history must be an int, got {}".format(type(max_history).__name__))
-    N = _pair_rows(tensors, "pair_history")
-    if max_history < 0:
-        raise ValueError("max_history must be >= 0, got {}".format(max_history))
+    _history_type(max_history)
+    N = _rows(tensors, "pair_history")
+    _history_sign(max_history)
     _same_device(tensors)
     return N
 
@@ -131,7 +155,7 @@ def check_common_neighbors_args(src, dst, ts, since=None, max_history=64, max_co
     tensors = _typed_tensors(_pair_tensors(src, dst, ts), since)
     H = _int_arg(max_history, "max_history", 1, CN_MAX_HISTORY + 1)
     K = _int_arg(max_common, "max_common", 0, CN_MAX_HISTORY + 1)
-    N = _pair_rows(tensors, "common_neighbors")
+    N = _rows(tensors, "common_neighbors")
     _same_device(tensors)
     return N, H, K
 
@@ -144,9 +168,7 @@ def check_temporal_degree_args(nodes, ts, since=None):
         if tuple(x.shape) != tuple(nodes.shape):
             raise ValueError("nodes has shape {}, {} has {}".format(
                 tuple(nodes.shape), name, tuple(x.shape)))
-    if nodes.numel() >= 2 ** 31:
-        raise ValueError("temporal_degree takes fewer than 2**31 elements, got {}".format(
-            nodes.numel()))
+    _below_2_31(nodes.numel(), "temporal_degree", "elements")
     _same_device(tensors)
     return int(nodes.numel())
 
@@ -163,42 +185,24 @@ class TemporalWalks(NamedTuple):
     times: torch.Tensor      # float32 [B, W, L]; its timestamp
 
 
-def _int_arg(value, name, lo, hi):
-    if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
-        raise TypeError("{} must be an int, got {}".format(name, type(value).__name__))
-    value = int(value)
-    if not lo <= value < hi:
-        raise ValueError("{} must be in [{}, {}), got {}".format(name, lo, hi, value))
-    return value
-
-
 def check_temporal_walk_args(src, ts, length, num_walks=1, recency=1, max_history=0, seed=0,
                              epoch=0, first_row=0):
     """Arguments of DynamicGraph.temporal_random_walk, checked before anything is launched or
     allocated: the kernel takes raw pointers and trusts them.  Needs no device.
     Returns (B, W, L)."""
-    for name, x, dtype in (("src", src, torch.int64), ("ts", ts, torch.float32)):
-        if not isinstance(x, torch.Tensor):
-            raise TypeError("{} must be a tensor, got {}".format(name, type(x).__name__))
-        if x.dtype != dtype:
-            raise TypeError("{} must be {}, got {}".format(name, dtype, x.dtype))
+    tensors = _typed_tensors([("src", src, torch.int64), ("ts", ts, torch.float32)])
     L = _int_arg(length, "length", 1, WALK_MAX_LENGTH + 1)
     W = _int_arg(num_walks, "num_walks", 1, 2 ** 16)
     _int_arg(recency, "recency", 1, WALK_MAX_RECENCY + 1)
     _int_arg(max_history, "max_history", 0, 2 ** 64)
     for name, x in (("seed", seed), ("epoch", epoch), ("first_row", first_row)):
         _int_arg(x, name, 0, 2 ** 64)
-    for name, x in (("src", src), ("ts", ts)):
-        if x.dim() != 1:
-            raise ValueError("{} must be 1-D, got shape {}".format(name, tuple(x.shape)))
-    B = int(src.shape[0])
-    if int(ts.shape[0]) != B:
-        raise ValueError("src has {} rows, ts has {}".format(B, int(ts.shape[0])))
+    _one_dim(tensors)
+    B = _equal_rows(tensors)
     if B * W >= 2 ** 31:
         raise ValueError("temporal_random_walk takes fewer than 2**31 walks per call, got "
                          "{} x {}".format(B, W))
-    if ts.device != src.device:
-        raise ValueError("ts is on {}, src on {}".format(ts.device, src.device))
+    _same_device(tensors)
     return B, W, L
 
 
@@ -360,6 +364,27 @@ class DynamicGraph:
                 n.value, C.byref(n)))
         return d, t, e
 
+    # What the edge-history readers below share: the device check, the `since` conversion and
+    # the launch on the current stream.
+
+    def _check_on_device(self, dev):
+        if dev.type != "cuda" or (dev.index is not None and dev.index != self._device):
+            raise ValueError("the graph is on device cuda:{}, the inputs on {}".format(
+                self._device, dev))
+
+    @staticmethod
+    def _since_tensor(since, shape, dev):
+        if since is None:
+            return None
+        if isinstance(since, torch.Tensor):
+            return since.detach().contiguous()
+        return torch.full(shape, float(since), dtype=torch.float32, device=dev)
+
+    def _launch(self, fn, *args):
+        """fn(graph, *args, device, the current stream), checked"""
+        _capi.check(fn(self._h, *args, self._device,
+                       _capi.current_stream(torch.device("cuda", self._device))))
+
     def seen_mask(self, src: torch.Tensor, ts: torch.Tensor, cand_ids: torch.Tensor,
                   max_history: int = 0) -> torch.Tensor:
         """Which of the candidates has each source already met: an int64 tensor [B, W],
@@ -389,19 +414,16 @@ class DynamicGraph:
         is 10^6 record reads for its row.  max_history is what bounds it."""
         B, Cn = check_seen_mask_args(src, ts, cand_ids, max_history)
         dev = src.device
-        if dev.type != "cuda" or (dev.index is not None and dev.index != self._device):
-            raise ValueError("the graph is on device cuda:{}, the inputs on {}".format(
-                self._device, dev))
+        self._check_on_device(dev)
         W = (Cn + 63) // 64
         with torch.cuda.device(self._device):
             mask = torch.zeros((B, W), dtype=torch.int64, device=dev)
             if B:
                 sorted_ids, perm = torch.sort(cand_ids.detach())
                 s, t = src.detach().contiguous(), ts.detach().contiguous()
-                _capi.check(self._lib.gf_graph_seen_mask(
-                    self._h, s.data_ptr(), t.data_ptr(), B, sorted_ids.data_ptr(),
-                    perm.data_ptr(), Cn, max_history, mask.data_ptr(), self._device,
-                    _capi.current_stream(torch.device("cuda", self._device))))
+                self._launch(self._lib.gf_graph_seen_mask, s.data_ptr(), t.data_ptr(), B,
+                             sorted_ids.data_ptr(), perm.data_ptr(), Cn, max_history,
+                             mask.data_ptr())
         return mask
 
     def pair_history(self, src: torch.Tensor, dst: torch.Tensor, ts: torch.Tensor, *,
@@ -421,7 +443,8 @@ class DynamicGraph:
         history includes the edges that pointed at the source.  Any dst is legal (negative,
         unknown to the graph) and matches nothing; a source that is negative, past the node table
         or without live edges gives (0, -inf, -1).  The exact rule is in include/gnnflow_hip.h
-        (gf_graph_pair_history) and restated in numpy in tests/pair_history_ref.py.
+        (gf_graph_pair_history), the window in csrc/history_window.hpp, and it is restated in
+        numpy in tests/pair_history_ref.py.
 
         src, dst: int64 [N], ts: float32 [N]; since: None, a float (the same lower end for every
         row) or a float32 tensor [N]; all tensors on the graph's device.  N == 0 returns three
@@ -438,40 +461,18 @@ class DynamicGraph:
         max_history and since are what bound it."""
         N = check_pair_history_args(src, dst, ts, since, max_history)
         dev = src.device
-        if dev.type != "cuda" or (dev.index is not None and dev.index != self._device):
-            raise ValueError("the graph is on device cuda:{}, the inputs on {}".format(
-                self._device, dev))
+        self._check_on_device(dev)
         with torch.cuda.device(self._device):
             count = torch.empty(N, dtype=torch.int64, device=dev)
             last_ts = torch.empty(N, dtype=torch.float32, device=dev)
             last_eid = torch.empty(N, dtype=torch.int64, device=dev)
             if N:
                 s, d, t = (x.detach().contiguous() for x in (src, dst, ts))
-                if since is None:
-                    lo = None
-                elif isinstance(since, torch.Tensor):
-                    lo = since.detach().contiguous()
-                else:
-                    lo = torch.full((N,), float(since), dtype=torch.float32, device=dev)
-                _capi.check(self._lib.gf_graph_pair_history(
-                    self._h, s.data_ptr(), d.data_ptr(), t.data_ptr(),
-                    None if lo is None else lo.data_ptr(), N, max_history, count.data_ptr(),
-                    last_ts.data_ptr(), last_eid.data_ptr(), self._device,
-                    _capi.current_stream(torch.device("cuda", self._device))))
+                lo = self._since_tensor(since, (N,), dev)
+                self._launch(self._lib.gf_graph_pair_history, s.data_ptr(), d.data_ptr(),
+                             t.data_ptr(), None if lo is None else lo.data_ptr(), N, max_history,
+                             count.data_ptr(), last_ts.data_ptr(), last_eid.data_ptr())
         return PairHistory(count, last_ts, last_eid)
-
-    def _check_on_device(self, dev):
-        if dev.type != "cuda" or (dev.index is not None and dev.index != self._device):
-            raise ValueError("the graph is on device cuda:{}, the inputs on {}".format(
-                self._device, dev))
-
-    @staticmethod
-    def _since_tensor(since, shape, dev):
-        if since is None:
-            return None
-        if isinstance(since, torch.Tensor):
-            return since.detach().contiguous()
-        return torch.full(shape, float(since), dtype=torch.float32, device=dev)
 
     def common_neighbors(self, src: torch.Tensor, dst: torch.Tensor, ts: torch.Tensor, *,
                          since=None, max_history: int = 64,
@@ -502,8 +503,8 @@ class DynamicGraph:
         has dst[i] among src[i]'s neighbours (and the other way round), and dst[i] is a common
         neighbour if it also has a loop.  A node that is negative, past the node table or without
         live edges has no considered edge.  "Strictly before" and "live" as for seen_mask.  The
-        exact rule is in include/gnnflow_hip.h (gf_graph_common_neighbors) and restated in numpy
-        in tests/common_neighbors_ref.py.
+        exact rule is in include/gnnflow_hip.h (gf_graph_common_neighbors), the window in
+        csrc/history_window.hpp, and it is restated in numpy in tests/common_neighbors_ref.py.
 
         src, dst: int64 [N], ts: float32 [N]; since: None, a float or a float32 tensor [N]; all
         tensors on the graph's device; 0 <= max_common <= 512.  N == 0 returns empty tensors of
@@ -526,13 +527,12 @@ class DynamicGraph:
             if N:
                 s, d, t = (x.detach().contiguous() for x in (src, dst, ts))
                 lo = self._since_tensor(since, (N,), dev)
-                _capi.check(self._lib.gf_graph_common_neighbors(
-                    self._h, s.data_ptr(), d.data_ptr(), t.data_ptr(),
-                    None if lo is None else lo.data_ptr(), N, H, K, n_src.data_ptr(),
-                    n_dst.data_ptr(), u_src.data_ptr(), u_dst.data_ptr(), common.data_ptr(),
-                    nodes.data_ptr() if K else None, cnt_src.data_ptr() if K else None,
-                    cnt_dst.data_ptr() if K else None, self._device,
-                    _capi.current_stream(torch.device("cuda", self._device))))
+                self._launch(self._lib.gf_graph_common_neighbors, s.data_ptr(), d.data_ptr(),
+                             t.data_ptr(), None if lo is None else lo.data_ptr(), N, H, K,
+                             n_src.data_ptr(), n_dst.data_ptr(), u_src.data_ptr(),
+                             u_dst.data_ptr(), common.data_ptr(),
+                             nodes.data_ptr() if K else None, cnt_src.data_ptr() if K else None,
+                             cnt_dst.data_ptr() if K else None)
         return CommonNeighbors(n_src, n_dst, u_src, u_dst, common, nodes, cnt_src, cnt_dst)
 
     def temporal_degree(self, nodes: torch.Tensor, ts: torch.Tensor, *,
@@ -554,10 +554,8 @@ class DynamicGraph:
             if n:
                 v, t = nodes.detach().contiguous(), ts.detach().contiguous()
                 lo = self._since_tensor(since, nodes.shape, dev)
-                _capi.check(self._lib.gf_graph_temporal_degree(
-                    self._h, v.data_ptr(), t.data_ptr(), None if lo is None else lo.data_ptr(),
-                    n, out.data_ptr(), self._device,
-                    _capi.current_stream(torch.device("cuda", self._device))))
+                self._launch(self._lib.gf_graph_temporal_degree, v.data_ptr(), t.data_ptr(),
+                             None if lo is None else lo.data_ptr(), n, out.data_ptr())
         return out
 
     def temporal_random_walk(self, src: torch.Tensor, ts: torch.Tensor, length: int,
@@ -574,7 +572,8 @@ class DynamicGraph:
         times[i, w, j], which become the next v and t.  A walk ends where v is negative or past
         the node table or has no considered edge; every slot from that step on holds nodes = -1,
         eids = -1, times = 0.  The exact rule, draws included, is in include/gnnflow_hip.h
-        (gf_graph_temporal_walks) and restated in numpy in tests/temporal_walk_ref.py.
+        (gf_graph_temporal_walks), the window in csrc/history_window.hpp, and it is restated in
+        numpy in tests/temporal_walk_ref.py.
 
         - Time strictly decreases along a walk: no edge is taken twice, an edge at the current
           time (a tie) is never followed, and a NaN time ends the walk at once.
@@ -604,20 +603,16 @@ class DynamicGraph:
         B, W, L = check_temporal_walk_args(src, ts, length, num_walks, recency, max_history,
                                            seed, epoch, first_row)
         dev = src.device
-        if dev.type != "cuda" or (dev.index is not None and dev.index != self._device):
-            raise ValueError("the graph is on device cuda:{}, the inputs on {}".format(
-                self._device, dev))
+        self._check_on_device(dev)
         with torch.cuda.device(self._device):
             nodes = torch.empty((B, W, L + 1), dtype=torch.int64, device=dev)
             eids = torch.empty((B, W, L), dtype=torch.int64, device=dev)
             times = torch.empty((B, W, L), dtype=torch.float32, device=dev)
             if B:
                 s, t = src.detach().contiguous(), ts.detach().contiguous()
-                _capi.check(self._lib.gf_graph_temporal_walks(
-                    self._h, s.data_ptr(), t.data_ptr(), B, W, L, int(recency),
-                    int(max_history), int(seed), int(epoch), int(first_row),
-                    nodes.data_ptr(), eids.data_ptr(), times.data_ptr(), self._device,
-                    _capi.current_stream(torch.device("cuda", self._device))))
+                self._launch(self._lib.gf_graph_temporal_walks, s.data_ptr(), t.data_ptr(), B,
+                             W, L, int(recency), int(max_history), int(seed), int(epoch),
+                             int(first_row), nodes.data_ptr(), eids.data_ptr(), times.data_ptr())
         return TemporalWalks(nodes, eids, times)
 
     def _float(self, fn) -> float:
