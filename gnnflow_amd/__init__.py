@@ -6,15 +6,18 @@ kernels (gfx950) behind the C ABI of include/gnnflow_hip.h.
 """
 from .baselines import EdgeBank, NeighborOverlap
 from .data import DeviceBatchStream, DeviceDstSet
-from .dynamic_graph import CommonNeighbors, DynamicGraph, PairHistory, TemporalWalks
+from .dynamic_graph import (CommonNeighbors, DynamicGraph, NeighborCooccurrence, PairHistory,
+                            TemporalWalks)
 from .metrics import LinkMetrics
 from .mfg import MFGBlock
 from .nn import (MLP, EdgePredictor, GATConv, GRUMemeoryUpdater, GRUMemoryUpdater, LinkLoss,
-                 SAGEConv, TemporalAttentionLayer, TimeEncode, TransfomerAttentionLayer)
+                 NeighborCooccurrenceEncoder, SAGEConv, TemporalAttentionLayer, TimeEncode,
+                 TransfomerAttentionLayer)
 from .temporal_sampler import SamplingResult, TemporalSampler
 
 __all__ = ["DynamicGraph", "TemporalSampler", "SamplingResult", "MFGBlock", "SAGEConv", "GATConv",
            "TimeEncode", "TemporalAttentionLayer", "TransfomerAttentionLayer", "GRUMemoryUpdater",
            "GRUMemeoryUpdater", "EdgePredictor", "MLP", "LinkMetrics", "LinkLoss",
            "DeviceDstSet", "DeviceBatchStream", "TemporalWalks", "PairHistory", "EdgeBank",
-           "CommonNeighbors", "NeighborOverlap"]
+           "CommonNeighbors", "NeighborOverlap", "NeighborCooccurrence",
+           "NeighborCooccurrenceEncoder"]

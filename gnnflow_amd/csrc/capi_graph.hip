@@ -3,6 +3,7 @@
 #include "capi_handles.hpp"
 #include "common_neighbors.hpp"
 #include "hist_negatives.hpp"
+#include "neighbor_cooccurrence.hpp"
 #include "pair_history.hpp"
 #include "seen_mask.hpp"
 #include "temporal_walk.hpp"
@@ -132,6 +133,19 @@ int gf_graph_temporal_degree(const gf_graph* g, const int64_t* d_nodes, const fl
     GF_G(g);
     gf::temporal_degree(g->impl.view(), d_nodes, d_ts, d_since, num, d_out, device,
                         as_stream(stream));
+  });
+}
+// reads the store's view NOW, as gf_batch_hist_negatives does
+int gf_graph_neighbor_cooccurrence(const gf_graph* g, const int64_t* d_src, const int64_t* d_dst,
+                                   const float* d_ts, const float* d_since, size_t num_rows,
+                                   size_t length, int include_self, int32_t* d_lengths,
+                                   int64_t* d_nodes, int64_t* d_eids, float* d_times,
+                                   int32_t* d_counts, int device, void* stream) {
+  return guarded([&] {
+    GF_G(g);
+    gf::neighbor_cooccurrence(g->impl.view(), d_src, d_dst, d_ts, d_since, num_rows, length,
+                              include_self != 0, d_lengths, d_nodes, d_eids, d_times, d_counts,
+                              device, as_stream(stream));
   });
 }
 // reads the store's view NOW, as gf_batch_hist_negatives does

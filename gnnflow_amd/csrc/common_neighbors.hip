@@ -24,7 +24,8 @@
 // `cap`, are the power of two >= 4H (>= 4): the load stays <= 1/2.  Every probe loop runs at most
 // cap trips and then gives the record up instead of spinning; that cannot happen, because with at
 // most cap / 2 keys in cap slots a probe sequence meets the record's own key or an empty slot
-// first, and no slot is ever emptied while records are inserted.
+// first, and no slot is ever emptied while records are inserted.  The probing (claim, find) and
+// the end of a phase are lds_id_table.hpp's, shared with neighbor_cooccurrence.hip.
 //
 // Three instantiations by H, the LDS bytes fixed per instantiation, `cap` slots of it cleared
 // and used:
@@ -56,6 +57,7 @@
 #include "common_neighbors.hpp"
 #include "common.hpp"
 #include "history_window.hpp"
+#include "lds_id_table.hpp"
 
 namespace gf {
 namespace {
@@ -64,9 +66,8 @@ static_assert(kCnMaxHistory == GF_CN_MAX_HISTORY,
               "gnnflow_hip.h and common_neighbors.hpp disagree on the history limit");
 
 constexpr int kThreads = 256;
-constexpr int kWave = 64;
+constexpr int kWave = kIdTableWave;
 constexpr uint32_t kMaxGrid = 4096;      // workgroups; the rows past a pass are grid-strided
-constexpr int64_t kEmpty = -1;
 
 struct CnArgs {
   StoreView store;
@@ -97,53 +98,6 @@ struct Table {
   uint32_t b[CAP];
   uint32_t sum[4];           // u_src, u_dst, common of the row where several waves share it
 };
-
-// TPR threads work on a row.  One wave: its LDS operations complete in order, the fence is for the
-// compiler.  Several waves: a barrier, reached by every wave of the workgroup the same number of
-// times (see the header comment).
-template <int TPR>
-__device__ __forceinline__ void phase_end() {
-  if constexpr (TPR == kWave) {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-  } else {
-    __syncthreads();
-  }
-}
-
-__device__ __forceinline__ uint32_t home_slot(int64_t z, uint32_t shift) {
-  return static_cast<uint32_t>((static_cast<uint64_t>(z) * 0x9E3779B97F4A7C15ull) >> shift);
-}
-
-// the slot of key z, claimed if z is new; cap when the table is full (it never is: header comment)
-template <int CAP>
-__device__ __forceinline__ uint32_t claim(Table<CAP>& tb, int64_t z, uint32_t cap, uint32_t shift) {
-  uint32_t h = home_slot(z, shift);
-  for (uint32_t i = 0; i < cap; ++i) {
-    const unsigned long long seen =
-        atomicCAS(reinterpret_cast<unsigned long long*>(&tb.key[h]),
-                  static_cast<unsigned long long>(kEmpty), static_cast<unsigned long long>(z));
-    if (seen == static_cast<unsigned long long>(kEmpty) ||
-        seen == static_cast<unsigned long long>(z))
-      return h;
-    h = (h + 1) & (cap - 1);
-  }
-  return cap;
-}
-
-// the slot that holds key z; cap if none does (an inserted key is always found)
-template <int CAP>
-__device__ __forceinline__ uint32_t find(const Table<CAP>& tb, int64_t z, uint32_t cap,
-                                         uint32_t shift) {
-  uint32_t h = home_slot(z, shift);
-  for (uint32_t i = 0; i < cap; ++i) {
-    const int64_t k = tb.key[h];
-    if (k == z) return h;
-    if (k == kEmpty) break;
-    h = (h + 1) & (cap - 1);
-  }
-  return cap;
-}
 
 template <int CAP, int TPR>
 __global__ void __launch_bounds__(kThreads) common_neighbors_kernel(const CnArgs a) {
@@ -179,7 +133,7 @@ __global__ void __launch_bounds__(kThreads) common_neighbors_kernel(const CnArgs
     }
 
     for (uint32_t x = rl; x < cap; x += TPR) {
-      tb.key[x] = kEmpty;
+      tb.key[x] = kIdEmpty;
       tb.pa[x] = -1;
       tb.a[x] = tb.b[x] = 0;
     }

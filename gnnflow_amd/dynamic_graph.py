@@ -173,6 +173,33 @@ def check_temporal_degree_args(nodes, ts, since=None):
     return int(nodes.numel())
 
 
+COOC_MAX_LENGTH = 512      # GF_COOC_MAX_LENGTH
+
+
+class NeighborCooccurrence(NamedTuple):
+    """What DynamicGraph.neighbor_cooccurrence returns, one row per (src, dst, ts) row; side 0 is
+    src's sequence, side 1 dst's, L = length slots each, oldest first after the self slot."""
+    lengths: torch.Tensor    # int32 [N, 2]; filled slots of each side, the self slot included
+    nodes: torch.Tensor      # int64 [N, 2, L]; the sequence's nodes, then -1
+    eids: torch.Tensor       # int64 [N, 2, L]; the edges' ids; -1 for the self slot and the padding
+    times: torch.Tensor      # float32 [N, 2, L]; the edges' times; ts for the self slot; 0 padding
+    counts: torch.Tensor     # int32 [N, 2, L, 2]; occurrences in src's, in dst's sequence
+
+
+def check_neighbor_cooccurrence_args(src, dst, ts, since=None, length=32, include_self=True):
+    """Arguments of DynamicGraph.neighbor_cooccurrence, checked before anything is launched or
+    allocated: the kernel takes raw pointers and trusts them.  Needs no device.
+    Returns (N, L, self)."""
+    tensors = _typed_tensors(_pair_tensors(src, dst, ts), since)
+    if not isinstance(include_self, bool):
+        raise TypeError("include_self must be a bool, got {}".format(type(include_self).__name__))
+    # length - include_self bounds the window, and a bound of 0 would be "no bound"
+    L = _int_arg(length, "length", 1 + int(include_self), COOC_MAX_LENGTH + 1)
+    N = _rows(tensors, "neighbor_cooccurrence")
+    _same_device(tensors)
+    return N, L, int(include_self)
+
+
 WALK_MAX_LENGTH = 32      # GF_WALK_MAX_LENGTH
 WALK_MAX_RECENCY = 8      # GF_WALK_MAX_RECENCY
 
@@ -557,6 +584,73 @@ class DynamicGraph:
                 self._launch(self._lib.gf_graph_temporal_degree, v.data_ptr(), t.data_ptr(),
                              None if lo is None else lo.data_ptr(), n, out.data_ptr())
         return out
+
+    def neighbor_cooccurrence(self, src: torch.Tensor, dst: torch.Tensor, ts: torch.Tensor, *,
+                              since=None, length: int = 32,
+                              include_self: bool = True) -> NeighborCooccurrence:
+        """The pair inputs of the sequence-based temporal models (DyGFormer, GraphMixer):
+        NeighborCooccurrence(lengths int32 [N, 2]; nodes, eids int64 [N, 2, L]; times float32
+        [N, 2, L]; counts int32 [N, 2, L, 2]), L = length.  Side 0 is src[i]'s sequence, side 1
+        dst[i]'s.
+
+        The sequence of a node is, with include_self, the node itself and then its considered
+        edges, oldest first.  The considered edges are common_neighbors': the node's live edges
+        in the store whose timestamp is strictly below ts[i] (float <: a NaN time gives none)
+        and, with `since`, not below since[i] -- the lower end is inclusive, a NaN since[i] is no
+        lower end -- and of that window only the newest H = length - include_self, so that a
+        side never has more than `length` elements.  Both sides are taken at the same time and
+        lower end.
+
+        - lengths[i, side]: the filled slots, the self slot included.
+        - nodes[i, side]: the node itself (with include_self), then the destinations of its
+          considered edges, then -1.
+        - eids[i, side], times[i, side]: the edges' ids and timestamps, bits copied; the self slot
+          has eid -1 and time ts[i]; the padding has -1 and 0.  ts[i, None, None] - times is
+          the models' time delta.
+        - counts[i, side, p, 0], counts[i, side, p, 1]: how often nodes[i, side, p] occurs in
+          src[i]'s sequence and how often in dst[i]'s -- channel 0 is "in src's sequence" on both
+          sides, as DyGFormer's padded node appearances.  0, 0 in the padding.
+
+        The self slot is present whatever the node is (negative, unknown to the graph, without
+        edges) and counts as one occurrence of the node.  A negative id, the self slot's or a
+        stored destination's, is nobody's neighbour: it is not counted and its own counts are
+        0, 0; `lengths` tells it apart from the padding.  src[i] == dst[i] is legal: both sides
+        are then equal.  "Strictly before" and "live" as for seen_mask: edges that
+        offload_old_blocks took are gone, and on a graph built with reverse edges a node's
+        sequence also holds the nodes that pointed at it.  The exact rule is in
+        include/gnnflow_hip.h (gf_graph_neighbor_cooccurrence), the window in
+        csrc/history_window.hpp, and it is restated in numpy in
+        tests/neighbor_cooccurrence_ref.py.
+
+        src, dst: int64 [N], ts: float32 [N]; since: None, a float or a float32 tensor [N]; all
+        tensors on the graph's device; include_self a bool; 1 + include_self <= length <= 512.
+        N == 0 returns empty tensors of these shapes without a launch; a graph without nodes
+        gives the self slots alone.  nn.NeighborCooccurrenceEncoder turns the counts into
+        features.
+
+        One kernel (csrc/neighbor_cooccurrence.hip: a row's two sequences hashed into a table
+        in LDS, integers only, the same inputs give the same bits) on the current stream, memory
+        from torch, never synchronises.  Synchronise the streams that calls were launched on
+        before add_edges or offload_old_blocks, as for seen_mask.  The cost is the 2 * H records
+        read per row and the 2 * length * 32 bytes written."""
+        N, L, self_slot = check_neighbor_cooccurrence_args(src, dst, ts, since, length,
+                                                           include_self)
+        dev = src.device
+        self._check_on_device(dev)
+        with torch.cuda.device(self._device):
+            lengths = torch.empty((N, 2), dtype=torch.int32, device=dev)
+            nodes = torch.empty((N, 2, L), dtype=torch.int64, device=dev)
+            eids = torch.empty((N, 2, L), dtype=torch.int64, device=dev)
+            times = torch.empty((N, 2, L), dtype=torch.float32, device=dev)
+            counts = torch.empty((N, 2, L, 2), dtype=torch.int32, device=dev)
+            if N:
+                s, d, t = (x.detach().contiguous() for x in (src, dst, ts))
+                lo = self._since_tensor(since, (N,), dev)
+                self._launch(self._lib.gf_graph_neighbor_cooccurrence, s.data_ptr(),
+                             d.data_ptr(), t.data_ptr(), None if lo is None else lo.data_ptr(),
+                             N, L, self_slot, lengths.data_ptr(), nodes.data_ptr(),
+                             eids.data_ptr(), times.data_ptr(), counts.data_ptr())
+        return NeighborCooccurrence(lengths, nodes, eids, times, counts)
 
     def temporal_random_walk(self, src: torch.Tensor, ts: torch.Tensor, length: int,
                              num_walks: int = 1, *, recency: int = 1, max_history: int = 0,

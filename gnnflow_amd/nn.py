@@ -293,6 +293,74 @@ class TimeEncode(nn.Module):
         return torch.cos(self.w(delta_time.reshape(-1, 1)))
 
 
+class _GatherCountPair(torch.autograd.Function):
+    """out[r] = tab[i0[r]] + tab[i1[r]] where filled[r], else 0.  The table's gradient is a sum
+    of all rows into a handful: it is accumulated in float64 and rounded once, so that it neither
+    loses bits as the batch grows nor depends on the order of the adds beyond that rounding."""
+
+    @staticmethod
+    def forward(ctx, tab, i0, i1, filled):
+        ctx.save_for_backward(i0, i1, filled)
+        ctx.rows = tab.shape[0]
+        out = tab.index_select(0, i0) + tab.index_select(0, i1)
+        return out.masked_fill(~filled.unsqueeze(1), 0.0)
+
+    @staticmethod
+    def backward(ctx, grad):
+        i0, i1, filled = ctx.saved_tensors
+        g = grad.masked_fill(~filled.unsqueeze(1), 0.0).double()
+        d_tab = torch.zeros((ctx.rows, g.shape[1]), dtype=torch.float64, device=g.device)
+        d_tab.index_add_(0, i0, g)
+        d_tab.index_add_(0, i1, g)
+        return d_tab.to(grad.dtype), None, None, None
+
+
+class NeighborCooccurrenceEncoder(nn.Module):
+    """DyGFormer's neighbour co-occurrence encoder over DynamicGraph.neighbor_cooccurrence's
+    counts: f(c) = Linear(dim, dim)(ReLU(Linear(1, dim)(c))), and the feature of a sequence
+    element is f(its count in src's sequence) + f(its count in dst's).
+
+    forward(counts int [N, 2, L, 2], lengths int [N, 2]) -> float32 [N, 2, L, dim], the positions
+    at and past lengths[i, side] exactly zero.  A count is an integer in [0, L], so f is evaluated
+    once on arange(M + 1) and gathered: two tiny GEMMs and two index_selects instead of a GEMM over
+    N * 2 * L * 2 rows, and the gradient goes back through the gather (summed into the table's
+    M + 1 rows in float64, rounded once).  M = max_count
+    when given (the table then has the same size in every call; L above it is a ValueError), else
+    the call's own L.  Plain torch: no kernel of its own."""
+
+    def __init__(self, dim: int, max_count: Optional[int] = None):
+        super().__init__()
+        if max_count is not None and (isinstance(max_count, bool) or
+                                      not isinstance(max_count, int) or max_count < 1):
+            raise ValueError("max_count must be None or an int >= 1, got {!r}".format(max_count))
+        self.dim, self.max_count = int(dim), max_count
+        self.lift = nn.Linear(1, dim)
+        self.proj = nn.Linear(dim, dim)
+
+    def table(self, max_count: int) -> torch.Tensor:
+        """f(0), f(1), .. f(max_count): float [max_count + 1, dim]"""
+        c = torch.arange(max_count + 1, device=self.lift.weight.device,
+                         dtype=self.lift.weight.dtype)
+        return self.proj(F.relu(self.lift(c.unsqueeze(1))))
+
+    def forward(self, counts: torch.Tensor, lengths: torch.Tensor) -> torch.Tensor:
+        if counts.dim() != 4 or counts.shape[1] != 2 or counts.shape[3] != 2:
+            raise ValueError("counts must be [N, 2, L, 2], got shape {}".format(
+                tuple(counts.shape)))
+        N, _, L, _ = counts.shape
+        if tuple(lengths.shape) != (N, 2):
+            raise ValueError("lengths must be [{}, 2], got shape {}".format(
+                N, tuple(lengths.shape)))
+        M = L if self.max_count is None else self.max_count
+        if L > M:
+            raise ValueError("sequences of {} slots, max_count is {}".format(L, M))
+        idx = counts.reshape(-1, 2).long()
+        filled = torch.arange(L, device=lengths.device) < lengths.unsqueeze(2)
+        out = _GatherCountPair.apply(self.table(M), idx[:, 0].contiguous(),
+                                     idx[:, 1].contiguous(), filled.reshape(-1))
+        return out.reshape(N, 2, L, self.dim)
+
+
 class TemporalAttentionLayer(nn.Module):
     """Temporal multi-head attention over a sampled block (reads b.srcdata['h'], b.edata['f'],
     b.edata['dt']):

@@ -1508,6 +1508,57 @@ GF_API int gf_graph_temporal_degree(const gf_graph* g, const int64_t* d_nodes, c
                                     const float* d_since /* NULL: no lower end */, size_t num,
                                     int64_t* d_out, int device, void* stream);
 
+/* The pair inputs of the sequence-based temporal models (DyGFormer, GraphMixer): the most recent
+ * interactions of both ends of each of num_rows pairs as two padded sequences of node id, edge id
+ * and time, and for every element of either sequence how often that node occurs in the source's
+ * sequence and how often in the destination's (DyGFormer's neighbour co-occurrence encoding).
+ * Row i has source s = d_src[i], destination d = d_dst[i], time t = d_ts[i] and, when d_since is
+ * not NULL, lower end lo = d_since[i].  With L = length (slots per side) and self = 1 when
+ * include_self != 0, else 0:
+ *   H        = L - self, the bound of the window, 1 <= H <= GF_COOC_MAX_LENGTH - self
+ *   W(v)     = the window of node v at (t, lo, H) exactly as defined for
+ *              gf_graph_common_neighbors (strictly before t, lo inclusive, the newest H, a NaN t
+ *              gives none, a NaN lo is no lower end; empty for v < 0, v >= table_len, no live
+ *              edge or a store without a node), oldest first, n(v) = |W(v)| <= H
+ *   seq(v)   = [v itself if self] followed by the dst of W(v)'s records; len(v) = self + n(v) <= L
+ *   a(z), b(z) = how often z occurs in seq(s), in seq(d), for z >= 0
+ * Side 0 is s's and side 1 is d's.  All outputs are row-major and contiguous, and every element
+ * is written, so they need no initialisation:
+ *   d_lengths int32   [num_rows, 2]        len(s), len(d)
+ *   d_nodes   int64   [num_rows, 2, L]     seq(v), then -1
+ *   d_eids    int64   [num_rows, 2, L]     the records' eid; -1 for the self slot and the padding
+ *   d_times   float32 [num_rows, 2, L]     the records' ts, bits copied; t for the self slot (also
+ *                                          when t is NaN); 0 in the padding
+ *   d_counts  int32   [num_rows, 2, L, 2]  [.., p, 0] = a(d_nodes[.., p]), [.., p, 1] =
+ *                                          b(d_nodes[.., p]); 0, 0 in the padding
+ * - Self slot.  With include_self the self slot is present whatever the node is (negative,
+ *   unknown to the graph, without edges): it is what DyGFormer puts at position 0, and it counts
+ *   as one occurrence of v in seq(v).
+ * - Negative ids.  A negative id, the self slot's or a stored destination's, is nobody's
+ *   neighbour: it is not counted and its own counts are 0, 0, as in gf_graph_common_neighbors.
+ *   d_lengths tells it apart from the padding.
+ * - s == d is legal; both sides are then equal, and a == b.
+ * - Channel 0 is "in the source's sequence" on BOTH sides.
+ * - H == 0 does not exist: length >= 1 + self is required.
+ * One launch on `stream`: a row's two sequences are inserted into an open-addressing table in LDS
+ * (at most 2L keys in >= 4L slots; a probe that finds no place after as many trips as there are
+ * slots drops its element, which cannot happen at that load) with LDS atomics on integers, then
+ * every position of both sequences is written with its two counts, one writer per element, no
+ * atomics on global memory: the same inputs give the same bits.  The cost is the 2H records read
+ * twice per row.  d_counts must be 8-byte aligned (a position's two counts are one store).
+ * Ordering against gf_graph_add_edges / gf_graph_offload_old_blocks: as gf_batch_hist_negatives.
+ * A NULL graph, a NULL buffer other than d_since with num_rows > 0, length outside
+ * [1 + self, GF_COOC_MAX_LENGTH], a misaligned d_counts, num_rows >= 2^31:
+ * GF_ERR_INVALID_ARGUMENT, nothing launched.  num_rows == 0: GF_OK, nothing launched. */
+#define GF_COOC_MAX_LENGTH 512
+GF_API int gf_graph_neighbor_cooccurrence(const gf_graph* g, const int64_t* d_src,
+                                          const int64_t* d_dst, const float* d_ts,
+                                          const float* d_since /* NULL: no lower end */,
+                                          size_t num_rows, size_t length, int include_self,
+                                          int32_t* d_lengths, int64_t* d_nodes, int64_t* d_eids,
+                                          float* d_times, int32_t* d_counts, int device,
+                                          void* stream);
+
 /* Backward-in-time random walks over the temporal edge store: W = num_walks walks of L = length
  * steps from each of num_rows roots.  Walk (i, w) starts at v_0 = d_src[i], t_0 = d_ts[i];
  * d_nodes[i, w, 0] = d_src[i] always.  Step j = 0 .. L - 1:
