@@ -281,20 +281,31 @@ void EdgeStore::bump_eids(const int64_t* eids, size_t n) {
 void EdgeStore::scan_batch(IngestBatch& b) {
   const int64_t* src = b.src;
   const int64_t* dst = b.dst;
+  const float* ts = b.ts;
   std::mutex mu;
   bool negative = false;
+  size_t first_nan = b.n;
   parallel_for(b.n, 1 << 16, [&](size_t i0, size_t i1) {
     int64_t m = 0;
-    bool neg = false;
+    bool neg = false, nan = false;
     for (size_t i = i0; i < i1; ++i) {
       neg |= (src[i] < 0) | (dst[i] < 0);
+      nan |= ts[i] != ts[i];
       m = std::max(m, std::max(src[i], dst[i]));
     }
+    size_t at = i1;   // where: looked up only in a part that has one, off the loop above
+    if (nan)
+      for (at = i0; ts[at] == ts[at]; ++at) {}
     std::lock_guard<std::mutex> lk(mu);
     b.max_node = std::max(b.max_node, m);
     negative |= neg;
+    if (nan) first_nan = std::min(first_nan, at);
   });
   GF_REQUIRE(!negative, "add_edges: negative vertex id");
+  // no ordering has a place for a NaN: `<` is not an order over it, and every later search of
+  // the vertex's run assumes one
+  GF_REQUIRE(first_nan == b.n,
+             "add_edges: NaN timestamp at position " + std::to_string(first_nan));
 }
 
 // 1. order by (source, timestamp, input position): the reference groups by

@@ -25,12 +25,14 @@
 namespace gf {
 namespace {
 
+// Unsigned keys in the order of float `<` (NaN never gets here: add_edges rejects it).  -0.0 and
+// +0.0 are equal under `<`, so they share one key and the stable sort leaves them in input
+// order, as the host orderings do; the key therefore does not tell a zero's sign, and the sorted
+// timestamps are read back from the input through the permutation, never decoded from keys.
 __device__ inline uint32_t orderable(float f) {
   const uint32_t b = __float_as_uint(f);
+  if (b == 0x80000000u) return 0x80000000u;   // -0.0: the key of +0.0
   return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ inline float unorderable(uint32_t k) {
-  return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu));
 }
 
 __global__ void make_keys_kernel(const int64_t* __restrict__ src, const float* __restrict__ ts,
@@ -43,13 +45,16 @@ __global__ void make_keys_kernel(const int64_t* __restrict__ src, const float* _
   }
 }
 
-// sorted keys -> sorted timestamps + head flags (1 where a new source vertex starts)
-__global__ void split_keys_kernel(const uint64_t* __restrict__ keys, uint32_t n,
+// sorted keys + permutation -> sorted timestamps (each with the bits it came with) + head flags
+// (1 where a new source vertex starts)
+__global__ void split_keys_kernel(const uint64_t* __restrict__ keys,
+                                  const uint32_t* __restrict__ perm,
+                                  const float* __restrict__ ts, uint32_t n,
                                   float* __restrict__ sorted_ts, uint32_t* __restrict__ flag) {
   const uint32_t stride = gridDim.x * blockDim.x;
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     const uint64_t k = keys[i];
-    sorted_ts[i] = unorderable(static_cast<uint32_t>(k));
+    sorted_ts[i] = ts[perm[i]];   // perm is a permutation of [0, n)
     flag[i] = (i == 0 || (keys[i - 1] >> 32) != (k >> 32)) ? 1u : 0u;
   }
 }
@@ -183,7 +188,8 @@ size_t IngestSorter::order(const int64_t* h_src, const int64_t* h_dst, const flo
   uint32_t* flag = reinterpret_cast<uint32_t*>(b + o_flag_);
   uint32_t* gid = reinterpret_cast<uint32_t*>(b + o_gid_);
   split_keys_kernel<<<dim3(grid_for(n)), dim3(256), 0, stream>>>(
-      keys1, n32, reinterpret_cast<float*>(b + o_sorted_ts_), flag);
+      keys1, vals1, reinterpret_cast<const float*>(b + o_ts_), n32,
+      reinterpret_cast<float*>(b + o_sorted_ts_), flag);
   tmp = tmp_bytes_;
   GF_HIP(rocprim::inclusive_scan(b + o_tmp_, tmp, flag, gid, n, rocprim::plus<uint32_t>(), stream));
   group_table_kernel<<<dim3(grid_for(n)), dim3(256), 0, stream>>>(

@@ -293,7 +293,8 @@ class DynamicGraph:
         timestamp on ingest).  gnnflow/dynamic_graph.py:85-126.
 
         Raises:
-            ValueError: if the timestamps are older than the existing edges.
+            ValueError: if the timestamps are older than the existing edges, or one of them is
+                NaN (the message names its position).  The graph is unchanged either way.
         """
         source_vertices = np.asarray(source_vertices)
         target_vertices = np.asarray(target_vertices)
