@@ -6,13 +6,13 @@ kernels (gfx950) behind the C ABI of include/gnnflow_hip.h.
 """
 from .baselines import EdgeBank, NeighborOverlap
 from .data import DeviceBatchStream, DeviceDstSet
-from .dynamic_graph import (CommonNeighbors, DynamicGraph, NeighborCooccurrence, PairHistory,
-                            TemporalWalks)
+from .dynamic_graph import (CommonNeighbors, DynamicGraph, NeighborAggregate,
+                            NeighborCooccurrence, PairHistory, TemporalWalks)
 from .metrics import LinkMetrics
 from .mfg import MFGBlock
-from .nn import (MLP, EdgePredictor, GATConv, GRUMemeoryUpdater, GRUMemoryUpdater, LinkLoss,
-                 NeighborCooccurrenceEncoder, SAGEConv, TemporalAttentionLayer, TimeEncode,
-                 TransfomerAttentionLayer)
+from .nn import (MLP, EdgePredictor, FixedTimeEncode, GATConv, GRUMemeoryUpdater,
+                 GRUMemoryUpdater, LinkLoss, NeighborCooccurrenceEncoder, SAGEConv,
+                 TemporalAttentionLayer, TimeEncode, TransfomerAttentionLayer)
 from .temporal_sampler import SamplingResult, TemporalSampler
 
 __all__ = ["DynamicGraph", "TemporalSampler", "SamplingResult", "MFGBlock", "SAGEConv", "GATConv",
@@ -20,4 +20,4 @@ __all__ = ["DynamicGraph", "TemporalSampler", "SamplingResult", "MFGBlock", "SAG
            "GRUMemeoryUpdater", "EdgePredictor", "MLP", "LinkMetrics", "LinkLoss",
            "DeviceDstSet", "DeviceBatchStream", "TemporalWalks", "PairHistory", "EdgeBank",
            "CommonNeighbors", "NeighborOverlap", "NeighborCooccurrence",
-           "NeighborCooccurrenceEncoder"]
+           "NeighborCooccurrenceEncoder", "NeighborAggregate", "FixedTimeEncode"]

@@ -3,6 +3,7 @@
 #include "capi_handles.hpp"
 #include "common_neighbors.hpp"
 #include "hist_negatives.hpp"
+#include "neighbor_aggregate.hpp"
 #include "neighbor_cooccurrence.hpp"
 #include "pair_history.hpp"
 #include "seen_mask.hpp"
@@ -146,6 +147,20 @@ int gf_graph_neighbor_cooccurrence(const gf_graph* g, const int64_t* d_src, cons
     gf::neighbor_cooccurrence(g->impl.view(), d_src, d_dst, d_ts, d_since, num_rows, length,
                               include_self != 0, d_lengths, d_nodes, d_eids, d_times, d_counts,
                               device, as_stream(stream));
+  });
+}
+// reads the store's view NOW, as gf_batch_hist_negatives does
+int gf_graph_neighbor_aggregate(const gf_graph* g, const int64_t* d_nodes, const float* d_ts,
+                                const float* d_since, size_t num_rows, size_t max_history,
+                                const float* d_node_feats, size_t node_rows, size_t dn,
+                                const float* d_edge_feats, size_t edge_rows, size_t de, int mean,
+                                int64_t* d_count, float* d_node_out, float* d_edge_out,
+                                int device, void* stream) {
+  return guarded([&] {
+    GF_G(g);
+    gf::neighbor_aggregate(g->impl.view(), d_nodes, d_ts, d_since, num_rows, max_history,
+                           d_node_feats, node_rows, dn, d_edge_feats, edge_rows, de, mean != 0,
+                           d_count, d_node_out, d_edge_out, device, as_stream(stream));
   });
 }
 // reads the store's view NOW, as gf_batch_hist_negatives does

@@ -200,6 +200,62 @@ def check_neighbor_cooccurrence_args(src, dst, ts, since=None, length=32, includ
     return N, L, int(include_self)
 
 
+AGG_MAX_WIDTH = 1024      # GF_AGG_MAX_WIDTH
+
+
+class NeighborAggregate(NamedTuple):
+    """What DynamicGraph.neighbor_aggregate returns, one row per (node, ts) row."""
+    count: torch.Tensor              # int64 [N]; the considered edges of the node
+    node: Optional[torch.Tensor]     # float32 [N, dn]; their destinations' rows reduced, or None
+    edge: Optional[torch.Tensor]     # float32 [N, de]; their own rows reduced, or None
+
+
+def check_neighbor_aggregate_args(nodes, ts, node_feats=None, edge_feats=None, since=None,
+                                  max_history=0, reduce="mean"):
+    """Arguments of DynamicGraph.neighbor_aggregate, checked before anything is launched or
+    allocated: the kernel takes raw pointers and trusts them.  Needs no device.
+    Returns (N, dn, de), a width of 0 for a table that is not given."""
+    rows = [("nodes", nodes, torch.int64), ("ts", ts, torch.float32)]
+    tables = [(name, x, torch.float32) for name, x in (("node_feats", node_feats),
+                                                      ("edge_feats", edge_feats)) if x is not None]
+    for name, x, _ in tables:      # ahead of the shared message: it names what is supported
+        if isinstance(x, torch.Tensor) and x.dtype in (torch.float16, torch.bfloat16):
+            raise TypeError("{} must be float32, got {}: half-precision tables are not "
+                            "supported".format(name, x.dtype))
+    tensors = _typed_tensors(rows + tables, since)
+    _history_type(max_history)
+    if not isinstance(reduce, str):
+        raise TypeError("reduce must be a str, got {}".format(type(reduce).__name__))
+    # `since` follows the tables in `tensors`: the 1-D ones are the rows and, when given, since
+    vectors = [t for t in tensors if t[0] not in ("node_feats", "edge_feats")]
+    _one_dim(vectors)
+    N = int(nodes.shape[0])
+    for name, x, _ in vectors[1:]:
+        if int(x.shape[0]) != N:
+            raise ValueError("nodes has {} rows, {} has {}".format(N, name, int(x.shape[0])))
+    _below_2_31(N, "neighbor_aggregate", "rows")
+    if not tables:
+        raise ValueError("neighbor_aggregate needs node_feats or edge_feats")
+    width = {"node_feats": 0, "edge_feats": 0}
+    for name, x, _ in tables:
+        if x.dim() != 2:
+            raise ValueError("{} must be 2-D, got shape {}".format(name, tuple(x.shape)))
+        if int(x.shape[0]) == 0:      # no storage to point the kernel at
+            raise ValueError("{} has no rows".format(name))
+        if not 1 <= int(x.shape[1]) <= AGG_MAX_WIDTH:
+            raise ValueError("{} must have 1 to {} columns, got {}".format(
+                name, AGG_MAX_WIDTH, int(x.shape[1])))
+        if not x.is_contiguous():
+            raise ValueError("{} must be contiguous (a table is never copied); got strides "
+                             "{}".format(name, tuple(x.stride())))
+        width[name] = int(x.shape[1])
+    if reduce not in ("sum", "mean"):
+        raise ValueError("reduce must be 'sum' or 'mean', got {!r}".format(reduce))
+    _history_sign(max_history)
+    _same_device(tensors)
+    return N, width["node_feats"], width["edge_feats"]
+
+
 WALK_MAX_LENGTH = 32      # GF_WALK_MAX_LENGTH
 WALK_MAX_RECENCY = 8      # GF_WALK_MAX_RECENCY
 
@@ -652,6 +708,70 @@ class DynamicGraph:
                              N, L, self_slot, lengths.data_ptr(), nodes.data_ptr(),
                              eids.data_ptr(), times.data_ptr(), counts.data_ptr())
         return NeighborCooccurrence(lengths, nodes, eids, times, counts)
+
+    def neighbor_aggregate(self, nodes: torch.Tensor, ts: torch.Tensor, *,
+                           node_feats: Optional[torch.Tensor] = None,
+                           edge_feats: Optional[torch.Tensor] = None, since=None,
+                           max_history: int = 0, reduce: str = "mean") -> NeighborAggregate:
+        """The features of what each node met before the row's time, summed or averaged over
+        its history window: NeighborAggregate(count int64 [N], node float32 [N, dn] or None,
+        edge float32 [N, de] or None).  GraphMixer's node encoder input (models.GraphMixer:
+        node_x + the mean of the features of the nodes met) and windowed mean pooling.
+
+        The considered edges of row i are pair_history's: the live edges of nodes[i] in the store
+        whose timestamp is strictly below ts[i] (float <: a NaN time gives none) and, with
+        `since`, not below since[i] -- the lower end is inclusive, a NaN since[i] is no lower end
+        -- and, when max_history > 0, only the newest max_history of that window (the bound comes
+        after `since`).  count[i] is their number n.  node[i] reduces node_feats[dst] over their
+        destinations and edge[i] reduces edge_feats[eid] over their edge ids, in the store's
+        order, oldest first: reduce="sum" is the float32 sum in that order starting from +0.0,
+        reduce="mean" that sum divided once by float(n) (a correctly rounded division), zeros
+        where n == 0.  An id without a row in its table (negative, or at or past the table's
+        number of rows) contributes a zero row and still counts in n, the rule
+        Memory.prepare_input uses for unknown ids.  A node that is negative, past the node table
+        or without live edges gives count 0 and zero rows.  "Strictly before" and "live" as for
+        seen_mask: edges that offload_old_blocks took are gone, and on a graph built with reverse
+        edges the window also holds the edges that pointed at the node.  The exact rule is in
+        include/gnnflow_hip.h (gf_graph_neighbor_aggregate), the window in
+        csrc/history_window.hpp, and it is restated in numpy in tests/neighbor_aggregate_ref.py:
+        the result is that sequential loop's, bit for bit, and the same from run to run.
+
+        nodes: int64 [N], ts: float32 [N]; since: None, a float or a float32 tensor [N];
+        node_feats, edge_feats: float32 [rows, 1 .. 1024], at least one of them, contiguous (a
+        non-contiguous table is a ValueError, not a silent copy of what may be gigabytes); all
+        tensors on the graph's device.  The tables are detached: no gradient flows to them, and
+        the outputs do not require grad.  The output of a table that is not given is None.
+        N == 0 returns empty tensors of these shapes without a launch.
+
+        One kernel (csrc/neighbor_aggregate.hip: a wave per row, the lanes own columns, no
+        [N, H, d] intermediate) on the current stream, memory from torch, never synchronises.
+        Edges added to the graph are seen by calls made after add_edges returns; add_edges and
+        offload_old_blocks move and free segments: synchronise the streams that calls were
+        launched on before calling either, as for seen_mask.
+
+        The cost is proportional to the edges considered: a row's window is walked by one wave,
+        which reads one table row per considered edge, so a hub with 10^6 earlier edges is 10^6
+        row reads for each of its rows.  max_history and since are what bound it."""
+        N, dn, de = check_neighbor_aggregate_args(nodes, ts, node_feats, edge_feats, since,
+                                                  max_history, reduce)
+        dev = nodes.device
+        self._check_on_device(dev)
+        with torch.cuda.device(self._device):
+            count = torch.empty(N, dtype=torch.int64, device=dev)
+            node = torch.empty((N, dn), dtype=torch.float32, device=dev) if dn else None
+            edge = torch.empty((N, de), dtype=torch.float32, device=dev) if de else None
+            if N:
+                v, t = nodes.detach().contiguous(), ts.detach().contiguous()
+                lo = self._since_tensor(since, (N,), dev)
+                nf = node_feats.detach() if dn else None
+                ef = edge_feats.detach() if de else None
+                self._launch(self._lib.gf_graph_neighbor_aggregate, v.data_ptr(), t.data_ptr(),
+                             None if lo is None else lo.data_ptr(), N, max_history,
+                             nf.data_ptr() if dn else None, nf.shape[0] if dn else 0, dn,
+                             ef.data_ptr() if de else None, ef.shape[0] if de else 0, de,
+                             1 if reduce == "mean" else 0, count.data_ptr(),
+                             node.data_ptr() if dn else None, edge.data_ptr() if de else None)
+        return NeighborAggregate(count, node, edge)
 
     def temporal_random_walk(self, src: torch.Tensor, ts: torch.Tensor, length: int,
                              num_walks: int = 1, *, recency: int = 1, max_history: int = 0,

@@ -293,6 +293,29 @@ class TimeEncode(nn.Module):
         return torch.cos(self.w(delta_time.reshape(-1, 1)))
 
 
+class FixedTimeEncode(nn.Module):
+    """GraphMixer's frozen time encoding cos(dt * w), w_i = 10^(-9 i / (dim - 1)) (w = 1 for
+    dim == 1): TimeEncode's initial frequencies, never trained.  `weight` [dim, 1] and the zero
+    `bias` [dim] are buffers, so the module has no parameters and they follow .to() and the
+    state dict.  forward(dt of any shape) -> dt.shape + (dim,); float32 input on the GPU takes
+    ops.time_encode (one kernel), anything else the torch expression."""
+
+    def __init__(self, dim: int):
+        super().__init__()
+        freq = 1 / 10 ** np.linspace(0, 9, dim, dtype=np.float32)
+        self.dim = int(dim)
+        self.register_buffer("weight", torch.from_numpy(freq).reshape(dim, 1))
+        self.register_buffer("bias", torch.zeros(dim))
+
+    def forward(self, delta_time: torch.Tensor) -> torch.Tensor:
+        flat = delta_time.reshape(-1)
+        if flat.is_cuda and flat.dtype == torch.float32 and self.weight.dtype == torch.float32:
+            out = ops.time_encode(flat, self.weight, self.bias)
+        else:
+            out = torch.cos(flat.unsqueeze(1) * self.weight.reshape(1, -1) + self.bias)
+        return out.reshape(tuple(delta_time.shape) + (self.dim,))
+
+
 class _GatherCountPair(torch.autograd.Function):
     """out[r] = tab[i0[r]] + tab[i1[r]] where filled[r], else 0.  The table's gradient is a sum
     of all rows into a handful: it is accumulated in float64 and rounded once, so that it neither

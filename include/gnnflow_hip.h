@@ -1559,6 +1559,57 @@ GF_API int gf_graph_neighbor_cooccurrence(const gf_graph* g, const int64_t* d_sr
                                           float* d_times, int32_t* d_counts, int device,
                                           void* stream);
 
+/* The features of what each of num_rows nodes met before the row's time, summed or averaged over
+ * its history window: GraphMixer's node encoder input and windowed mean pooling.  Row i has node
+ * v = d_nodes[i], time t = d_ts[i] and, when d_since is not NULL, lower end lo = d_since[i].  Its
+ * considered records are the window of v at (t, lo, max_history) exactly as defined for
+ * gf_graph_pair_history:
+ * - e = table[v]; c = the number of x in ts_pool[e.start .. e.start + e.size) with x < t, strict
+ *   and with the float < operator (a NaN t gives c = 0), over the live range only;
+ * - c0 = 0, or with d_since min(c, the number of x with x < lo), the same operator: a NaN lo
+ *   gives c0 = 0, and the lower end is inclusive;
+ * - n = c - c0, or min(c - c0, max_history) when max_history > 0: the NEWEST n edges of the
+ *   window, seg = nbr_pool[e.start + c - n .. e.start + c), oldest first;
+ * - v < 0, v >= table_len, no live edge or a store without a node: n = 0.
+ * With N = d_node_feats (float32 [node_rows, dn], row-major and contiguous), E = d_edge_feats
+ * (float32 [edge_rows, de]) and N[id, :], E[id, :] the ZERO row for an id without a row in its
+ * table (id < 0 or id >= node_rows / edge_rows):
+ *   d_count[i]       = n                                                          int64 [num_rows]
+ *   d_node_out[i, c] = (((+0.0f + N[seg[0].dst, c]) + N[seg[1].dst, c]) + ...) + N[seg[n-1].dst, c]
+ *                                                                           float32 [num_rows, dn]
+ *   d_edge_out[i, c] = the same over E[seg[x].eid, c]                       float32 [num_rows, de]
+ * in float32, one addition per record in window order.  With mean != 0 that sum is then divided
+ * once by (float)n with a correctly rounded IEEE division, not multiplied by a reciprocal; where
+ * n == 0 the result is zeros.  A record without a row adds nothing and still counts in n (the
+ * rule of unknown ids in the TGN memory's input).  Either table may be absent, as NULL with width
+ * 0 (its output is then not touched and may be NULL), but not both.  Widths are
+ * 1 .. GF_AGG_MAX_WIDTH.  Every element of d_count and of the outputs of the given tables is
+ * written, the rows with an empty window too: they need no initialisation.  On a graph built
+ * with reverse edges the window includes the edges that pointed at v.
+ * One launch on `stream`: a wave per row, the lanes own columns (float4 columns when the width is
+ * a multiple of 4 and the table and its output are 16-byte aligned), every output element is
+ * written by one lane whose additions run in window order, plain loads and stores, no LDS, no
+ * atomics: the same inputs give the same bits, and they are the bits of a sequential float32
+ * loop.  The cost is the rows read (a hub's whole history when max_history == 0 and d_since ==
+ * NULL, walked by one wave); max_history > 2^32 - 1 is no bound.  Ordering against
+ * gf_graph_add_edges / gf_graph_offload_old_blocks: as gf_batch_hist_negatives (reads the store's
+ * view NOW).
+ * A NULL graph, no table at all, a NULL table with a width other than 0, a width outside
+ * [1, GF_AGG_MAX_WIDTH] of a table that is given, num_rows >= 2^31, and with num_rows > 0 a NULL
+ * d_nodes, d_ts, d_count or output of a given table: GF_ERR_INVALID_ARGUMENT, nothing launched.
+ * num_rows == 0: GF_OK, nothing launched. */
+#define GF_AGG_MAX_WIDTH 1024
+GF_API int gf_graph_neighbor_aggregate(const gf_graph* g, const int64_t* d_nodes,
+                                       const float* d_ts,
+                                       const float* d_since /* NULL: no lower end */,
+                                       size_t num_rows, size_t max_history,
+                                       const float* d_node_feats /* NULL: no node table */,
+                                       size_t node_rows, size_t dn,
+                                       const float* d_edge_feats /* NULL: no edge table */,
+                                       size_t edge_rows, size_t de, int mean, int64_t* d_count,
+                                       float* d_node_out, float* d_edge_out, int device,
+                                       void* stream);
+
 /* Backward-in-time random walks over the temporal edge store: W = num_walks walks of L = length
  * steps from each of num_rows roots.  Walk (i, w) starts at v_0 = d_src[i], t_0 = d_ts[i];
  * d_nodes[i, w, 0] = d_src[i] always.  Step j = 0 .. L - 1:
