@@ -5,11 +5,9 @@ The whole stream is ingested into the graph once.  Per batch the roots are [src 
 random destination per edge as the negative), all at the edge's time, and for every root
 
 - the link encoder's tokens are its newest `--tokens` interactions STRICTLY BEFORE t:
-  `graph.neighbor_cooccurrence(roots, roots, ts, length=K, include_self=False)`, side 0, gives
-  their edge ids and times, the edge features are indexed with the ids, and the padded slots are
-  zeroed inside the model by `lengths`.  The reader is a pair reader: with the root on both sides
-  it reads each window twice and hashes it for counts that are not used here; a per-node sequence
-  reader does not exist yet;
+  `graph.neighbor_sequence(roots, ts, length=K, edge_feats=..., time_encoder=model.time_enc)`
+  returns them finished, [edge features | time encoding of t minus the edge's time] with the
+  padded slots zero, from one kernel, and `model.forward_tokens` takes them as they are;
 - the node encoder's `nbr_mean` is `graph.neighbor_aggregate(roots, ts, node_feats=...,
   max_history=H).node`: the mean of the features of the nodes met over the newest `--history`
   edges, one kernel, no [N, H, d] intermediate.
@@ -65,13 +63,13 @@ def main(num_batches=5, batch_size=200, num_tokens=32, max_history=64, dim=16, n
         neg = dsts[torch.randint(0, len(dsts), (len(src),), device=dev)]
         roots, ts = torch.cat([src, dst, neg]), t.repeat(3)
 
-        seq = graph.neighbor_cooccurrence(roots, roots, ts, length=K, include_self=False)
-        lengths, eids, times = seq.lengths[:, 0], seq.eids[:, 0], seq.times[:, 0]
-        edge_x = edge_feats[eids.clamp(min=0)]                    # the -1 slots: zeroed by lengths
-        delta_t = ts[:, None] - times
+        seq = graph.neighbor_sequence(roots, ts, length=K, edge_feats=edge_feats,
+                                      time_encoder=model.time_enc)
+        lengths, delta_t = seq.lengths, seq.delta_t
+        edge_x = seq.tokens[..., :dim]                            # a view: the tokens' edge part
         agg = graph.neighbor_aggregate(roots, ts, node_feats=node_feats, max_history=max_history)
 
-        pred_pos, pred_neg = model(edge_x, delta_t, lengths, node_feats[roots], agg.node)
+        pred_pos, pred_neg = model.forward_tokens(seq.tokens, node_feats[roots], agg.node)
         loss = criterion(pred_pos, pred_neg)
         optimizer.zero_grad()
         loss.backward()

@@ -7,7 +7,8 @@ kernels (gfx950) behind the C ABI of include/gnnflow_hip.h.
 from .baselines import EdgeBank, NeighborOverlap
 from .data import DeviceBatchStream, DeviceDstSet
 from .dynamic_graph import (CommonNeighbors, DynamicGraph, NeighborAggregate,
-                            NeighborCooccurrence, PairHistory, TemporalWalks)
+                            NeighborCooccurrence, NeighborSequence, PairHistory,
+                            TemporalWalks)
 from .metrics import LinkMetrics
 from .mfg import MFGBlock
 from .nn import (MLP, EdgePredictor, FixedTimeEncode, GATConv, GRUMemeoryUpdater,
@@ -20,4 +21,5 @@ __all__ = ["DynamicGraph", "TemporalSampler", "SamplingResult", "MFGBlock", "SAG
            "GRUMemeoryUpdater", "EdgePredictor", "MLP", "LinkMetrics", "LinkLoss",
            "DeviceDstSet", "DeviceBatchStream", "TemporalWalks", "PairHistory", "EdgeBank",
            "CommonNeighbors", "NeighborOverlap", "NeighborCooccurrence",
-           "NeighborCooccurrenceEncoder", "NeighborAggregate", "FixedTimeEncode"]
+           "NeighborCooccurrenceEncoder", "NeighborAggregate", "FixedTimeEncode",
+           "NeighborSequence"]

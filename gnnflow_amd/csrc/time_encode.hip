@@ -20,9 +20,10 @@
 //   gw[j]    = - sum_i g[i,j] * sinf(w[j]*t[i] + bias[j]) * t[i]
 //   gbias[j] = - sum_i g[i,j] * sinf(w[j]*t[i] + bias[j])
 //
-// with g read in place from grad_out through a row pitch and a column offset.  te_arg() is the
-// only place the argument is computed, forward and backward (the library is built with
-// -ffp-contract=off and without fast-math: one multiply, one add).  Workgroup p owns the rows
+// with g read in place from grad_out through a row pitch and a column offset.  te_arg()
+// (time_encode_expr.hpp, shared with neighbor_sequence.hip) is the only place the argument is
+// computed, forward and backward (the library is built with -ffp-contract=off and without
+// fast-math: one multiply, one add), and te_cos() there the only cosine of it.  Workgroup p owns the rows
 // [p * rows_per_wg, (p + 1) * rows_per_wg); lanes sit over the columns j (CX of them, RY = 256 / CX
 // row phases), each lane accumulates its rows in registers in ascending order, the RY phases
 // are summed in ascending order through LDS, and the workgroup writes one row [2, T] of
@@ -44,6 +45,7 @@
 #include "bf16.hpp"
 #include "block_ops.hpp"
 #include "common.hpp"
+#include "time_encode_expr.hpp"
 
 #include <cstdint>
 
@@ -53,8 +55,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kFinishThreads = 1024;   // 32 columns x 32 row phases
 constexpr size_t kMinRowsPerGroup = 16;
-
-__device__ __forceinline__ float te_arg(float w, float t, float b) { return w * t + b; }
 
 template <int V> struct Chunk;
 template <> struct Chunk<1> {
@@ -102,7 +102,7 @@ time_encode_cat_fwd(const float* __restrict__ a, uint32_t qa, const float* __res
     const Chunk<V> wj = Chunk<V>::load(w + j), bj = Chunk<V>::load(bias + j);
     const float ti = t[row];
 #pragma unroll
-    for (int e = 0; e < V; ++e) x.v[e] = cosf(te_arg(wj.v[e], ti, bj.v[e]));
+    for (int e = 0; e < V; ++e) x.v[e] = te_cos(wj.v[e], ti, bj.v[e]);
   }
   x.store(out + static_cast<uint64_t>(k) * V);
 }

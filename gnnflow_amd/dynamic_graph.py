@@ -256,6 +256,93 @@ def check_neighbor_aggregate_args(nodes, ts, node_feats=None, edge_feats=None, s
     return N, width["node_feats"], width["edge_feats"]
 
 
+SEQ_MAX_LENGTH = 512      # GF_SEQ_MAX_LENGTH
+SEQ_MAX_WIDTH = 1024      # GF_SEQ_MAX_WIDTH
+
+
+class NeighborSequence(NamedTuple):
+    """What DynamicGraph.neighbor_sequence returns, one row per (node, ts) row; L = length slots,
+    oldest first, the slots p >= lengths[i] are padding."""
+    lengths: torch.Tensor            # int32 [N]; filled slots
+    nodes: torch.Tensor              # int64 [N, L]; the edges' destinations, then -1
+    eids: torch.Tensor               # int64 [N, L]; the edges' ids, then -1
+    times: torch.Tensor              # float32 [N, L]; the edges' times, then 0
+    delta_t: torch.Tensor            # float32 [N, L]; ts[i] - times[i, p], then 0
+    tokens: Optional[torch.Tensor]   # float32 [N, L, de + dn + dT], zeros in the padding, or None
+
+
+def _encoder_tensors(time_encoder):
+    """(weight, bias) of a time encoder: a (weight, bias) pair, or a module that holds them as
+    `weight` and `bias` (nn.FixedTimeEncode) or as those of its Linear `w` (nn.TimeEncode)."""
+    if isinstance(time_encoder, (tuple, list)):
+        if len(time_encoder) != 2:
+            raise TypeError("time_encoder must be a module or a (weight, bias) pair, got {} "
+                            "elements".format(len(time_encoder)))
+        return time_encoder[0], time_encoder[1]
+    for holder in (time_encoder, getattr(time_encoder, "w", None)):
+        if hasattr(holder, "weight") and hasattr(holder, "bias"):
+            return holder.weight, holder.bias
+    raise TypeError("time_encoder must be a module with weight and bias or a (weight, bias) pair, "
+                    "got {}".format(type(time_encoder).__name__))
+
+
+def check_neighbor_sequence_args(nodes, ts, since=None, length=32, edge_feats=None,
+                                 node_feats=None, time_encoder=None):
+    """Arguments of DynamicGraph.neighbor_sequence, checked before anything is launched or
+    allocated: the kernel takes raw pointers and trusts them.  Needs no device.
+    Returns (N, L, de, dn, dT), a width of 0 for a part that is not given."""
+    rows = [("nodes", nodes, torch.int64), ("ts", ts, torch.float32)]
+    tables = [(name, x, torch.float32) for name, x in (("edge_feats", edge_feats),
+                                                      ("node_feats", node_feats)) if x is not None]
+    for name, x, _ in tables:      # ahead of the shared message: it names what is supported
+        if isinstance(x, torch.Tensor) and x.dtype in (torch.float16, torch.bfloat16):
+            raise TypeError("{} must be float32, got {}: half-precision tables are not "
+                            "supported".format(name, x.dtype))
+    encoder = []
+    if time_encoder is not None:
+        weight, bias = _encoder_tensors(time_encoder)
+        encoder = [("time_encoder's weight", weight, torch.float32),
+                   ("time_encoder's bias", bias, torch.float32)]
+    tensors = _typed_tensors(rows + tables + encoder, since)
+    L = _int_arg(length, "length", 1, SEQ_MAX_LENGTH + 1)
+    # `since` follows the parts in `tensors`: the 1-D ones are the rows and, when given, since
+    vectors = [t for t in tensors if t[0] in ("nodes", "ts", "since")]
+    _one_dim(vectors)
+    N = int(nodes.shape[0])
+    for name, x, _ in vectors[1:]:
+        if int(x.shape[0]) != N:
+            raise ValueError("nodes has {} rows, {} has {}".format(N, name, int(x.shape[0])))
+    _below_2_31(N, "neighbor_sequence", "rows")
+    width = {"edge_feats": 0, "node_feats": 0}
+    for name, x, _ in tables:
+        if x.dim() != 2:
+            raise ValueError("{} must be 2-D, got shape {}".format(name, tuple(x.shape)))
+        if int(x.shape[0]) == 0:      # no storage to point the kernel at
+            raise ValueError("{} has no rows".format(name))
+        if not 1 <= int(x.shape[1]) <= SEQ_MAX_WIDTH:
+            raise ValueError("{} must have 1 to {} columns, got {}".format(
+                name, SEQ_MAX_WIDTH, int(x.shape[1])))
+        if not x.is_contiguous():
+            raise ValueError("{} must be contiguous (a table is never copied); got strides "
+                             "{}".format(name, tuple(x.stride())))
+        width[name] = int(x.shape[1])
+    dT = 0
+    if encoder:
+        weight, bias = encoder[0][1], encoder[1][1]
+        if bias.dim() != 1:
+            raise ValueError("time_encoder's bias must be [dT], got shape {}".format(
+                tuple(bias.shape)))
+        dT = int(bias.shape[0])
+        if not 1 <= dT <= SEQ_MAX_WIDTH:
+            raise ValueError("time_encoder must have 1 to {} columns, got {}".format(
+                SEQ_MAX_WIDTH, dT))
+        if tuple(weight.shape) not in ((dT, 1), (dT,)):
+            raise ValueError("time_encoder's weight must be [dT, 1] or [dT] with dT = {}, got "
+                             "shape {}".format(dT, tuple(weight.shape)))
+    _same_device(tensors)
+    return N, L, width["edge_feats"], width["node_feats"], dT
+
+
 WALK_MAX_LENGTH = 32      # GF_WALK_MAX_LENGTH
 WALK_MAX_RECENCY = 8      # GF_WALK_MAX_RECENCY
 
@@ -772,6 +859,88 @@ class DynamicGraph:
                              1 if reduce == "mean" else 0, count.data_ptr(),
                              node.data_ptr() if dn else None, edge.data_ptr() if de else None)
         return NeighborAggregate(count, node, edge)
+
+    def neighbor_sequence(self, nodes: torch.Tensor, ts: torch.Tensor, *, since=None,
+                          length: int = 32, edge_feats: Optional[torch.Tensor] = None,
+                          node_feats: Optional[torch.Tensor] = None,
+                          time_encoder=None) -> NeighborSequence:
+        """Each node's newest interactions before the row's time as one padded sequence, and
+        optionally the finished tokens of a sequence model: NeighborSequence(lengths int32 [N];
+        nodes, eids int64 [N, L]; times, delta_t float32 [N, L]; tokens float32
+        [N, L, de + dn + dT] or None), L = length.  The per-node reader of GraphMixer's link
+        encoder (models.GraphMixer.forward_tokens) and of DyGFormer- or TCL-style models, where
+        neighbor_cooccurrence reads the two ends of a pair.
+
+        The window of row i is pair_history's: the live edges of nodes[i] in the store whose
+        timestamp is strictly below ts[i] (float <: a NaN time gives none) and, with `since`, not
+        below since[i] -- the lower end is inclusive, a NaN since[i] is no lower end -- and of
+        those the newest `length`, oldest first.  lengths[i] = n is their number.
+
+        - For p < n: nodes[i, p], eids[i, p] and times[i, p] are the edge's destination, id and
+          timestamp (bits copied), delta_t[i, p] = ts[i] - times[i, p], one float32 subtraction.
+        - For p >= n, the padding: -1, -1, 0, 0 -- neighbor_cooccurrence's convention, whose
+          side 0 with include_self=False the first four outputs equal element for element.
+        - tokens[i, p] = [edge_feats[eid] | node_feats[dst] | cos(w * delta_t[i, p] + b)] for
+          p < n.  The table parts are copies of the rows, bit for bit; an id without a row in
+          its table (negative, or at or past its number of rows) gives a zero part,
+          neighbor_aggregate's rule.  The time part is ops.time_encode's expression evaluated by
+          the same code: it equals ops.time_encode(delta_t.reshape(-1), weight, bias) bit for
+          bit.  Every element of a padded slot is +0.0, the time part too: what
+          masked_fill(padding, 0.0) leaves.  tokens is None when no part is given.
+
+        A node that is negative, past the node table or without live edges gives an all-padding
+        row.  "Strictly before" and "live" as for seen_mask: edges that offload_old_blocks took
+        are gone, and on a graph built with reverse edges the window also holds the edges that
+        pointed at the node.  The exact rule is in include/gnnflow_hip.h
+        (gf_graph_neighbor_sequence), the window in csrc/history_window.hpp, and it is restated
+        in numpy in tests/neighbor_sequence_ref.py.
+
+        nodes: int64 [N], ts: float32 [N]; since: None, a float or a float32 tensor [N];
+        1 <= length <= 512; edge_feats, node_feats: float32 [rows, 1 .. 1024], contiguous (a
+        non-contiguous table is a ValueError, not a silent copy of what may be gigabytes; a
+        float16 or bfloat16 table is a TypeError); time_encoder: a module that holds `weight`
+        [dT, 1] and `bias` [dT] (nn.FixedTimeEncode, nn.TimeEncode) or a (weight, bias) pair,
+        float32, 1 <= dT <= 1024; all tensors on the graph's device.  The tables and the
+        encoder are read detached: no gradient flows to them or to ts, and the outputs do not
+        require grad.  N == 0 returns empty tensors of these shapes without a launch.
+
+        One kernel (csrc/neighbor_sequence.hip: a wave per row, the lanes spread over the
+        row's positions and over the flattened (position, column) space of its tokens; the same
+        inputs give the same bits) on the current stream, memory from torch, never
+        synchronises.  Synchronise the streams that calls were launched on before add_edges or
+        offload_old_blocks, as for seen_mask.  The cost is the `length` records and table rows
+        read per row and the length * (24 + 4 * width) bytes written."""
+        N, L, de, dn, dT = check_neighbor_sequence_args(nodes, ts, since, length, edge_feats,
+                                                        node_feats, time_encoder)
+        dev = nodes.device
+        self._check_on_device(dev)
+        width = de + dn + dT
+        with torch.cuda.device(self._device):
+            lengths = torch.empty(N, dtype=torch.int32, device=dev)
+            out_nodes = torch.empty((N, L), dtype=torch.int64, device=dev)
+            eids = torch.empty((N, L), dtype=torch.int64, device=dev)
+            times = torch.empty((N, L), dtype=torch.float32, device=dev)
+            delta_t = torch.empty((N, L), dtype=torch.float32, device=dev)
+            tokens = torch.empty((N, L, width), dtype=torch.float32,
+                                 device=dev) if width else None
+            if N:
+                v, t = nodes.detach().contiguous(), ts.detach().contiguous()
+                lo = self._since_tensor(since, (N,), dev)
+                ef = edge_feats.detach() if de else None
+                nf = node_feats.detach() if dn else None
+                w = b = None
+                if dT:
+                    w, b = (x.detach().reshape(dT).contiguous()
+                            for x in _encoder_tensors(time_encoder))
+                self._launch(self._lib.gf_graph_neighbor_sequence, v.data_ptr(), t.data_ptr(),
+                             None if lo is None else lo.data_ptr(), N, L,
+                             ef.data_ptr() if de else None, ef.shape[0] if de else 0, de,
+                             nf.data_ptr() if dn else None, nf.shape[0] if dn else 0, dn,
+                             w.data_ptr() if dT else None, b.data_ptr() if dT else None, dT,
+                             lengths.data_ptr(), out_nodes.data_ptr(), eids.data_ptr(),
+                             times.data_ptr(), delta_t.data_ptr(),
+                             tokens.data_ptr() if width else None)
+        return NeighborSequence(lengths, out_nodes, eids, times, delta_t, tokens)
 
     def temporal_random_walk(self, src: torch.Tensor, ts: torch.Tensor, length: int,
                              num_walks: int = 1, *, recency: int = 1, max_history: int = 0,

@@ -1,8 +1,10 @@
 """GraphMixer (Cong et al., "Do We Really Need Complicated Model Architectures For Temporal
 Networks?", ICLR 2023) per node, on the readers of DynamicGraph: the link encoder is an MLP-Mixer
-over a node's newest K interactions (DynamicGraph.neighbor_cooccurrence's sequences), the node
-encoder is the node's own features plus the mean of the features of the nodes it met
-(DynamicGraph.neighbor_aggregate).  Plain torch modules; the GEMMs are torch's."""
+over a node's newest K interactions, the node encoder is the node's own features plus the mean of
+the features of the nodes it met (DynamicGraph.neighbor_aggregate).  The link encoder's tokens
+come finished from DynamicGraph.neighbor_sequence(..., edge_feats=, time_encoder=model.time_enc)
+-- one kernel, padding already zero -- into forward_tokens; forward builds the same tokens in
+torch from edge features, time deltas and lengths.  Plain torch modules; the GEMMs are torch's."""
 from typing import Optional
 
 import torch
@@ -97,7 +99,26 @@ class GraphMixer(nn.Module):
             parts.insert(0, edge_x)
         tokens = torch.cat(parts, dim=2)
         padding = torch.arange(K, device=delta_t.device) >= lengths.reshape(n, 1)
-        x = self.link_in(tokens.masked_fill(padding.unsqueeze(2), 0.0))
+        return self.forward_tokens(tokens.masked_fill(padding.unsqueeze(2), 0.0), node_x,
+                                   nbr_mean, return_embed)
+
+    def forward_tokens(self, tokens: torch.Tensor, node_x: Optional[torch.Tensor] = None,
+                       nbr_mean: Optional[torch.Tensor] = None, return_embed: bool = False):
+        """
+        forward() from finished tokens, whose padded slots are already zero.
+
+        Args:
+            tokens: float [n, K, dim_edge + dim_time], [edge_x | time_enc(delta_t)] with zeros in
+                the padding: DynamicGraph.neighbor_sequence(nodes, ts, length=K,
+                edge_feats=..., time_encoder=self.time_enc).tokens (without edge_feats when
+                dim_edge == 0)
+            node_x, nbr_mean, return_embed: as in forward()
+        """
+        if tokens.dim() != 3 or tokens.shape[1] != self.num_tokens or \
+                tokens.shape[2] != self.dim_edge + self.dim_time:
+            raise ValueError("tokens must be [n, {}, {}], got {}".format(
+                self.num_tokens, self.dim_edge + self.dim_time, tuple(tokens.shape)))
+        x = self.link_in(tokens)
         for mixer in self.mixers:
             x = mixer(x)
         h = x.mean(dim=1)

@@ -1610,6 +1610,60 @@ GF_API int gf_graph_neighbor_aggregate(const gf_graph* g, const int64_t* d_nodes
                                        float* d_node_out, float* d_edge_out, int device,
                                        void* stream);
 
+/* The newest interactions of each of num_rows nodes as one padded sequence, and optionally the
+ * finished tokens a sequence model reads from it (GraphMixer's link encoder, DyGFormer, TCL): the
+ * per-node reader, where gf_graph_neighbor_cooccurrence reads the two ends of a pair.  Row i has
+ * node v = d_nodes[i], time t = d_ts[i] and, when d_since is not NULL, lower end lo = d_since[i].
+ * With L = length, its records are the window of v at (t, lo, L) exactly as defined for
+ * gf_graph_neighbor_aggregate with max_history = L (strictly before t, lo inclusive, the newest L,
+ * a NaN t gives none, a NaN lo is no lower end; empty for v < 0, v >= table_len, no live edge or
+ * a store without a node): seg[0 .. n), oldest first, n <= L.  All outputs are row-major and
+ * contiguous, and every element is written, so they need no initialisation:
+ *   d_lengths   int32   [num_rows]        n
+ *   d_out_nodes int64   [num_rows, L]     seg[p].dst for p < n, then -1
+ *   d_eids      int64   [num_rows, L]     seg[p].eid for p < n, then -1
+ *   d_times     float32 [num_rows, L]     seg[p].ts for p < n, bits copied, then 0
+ *   d_delta_t   float32 [num_rows, L]     t - seg[p].ts for p < n, one float32 subtraction, then 0
+ *   d_tokens    float32 [num_rows, L, de + dn + dim_time], for p < n
+ *                 [0, de)            d_edge_feats[seg[p].eid, :]   (float32 [edge_rows, de])
+ *                 [de, de + dn)      d_node_feats[seg[p].dst, :]   (float32 [node_rows, dn])
+ *                 de + dn + j        cosf(d_weight[j] * d_delta_t[i, p] + d_bias[j]), j < dim_time
+ *               and +0.0 in every element, the time part too, for p >= n
+ * which is gf_graph_neighbor_cooccurrence's side 0 with include_self == 0, element for element,
+ * in the first four.  The table parts are copies of the rows, bit for bit; an id without a row in
+ * its table (id < 0 or id >= edge_rows / node_rows) gives a zero part, the rule of
+ * gf_graph_neighbor_aggregate.  The time part is gf_time_encode_cat's expression evaluated by the
+ * same code (one multiply, one add, the precise cosf): it equals that call on d_delta_t bit for
+ * bit.  Each of the three parts may be absent, as NULL with width 0 (d_weight and d_bias are
+ * given together); without any part d_tokens is not touched and may be NULL.  Tables are
+ * row-major and contiguous; widths are 1 .. GF_SEQ_MAX_WIDTH, length is 1 .. GF_SEQ_MAX_LENGTH.
+ * On a graph built with reverse edges the window includes the edges that pointed at v.
+ * One launch on `stream`: a wave per row; the lanes stride over the L positions for the four
+ * planes (one 32-byte record read per filled position) and over the flattened (position, column)
+ * space of each part for the tokens (float4 columns when every given width is a multiple of 4 and
+ * the tables and d_tokens are 16-byte aligned, scalar columns otherwise), one writer per element,
+ * plain loads and stores, no LDS, no atomics: the same inputs give the same bits.  Index
+ * arithmetic on [num_rows, L, width] is 64-bit.  Ordering against gf_graph_add_edges /
+ * gf_graph_offload_old_blocks: as gf_batch_hist_negatives (reads the store's view NOW).
+ * A NULL graph, length outside [1, GF_SEQ_MAX_LENGTH], a NULL part with a width other than 0, a
+ * width outside [1, GF_SEQ_MAX_WIDTH] of a part that is given, only one of d_weight and d_bias,
+ * num_rows >= 2^31, and with num_rows > 0 a NULL d_nodes, d_ts, d_lengths, d_out_nodes, d_eids,
+ * d_times or d_delta_t, or a NULL d_tokens when a part is given: GF_ERR_INVALID_ARGUMENT, nothing
+ * launched.  num_rows == 0: GF_OK, nothing launched. */
+#define GF_SEQ_MAX_LENGTH 512
+#define GF_SEQ_MAX_WIDTH 1024
+GF_API int gf_graph_neighbor_sequence(const gf_graph* g, const int64_t* d_nodes, const float* d_ts,
+                                      const float* d_since /* NULL: no lower end */,
+                                      size_t num_rows, size_t length,
+                                      const float* d_edge_feats /* NULL: no edge table */,
+                                      size_t edge_rows, size_t de,
+                                      const float* d_node_feats /* NULL: no node table */,
+                                      size_t node_rows, size_t dn,
+                                      const float* d_weight /* NULL: no time part */,
+                                      const float* d_bias, size_t dim_time, int32_t* d_lengths,
+                                      int64_t* d_out_nodes, int64_t* d_eids, float* d_times,
+                                      float* d_delta_t, float* d_tokens, int device, void* stream);
+
 /* Backward-in-time random walks over the temporal edge store: W = num_walks walks of L = length
  * steps from each of num_rows roots.  Walk (i, w) starts at v_0 = d_src[i], t_0 = d_ts[i];
  * d_nodes[i, w, 0] = d_src[i] always.  Step j = 0 .. L - 1:
