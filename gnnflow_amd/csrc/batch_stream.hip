@@ -58,10 +58,6 @@ struct AssembleArgs {
   uint64_t capacity;         // elements roots (and ts) can hold
 };
 
-__device__ __forceinline__ bool aligned16(const void* p) {
-  return (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
-}
-
 template <bool kNegOnly>
 __global__ void __launch_bounds__(kThreads) batch_assemble_kernel(const AssembleArgs a) {
   const uint64_t planes = (kNegOnly ? 0u : 2u) + a.K;

@@ -60,6 +60,11 @@ int guarded(Fn&& fn) noexcept {
   }
 }
 
+// may p be read and written 16 bytes at a time (a float4, two int64): host code and kernels
+__host__ __device__ inline bool aligned16(const void* p) {
+  return (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
+}
+
 // Grow-only device allocation.  grow(n, keep, stream) reallocates to >= n bytes
 // (geometric) and, if keep > 0, copies the first `keep` bytes device-to-device.
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }

@@ -348,8 +348,6 @@ edge_rank_merge(const uint32_t* __restrict__ counts, const uint64_t* __restrict_
   }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 size_t num_chunks(size_t num_cand) { return (num_cand + kEdgeRankChunk - 1) / kEdgeRankChunk; }
 
 void check_shape(size_t num_src, size_t num_cand, size_t k) {

@@ -61,6 +61,16 @@ inline dim3 strided_grid(uint64_t items, uint32_t per_group, uint32_t max_groups
   return dim3(static_cast<uint32_t>(std::min<uint64_t>(groups, max_groups)));
 }
 
+// The geometry of the readers in which a wave takes a row at a time (seen_mask.hip,
+// pair_history.hip, neighbor_aggregate.hip, neighbor_sequence.hip), which launch
+// strided_grid(rows, kWaves, kMaxGrid) workgroups of kThreads.  The other readers have their own.
+namespace wave_per_row {
+constexpr int kThreads = 256;
+constexpr int kWave = 64;
+constexpr int kWaves = kThreads / kWave;      // rows a workgroup works on at a time
+constexpr uint32_t kMaxGrid = 4096;           // rows past kMaxGrid * kWaves are grid-strided
+}  // namespace wave_per_row
+
 // elements of the ascending run ts[0:n) that are < t (float <: a NaN t gives 0)
 __device__ __forceinline__ uint32_t count_before(const float* __restrict__ ts, uint32_t n,
                                                  float t) {

@@ -28,15 +28,13 @@
 // bound it.
 #include "neighbor_aggregate.hpp"
 #include "common.hpp"
+#include "feature_table.hpp"
 #include "history_window.hpp"
 
 namespace gf {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWave = 64;
-constexpr int kWaves = kThreads / kWave;      // rows a workgroup works on at a time
-constexpr uint32_t kMaxGrid = 4096;           // rows past kMaxGrid * kWaves are grid-strided
+using namespace wave_per_row;                 // kThreads, kWave, kWaves, kMaxGrid
 constexpr uint32_t kUnroll = 8;               // rows of a table in flight per wave
 
 struct Table {
@@ -68,8 +66,6 @@ __device__ __forceinline__ void divide(float4& a, float n) {
   a.x = __fdiv_rn(a.x, n); a.y = __fdiv_rn(a.y, n);
   a.z = __fdiv_rn(a.z, n); a.w = __fdiv_rn(a.w, n);
 }
-__device__ __forceinline__ void clear(float& a) { a = 0.0f; }
-__device__ __forceinline__ void clear(float4& a) { a = make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
 
 // lane `src`'s value in every lane, as a scalar
 __device__ __forceinline__ int64_t from_lane(int64_t v, int src) {
@@ -136,18 +132,11 @@ __global__ void __launch_bounds__(kThreads) neighbor_aggregate_kernel(const Aggr
   }
 }
 
-bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-
 // `out` may be null only in a call without rows
 Table table_of(const std::string& w, const char* name, const float* feats, size_t rows,
                size_t width, float* out, bool need_out) {
-  if (feats == nullptr) {
-    GF_REQUIRE(width == 0, w + ": " + name + " table is null but its width is not 0");
-    return {nullptr, 0, 0, 0, nullptr};
-  }
-  GF_REQUIRE(width >= 1 && width <= kAggregateMaxWidth,
-             w + ": " + name + " table width outside 1 .. 1024");
-  GF_REQUIRE(out != nullptr || !need_out, w + ": null output of the " + name + " table");
+  check_feature_table(w, name, feats, width, kAggregateMaxWidth, out != nullptr || !need_out);
+  if (feats == nullptr) return {nullptr, 0, 0, 0, nullptr};
   const bool vec4 = width % 4 == 0 && aligned16(feats) && aligned16(out);
   return {feats, rows, static_cast<uint32_t>(width), vec4 ? 1u : 0u, out};
 }
@@ -163,9 +152,9 @@ void neighbor_aggregate(const GraphView& g, const int64_t* d_nodes, const float*
   const std::string w("neighbor_aggregate");
   GF_REQUIRE(num_rows < (size_t{1} << 31), w + ": 2^31 rows or more");
   GF_REQUIRE(d_node_feats || d_edge_feats, w + ": no feature table");
-  const Table node = table_of(w, "node", d_node_feats, node_rows, dn, d_node_out,
+  const Table node = table_of(w, "the node table", d_node_feats, node_rows, dn, d_node_out,
                               num_rows != 0);
-  const Table edge = table_of(w, "edge", d_edge_feats, edge_rows, de, d_edge_out,
+  const Table edge = table_of(w, "the edge table", d_edge_feats, edge_rows, de, d_edge_out,
                               num_rows != 0);
   if (num_rows == 0) return;
   GF_REQUIRE(d_nodes && d_ts, w + ": null nodes or ts");

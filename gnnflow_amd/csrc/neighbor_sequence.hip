@@ -37,6 +37,7 @@
 // [N, L, W] is 64-bit; inside a row L * W <= 512 * 3072 fits 32 bits.
 #include "neighbor_sequence.hpp"
 #include "common.hpp"
+#include "feature_table.hpp"
 #include "history_window.hpp"
 #include "time_encode_expr.hpp"
 
@@ -46,10 +47,7 @@ namespace {
 static_assert(kSeqMaxLength == GF_SEQ_MAX_LENGTH && kSeqMaxWidth == GF_SEQ_MAX_WIDTH,
               "gnnflow_hip.h and neighbor_sequence.hpp disagree on the limits");
 
-constexpr int kThreads = 256;
-constexpr int kWave = 64;
-constexpr int kWaves = kThreads / kWave;      // rows a workgroup works on at a time
-constexpr uint32_t kMaxGrid = 4096;           // rows past kMaxGrid * kWaves are grid-strided
+using namespace wave_per_row;                 // kThreads, kWave, kWaves, kMaxGrid
 constexpr uint32_t kUnroll = 4;               // table chunks in flight per lane
 
 struct Part {
@@ -74,9 +72,6 @@ struct SequenceArgs {
   float* delta_t;            // [rows, L]
   float* tokens;             // [rows, L, W]; nullptr when no part is given
 };
-
-__device__ __forceinline__ void clear(float& a) { a = 0.0f; }
-__device__ __forceinline__ void clear(float4& a) { a = make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
 
 // columns j .. of the time part at delta dt
 __device__ __forceinline__ void encode(float& a, const float* __restrict__ w,
@@ -208,16 +203,10 @@ __global__ void __launch_bounds__(kThreads) neighbor_sequence_kernel(const Seque
   }
 }
 
-bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-
 Part part_of(const std::string& w, const char* name, const float* feats, size_t rows,
              size_t width) {
-  if (feats == nullptr) {
-    GF_REQUIRE(width == 0, w + ": " + name + " is null but its width is not 0");
-    return {nullptr, 0, 0};
-  }
-  GF_REQUIRE(width >= 1 && width <= kSeqMaxWidth,
-             w + ": width of " + name + " outside 1 .. " + std::to_string(kSeqMaxWidth));
+  check_feature_table(w, name, feats, width, kSeqMaxWidth);
+  if (feats == nullptr) return {nullptr, 0, 0};
   return {feats, rows, static_cast<uint32_t>(width)};
 }
 

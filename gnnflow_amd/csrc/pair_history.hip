@@ -25,10 +25,7 @@
 namespace gf {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWave = 64;
-constexpr int kWaves = kThreads / kWave;      // rows a workgroup works on at a time
-constexpr uint32_t kMaxGrid = 4096;           // rows past kMaxGrid * kWaves are grid-strided
+using namespace wave_per_row;      // kThreads, kWave, kWaves, kMaxGrid
 
 struct PairArgs {
   StoreView store;           // without a node: every row gets the empty answer

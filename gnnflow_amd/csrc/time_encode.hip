@@ -175,7 +175,6 @@ time_encode_bwd_finish(const float* __restrict__ partials, uint32_t rows, uint32
   }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 // can four elements at p be one store?  16-byte aligned float32, 8-byte aligned bfloat16
 template <class T>
 bool aligned4(const T* p) { return (reinterpret_cast<uintptr_t>(p) & (4 * sizeof(T) - 1)) == 0; }

@@ -4,11 +4,9 @@ gf_graph_temporal_degree) and of gnnflow_amd.NeighborOverlap's scores on top of 
 
 Histories as in tests/pair_history_ref.py: {node: (dst int64 [m], ts float32 [m], eid int64 [m])},
 OLDEST FIRST.  For row i with s = src[i], d = dst[i], t = ts[i] and, when `since` is given,
-lo = since[i], the window of a node v over h = histories[v] is pair_history's:
+lo = since[i], the window of a node v over h = histories[v] is pair_history's
+(tests/history_window_ref.py: c, c0, n) at the bound H = max_history, 1 .. MAX_HISTORY:
 
-    c  = #{x in h.ts : x < t}                    float32 <: a NaN t gives 0
-    c0 = min(c, #{x in h.ts : x < lo})           float32 <: a NaN lo gives 0; 0 without `since`
-    n  = min(c - c0, H)                          H = max_history, 1 .. MAX_HISTORY
     records h.dst[c - n : c], at positions 0 .. n - 1
 
 and empty for a node without a history.  A = window(s), B = window(d).  For z >= 0: a(z), b(z) =
@@ -24,7 +22,8 @@ is shaped like the kernel's table.
 """
 import numpy as np
 
-from tests.pair_history_ref import count_before, from_graph  # noqa: F401  (from_graph: for users)
+from tests import history_window_ref
+from tests.history_window_ref import count_before, from_graph  # noqa: F401  (re-exported)
 
 MAX_HISTORY = 512                  # GF_CN_MAX_HISTORY, also the bound of max_common
 SCORES = ("cn", "jaccard", "aa", "ra", "pa")
@@ -34,19 +33,17 @@ def _bounds(h, t, lo):
     """(c0, c) of a history at time t and lower end lo (None: no lower end)."""
     if h is None or len(h[0]) == 0:
         return 0, 0
-    c = count_before(h[1], t)
-    c0 = min(c, count_before(h[1], lo)) if lo is not None else 0
-    return c0, c
+    return history_window_ref.window(h[1], t, lo)      # without a bound c - n is c0
 
 
 def window(histories, v, t, lo, max_history):
-    """The destinations of node v's window, oldest first (int64 [n])."""
+    """The destinations of node v's window, oldest first (int64 [n]).  max_history is a bound
+    here, 0 included: 0 records, not "no bound"."""
     h = histories.get(int(v))
-    c0, c = _bounds(h, t, lo)
-    n = min(c - c0, max_history)
-    if n == 0:
+    if h is None or len(h[0]) == 0 or max_history == 0:
         return np.zeros(0, np.int64)
-    return np.asarray(h[0][c - n:c], np.int64)
+    a, c = history_window_ref.window(h[1], t, lo, max_history)
+    return np.asarray(h[0][a:c], np.int64)
 
 
 def common_neighbors(histories, src, dst, ts, since=None, max_history=64, max_common=32):

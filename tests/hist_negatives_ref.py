@@ -17,6 +17,7 @@ import numpy as np
 
 from tests.attention_dropout_ref import philox_first
 from tests.batch_stream_ref import MASK64, tids
+from tests.history_window_ref import count_before
 
 SEED_TAG = 0x484953544E454730      # GF_HIST_NEG_SEED_TAG, "HISTNEG0"
 ATTEMPTS = 4                       # GF_HIST_NEG_ATTEMPTS
@@ -31,9 +32,7 @@ def attempt_seed(seed, a):
 
 def history_size(h_ts, t):
     """c: elements of the node's timestamps strictly below t, compared as float32."""
-    h_ts = np.asarray(h_ts, dtype=np.float32)
-    with np.errstate(invalid="ignore"):
-        return int(np.count_nonzero(h_ts < np.float32(t)))
+    return count_before(h_ts, t)
 
 
 def draws(c, first_row, lo, B, K, Kh, seed, epoch):

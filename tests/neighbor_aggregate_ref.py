@@ -6,10 +6,8 @@ in the store's order; `from_graph` reads them with get_temporal_neighbors (which
 first) for every node a query names.  For row i with v = nodes[i], t = ts[i] and, when `since` is
 given, lo = since[i], over h = histories[v]:
 
-    c  = #{x in h.ts : x < t}                    float32 <: a NaN t gives 0
-    c0 = min(c, #{x in h.ts : x < lo})           float32 <: a NaN lo gives 0; 0 without `since`
-    n  = min(c - c0, max_history) if max_history else c - c0
-    considered = positions c - n .. c - 1        lo <= ts < t, the newest n, oldest first
+    considered = positions c - n .. c - 1, the window of h at (t, lo, max_history),
+                 tests/history_window_ref.py, oldest first
     count[i]   = n
     node[i, :] = (((0 + N[h.dst[c - n]]) + N[h.dst[c - n + 1]]) + ...) + N[h.dst[c - 1]]
     edge[i, :] = the same over E[h.eid[p]]
@@ -23,15 +21,7 @@ Pure numpy.
 """
 import numpy as np
 
-from tests.pair_history_ref import count_before, from_graph      # noqa: F401  (re-exported)
-
-
-def window(h_ts, t, lo=None, max_history=0):
-    """(c - n, c): the considered positions of a history with timestamps h_ts."""
-    c = count_before(h_ts, t)
-    c0 = min(c, count_before(h_ts, lo)) if lo is not None else 0
-    n = min(c - c0, max_history) if max_history else c - c0
-    return c - n, c
+from tests.history_window_ref import count_before, from_graph, window   # noqa: F401  (re-exported)
 
 
 def sequential_sum(table, ids):

@@ -4,11 +4,9 @@ include/gnnflow_hip.h: gf_graph_neighbor_cooccurrence).
 Histories as in tests/pair_history_ref.py: {node: (dst int64 [m], ts float32 [m], eid int64 [m])},
 OLDEST FIRST.  For row i with s = src[i], d = dst[i], t = ts[i] and, when `since` is given,
 lo = since[i], with L = length and self = 1 if include_self else 0, the window of a node v over
-h = histories[v] is common_neighbors' at the bound H = L - self (1 .. MAX_LENGTH - self):
+h = histories[v] is common_neighbors' at the bound H = L - self (1 .. MAX_LENGTH - self),
+tests/history_window_ref.py's c and n:
 
-    c  = #{x in h.ts : x < t}                    float32 <: a NaN t gives 0
-    c0 = min(c, #{x in h.ts : x < lo})           float32 <: a NaN lo gives 0; 0 without `since`
-    n  = min(c - c0, H)
     records c - n .. c - 1 of h, oldest first
 
 and empty for a node without a history.  seq(v) = [v itself if self] + the records' dst.  For
@@ -25,7 +23,7 @@ Pure numpy, dictionaries and loops: nothing here is shaped like the kernel's tab
 """
 import numpy as np
 
-from tests.pair_history_ref import count_before, from_graph  # noqa: F401  (from_graph: for users)
+from tests.history_window_ref import count_before, from_graph, window  # noqa: F401  (re-exported)
 
 MAX_LENGTH = 512                   # GF_COOC_MAX_LENGTH
 
@@ -39,10 +37,7 @@ def sequence(histories, v, t, lo, length, include_self):
     assert H >= 1
     h = histories.get(int(v))
     if h is not None and len(h[0]):
-        c = count_before(h[1], t)
-        c0 = min(c, count_before(h[1], lo)) if lo is not None else 0
-        n = min(c - c0, H)
-        for p in range(c - n, c):
+        for p in range(*window(h[1], t, lo, H)):
             nodes.append(int(h[0][p])), eids.append(int(h[2][p])), times.append(np.float32(h[1][p]))
     return nodes, eids, times
 

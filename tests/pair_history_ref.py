@@ -6,10 +6,7 @@ in the store's order; `from_graph` reads them with get_temporal_neighbors (which
 first) for every node a query names.  For row i with s = src[i], d = dst[i], t = ts[i] and, when
 `since` is given, lo = since[i], over h = histories[s]:
 
-    c  = #{x in h.ts : x < t}                    float32 <: a NaN t gives 0
-    c0 = min(c, #{x in h.ts : x < lo})           float32 <: a NaN lo gives 0; 0 without `since`
-    n  = min(c - c0, max_history) if max_history else c - c0
-    considered = positions c - n .. c - 1        lo <= ts < t, the newest n
+    considered  = the window of h at (t, lo, max_history), tests/history_window_ref.py
     count[i]    = #{p considered : h.dst[p] == d}
     last_ts[i]  = h.ts[p*],  last_eid[i] = h.eid[p*]    p* the largest such p;  -inf, -1 for none
 
@@ -17,15 +14,7 @@ A source without a history (negative, unknown, no live edges) gives (0, -inf, -1
 """
 import numpy as np
 
-
-def count_before(ts, t):
-    """#{x in ts : x < t} in float32; the history ascends, so these are a prefix.  NaN goes
-    through < as it is: nothing is below NaN."""
-    with np.errstate(invalid="ignore"):
-        before = np.asarray(ts, np.float32) < np.float32(t)
-    c = int(before.sum())
-    assert before[:c].all()
-    return c
+from tests.history_window_ref import count_before, from_graph, window  # noqa: F401  (re-exported)
 
 
 def pair_history(histories, src, dst, ts, since=None, max_history=0):
@@ -45,10 +34,8 @@ def pair_history(histories, src, dst, ts, since=None, max_history=0):
         if h is None or len(h[0]) == 0:
             continue
         h_dst, h_ts, h_eid = h
-        c = count_before(h_ts, ts[i])
-        c0 = min(c, count_before(h_ts, since[i])) if since is not None else 0
-        n = min(c - c0, max_history) if max_history else c - c0
-        hits = np.flatnonzero(np.asarray(h_dst[c - n:c], np.int64) == dst[i]) + (c - n)
+        a, c = window(h_ts, ts[i], None if since is None else since[i], max_history)
+        hits = np.flatnonzero(np.asarray(h_dst[a:c], np.int64) == dst[i]) + a
         count[i] = len(hits)
         if len(hits):
             last_ts[i] = np.float32(h_ts[hits[-1]])
@@ -70,13 +57,3 @@ def edge_bank_scores(histories, src, dst, ts, mode="unlimited", window=None, min
         return (count >= min_count).astype(np.float32)
     assert score == "count"
     return count.astype(np.float32)
-
-
-def from_graph(graph, nodes):
-    """{node: (dst, ts, eid)} oldest first, for every distinct valid node of `nodes`."""
-    out = {}
-    for v in np.unique(np.asarray(nodes, np.int64)):
-        if 0 <= v <= graph.max_vertex_id():
-            d, t, e = graph.get_temporal_neighbors(int(v))
-            out[int(v)] = (d[::-1].copy(), t[::-1].copy(), e[::-1].copy())
-    return out

@@ -13,6 +13,8 @@ in (bit 63 is the sign).  Pure numpy.
 """
 import numpy as np
 
+from tests import history_window_ref
+
 
 def num_words(C):
     return (C + 63) // 64
@@ -21,14 +23,8 @@ def num_words(C):
 def considered(history, t, max_history=0):
     """The dst of the considered entries of one history (oldest first) for a query at time t."""
     dst, ts = history
-    dst, ts = np.asarray(dst, np.int64), np.asarray(ts, np.float32)
-    with np.errstate(invalid="ignore"):
-        before = ts < np.float32(t)
-    # the history ascends in time, so the entries before t are a prefix
-    c = int(before.sum())
-    assert before[:c].all()
-    n = c if max_history == 0 else min(c, max_history)
-    return dst[c - n:c]
+    a, c = history_window_ref.window(ts, t, None, max_history)
+    return np.asarray(dst, np.int64)[a:c]
 
 
 def seen_mask(histories, src, ts, cand_ids, max_history=0):
@@ -63,9 +59,4 @@ def unpack(words, C):
 
 def from_graph(graph, nodes):
     """{node: (dst, ts)} oldest first, for every distinct valid node of `nodes`."""
-    out = {}
-    for v in np.unique(np.asarray(nodes, np.int64)):
-        if 0 <= v <= graph.max_vertex_id():
-            d, t, _ = graph.get_temporal_neighbors(int(v))
-            out[int(v)] = (d[::-1].copy(), t[::-1].copy())
-    return out
+    return {v: h[:2] for v, h in history_window_ref.from_graph(graph, nodes).items()}

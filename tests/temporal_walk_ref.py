@@ -25,6 +25,7 @@ newest first), `from_edges` builds them from the edge arrays the graph was given
 import numpy as np
 
 from tests.attention_dropout_ref import philox_first
+from tests.history_window_ref import count_before
 
 MASK64 = (1 << 64) - 1
 SEED_TAG = 0x54454D5057414C4B      # GF_WALK_SEED_TAG, "TEMPWALK"
@@ -64,8 +65,7 @@ def pick(u, n):
 
 def history_size(h_ts, t):
     """c: elements of the node's timestamps strictly below t, compared as float32."""
-    with np.errstate(invalid="ignore"):
-        return int(np.count_nonzero(np.asarray(h_ts, dtype=np.float32) < np.float32(t)))
+    return count_before(h_ts, t)
 
 
 def walks(histories, table_len, src, ts, length, num_walks=1, recency=1, max_history=0, seed=0,

@@ -1,9 +1,10 @@
 """Which error wins when two arguments of an edge-history reader are wrong at once.
 
-The five checkers (dynamic_graph.check_seen_mask_args, check_pair_history_args,
-check_common_neighbors_args, check_temporal_degree_args, check_temporal_walk_args) report their
-errors in a fixed order, and callers see that order: the per-reader error tests pin every message,
-this file pins the order.  Each case breaks two checks that are adjacent in a checker's order and
+The seven checkers (dynamic_graph.check_seen_mask_args, check_pair_history_args,
+check_common_neighbors_args, check_temporal_degree_args, check_temporal_walk_args,
+check_neighbor_aggregate_args, check_neighbor_sequence_args) report their errors in a fixed order,
+and callers see that order: the per-reader error tests pin every message, this file pins the
+order.  Each case breaks two checks that are adjacent in a checker's order and
 names the one reported; the expected winners were written from the checkers as they stood before
 they were folded onto shared helpers.  CPU only: a tensor on `meta` stands for another device, and
 a zero-stride view for 2**31 rows without their memory."""
@@ -11,7 +12,8 @@ import numpy as np
 import pytest
 import torch
 
-from gnnflow_amd.dynamic_graph import (check_common_neighbors_args, check_pair_history_args,
+from gnnflow_amd.dynamic_graph import (check_common_neighbors_args, check_neighbor_aggregate_args,
+                                       check_neighbor_sequence_args, check_pair_history_args,
                                        check_seen_mask_args, check_temporal_degree_args,
                                        check_temporal_walk_args)
 
@@ -28,6 +30,10 @@ def f32(n=4, device="cpu"):
 
 def big(dtype, device="cpu"):
     return torch.zeros(1, dtype=dtype, device=device).expand(BIG)
+
+
+def tab(rows=6, cols=8, device="cpu"):
+    return torch.zeros((rows, cols), dtype=torch.float32, device=device)
 
 
 def seen(**over):
@@ -59,6 +65,21 @@ def walk(**over):
              first_row=0)
     a.update(over)
     return check_temporal_walk_args(**a)
+
+
+def agg(**over):
+    # one table: taking it away is then a fault of its own
+    a = dict(nodes=i64(), ts=f32(), node_feats=tab(), edge_feats=None, since=None, max_history=0,
+             reduce="mean")
+    a.update(over)
+    return check_neighbor_aggregate_args(**a)
+
+
+def seq(**over):
+    a = dict(nodes=i64(), ts=f32(), since=None, length=8, edge_feats=tab(), node_feats=tab(),
+             time_encoder=(tab(4, 1), f32()))
+    a.update(over)
+    return check_neighbor_sequence_args(**a)
 
 
 # (checker, the two faults, the exception, what its message starts with)
@@ -150,6 +171,114 @@ CASES = [
      "temporal_random_walk takes fewer than 2\\*\\*31 walks"),
     (walk, dict(src=i64(2 ** 15), ts=f32(2 ** 15, "meta"), num_walks=2 ** 16 - 1), ValueError,
      "ts is on meta, src on"),
+    # neighbor_aggregate: half-precision node_feats, edge_feats; types of nodes, ts, node_feats,
+    # edge_feats, since; max_history's type; reduce's type; 1-D; lengths; 2**31 rows; no table;
+    # per table, node_feats first: 2-D, no rows, columns, contiguous; reduce's value;
+    # max_history's sign; devices
+    (agg, dict(node_feats=tab().half(), nodes=i64().int()), TypeError,
+     "node_feats must be float32, got torch.float16: half-precision"),
+    (agg, dict(node_feats=tab().half(), edge_feats=tab().bfloat16()), TypeError,
+     "node_feats must be float32, got torch.float16"),
+    (agg, dict(edge_feats=tab().bfloat16(), nodes=[0, 1]), TypeError,
+     "edge_feats must be float32, got torch.bfloat16: half-precision"),
+    (agg, dict(nodes=i64().int(), ts=f32().double()), TypeError, "nodes must be torch.int64"),
+    (agg, dict(ts=f32().double(), node_feats=tab().double()), TypeError,
+     "ts must be torch.float32"),
+    (agg, dict(node_feats=tab().double(), edge_feats=tab().int()), TypeError,
+     "node_feats must be torch.float32"),
+    (agg, dict(edge_feats=np.zeros((6, 8), np.float32), since=f32().double()), TypeError,
+     "edge_feats must be a tensor"),
+    (agg, dict(since=f32().double(), max_history=None), TypeError, "since must be torch.float32"),
+    (agg, dict(since="yesterday", max_history=1.0), TypeError, "since must be None, a float or"),
+    (agg, dict(max_history=True, reduce=None), TypeError, "max_history must be an int"),
+    (agg, dict(max_history=np.int64(3), reduce=None), TypeError, "max_history must be an int"),
+    (agg, dict(reduce=None, nodes=i64().reshape(2, 2)), TypeError, "reduce must be a str"),
+    (agg, dict(nodes=i64().reshape(2, 2), ts=f32(3)), ValueError, "nodes must be 1-D"),
+    (agg, dict(since=f32().reshape(2, 2), ts=f32(3)), ValueError, "since must be 1-D"),
+    (agg, dict(ts=f32(3), since=f32(5)), ValueError, "nodes has 4 rows, ts has 3"),
+    (agg, dict(since=f32(5), node_feats=None), ValueError, "nodes has 4 rows, since has 5"),
+    (agg, dict(nodes=big(torch.int64), ts=f32(3)), ValueError,
+     "nodes has 2147483648 rows, ts has 3"),
+    (agg, dict(nodes=big(torch.int64), ts=big(torch.float32), node_feats=None), ValueError,
+     "neighbor_aggregate takes fewer than 2\\*\\*31 rows"),
+    (agg, dict(node_feats=None, reduce="max"), ValueError,
+     "neighbor_aggregate needs node_feats or edge_feats"),
+    (agg, dict(node_feats=None, max_history=-1), ValueError,
+     "neighbor_aggregate needs node_feats or edge_feats"),
+    (agg, dict(node_feats=torch.zeros(0)), ValueError, "node_feats must be 2-D"),
+    (agg, dict(node_feats=tab(0, 2000)), ValueError, "node_feats has no rows"),
+    (agg, dict(node_feats=tab(2000, 6).t()), ValueError,
+     "node_feats must have 1 to 1024 columns, got 2000"),
+    (agg, dict(node_feats=tab().t(), edge_feats=f32(6)), ValueError,
+     "node_feats must be contiguous"),
+    (agg, dict(edge_feats=f32(6), reduce="max"), ValueError, "edge_feats must be 2-D"),
+    (agg, dict(edge_feats=tab().t(), reduce="max"), ValueError, "edge_feats must be contiguous"),
+    (agg, dict(reduce="max", max_history=-1), ValueError, "reduce must be 'sum' or 'mean'"),
+    (agg, dict(max_history=-1, ts=f32(4, "meta")), ValueError, "max_history must be >= 0"),
+    (agg, dict(ts=f32(4, "meta"), node_feats=tab(device="meta")), ValueError,
+     "ts is on meta, nodes on"),
+    (agg, dict(node_feats=tab(device="meta"), since=f32(4, "meta")), ValueError,
+     "node_feats is on meta, nodes on"),
+    # neighbor_sequence: half-precision edge_feats, node_feats; what time_encoder is; types of
+    # nodes, ts, edge_feats, node_feats, the encoder's weight and bias, since; length's type, then
+    # range; 1-D; lengths; 2**31 rows; per table, edge_feats first: 2-D, no rows, columns,
+    # contiguous; the encoder's bias, width, weight; devices
+    (seq, dict(edge_feats=tab().half(), nodes=i64().int()), TypeError,
+     "edge_feats must be float32, got torch.float16: half-precision"),
+    (seq, dict(edge_feats=tab().bfloat16(), node_feats=tab().half()), TypeError,
+     "edge_feats must be float32, got torch.bfloat16"),
+    (seq, dict(node_feats=tab().half(), time_encoder=3), TypeError,
+     "node_feats must be float32, got torch.float16: half-precision"),
+    (seq, dict(time_encoder=(f32(), f32(), f32()), nodes=i64().int()), TypeError,
+     "time_encoder must be a module or a \\(weight, bias\\) pair, got 3 elements"),
+    (seq, dict(time_encoder=3, nodes=[0, 1]), TypeError,
+     "time_encoder must be a module with weight and bias or"),
+    (seq, dict(nodes=i64().int(), ts=f32().double()), TypeError, "nodes must be torch.int64"),
+    (seq, dict(ts=f32().double(), edge_feats=tab().double()), TypeError,
+     "ts must be torch.float32"),
+    (seq, dict(edge_feats=tab().double(), node_feats=tab().int()), TypeError,
+     "edge_feats must be torch.float32"),
+    (seq, dict(node_feats=tab().int(), time_encoder=(tab(4, 1).double(), f32())), TypeError,
+     "node_feats must be torch.float32"),
+    (seq, dict(time_encoder=(tab(4, 1).double(), f32().double())), TypeError,
+     "time_encoder's weight must be torch.float32"),
+    (seq, dict(time_encoder=(tab(4, 1), [0.0] * 4), since=f32().double()), TypeError,
+     "time_encoder's bias must be a tensor"),
+    (seq, dict(since=f32().double(), length=1.0), TypeError, "since must be torch.float32"),
+    (seq, dict(since="yesterday", length=None), TypeError, "since must be None, a float or"),
+    (seq, dict(length=True, nodes=i64().reshape(2, 2)), TypeError, "length must be an int"),
+    (seq, dict(length=513, nodes=i64().reshape(2, 2)), ValueError,
+     "length must be in \\[1, 513\\)"),
+    (seq, dict(nodes=i64().reshape(2, 2), ts=f32(3)), ValueError, "nodes must be 1-D"),
+    (seq, dict(since=f32().reshape(2, 2), ts=f32(3)), ValueError, "since must be 1-D"),
+    (seq, dict(ts=f32(3), since=f32(5)), ValueError, "nodes has 4 rows, ts has 3"),
+    (seq, dict(since=f32(5), edge_feats=f32(6)), ValueError, "nodes has 4 rows, since has 5"),
+    (seq, dict(nodes=big(torch.int64), ts=f32(3)), ValueError,
+     "nodes has 2147483648 rows, ts has 3"),
+    (seq, dict(nodes=big(torch.int64), ts=big(torch.float32), edge_feats=f32(6)), ValueError,
+     "neighbor_sequence takes fewer than 2\\*\\*31 rows"),
+    (seq, dict(edge_feats=torch.zeros(0)), ValueError, "edge_feats must be 2-D"),
+    (seq, dict(edge_feats=tab(0, 2000)), ValueError, "edge_feats has no rows"),
+    (seq, dict(edge_feats=tab(2000, 6).t()), ValueError,
+     "edge_feats must have 1 to 1024 columns, got 2000"),
+    (seq, dict(edge_feats=tab().t(), node_feats=f32(6)), ValueError,
+     "edge_feats must be contiguous"),
+    (seq, dict(node_feats=f32(6), time_encoder=(tab(4, 1), tab(4, 1))), ValueError,
+     "node_feats must be 2-D"),
+    (seq, dict(node_feats=tab().t(), time_encoder=(tab(4, 1), tab(4, 1))), ValueError,
+     "node_feats must be contiguous"),
+    (seq, dict(time_encoder=(tab(3, 1), tab(2000, 1))), ValueError,
+     "time_encoder's bias must be \\[dT\\], got shape \\(2000, 1\\)"),
+    (seq, dict(time_encoder=(tab(3, 1), f32(2000))), ValueError,
+     "time_encoder must have 1 to 1024 columns, got 2000"),
+    (seq, dict(time_encoder=(tab(3, 1), f32()), ts=f32(4, "meta")), ValueError,
+     "time_encoder's weight must be \\[dT, 1\\] or \\[dT\\] with dT = 4"),
+    (seq, dict(ts=f32(4, "meta"), edge_feats=tab(device="meta")), ValueError,
+     "ts is on meta, nodes on"),
+    (seq, dict(edge_feats=tab(device="meta"), time_encoder=(tab(4, 1), f32(4, "meta"))),
+     ValueError, "edge_feats is on meta, nodes on"),
+    (seq, dict(time_encoder=(tab(4, 1), f32(4, "meta")), since=f32(4, "meta")), ValueError,
+     "time_encoder's bias is on meta, nodes on"),
 ]
 
 
