@@ -8,7 +8,7 @@ from .baselines import EdgeBank, NeighborOverlap
 from .data import DeviceBatchStream, DeviceDstSet
 from .dynamic_graph import (CommonNeighbors, DynamicGraph, NeighborAggregate,
                             NeighborCooccurrence, NeighborSequence, PairHistory,
-                            TemporalWalks)
+                            PairSequence, TemporalWalks)
 from .metrics import LinkMetrics
 from .mfg import MFGBlock
 from .nn import (MLP, EdgePredictor, FixedTimeEncode, GATConv, GRUMemeoryUpdater,
@@ -22,4 +22,4 @@ __all__ = ["DynamicGraph", "TemporalSampler", "SamplingResult", "MFGBlock", "SAG
            "DeviceDstSet", "DeviceBatchStream", "TemporalWalks", "PairHistory", "EdgeBank",
            "CommonNeighbors", "NeighborOverlap", "NeighborCooccurrence",
            "NeighborCooccurrenceEncoder", "NeighborAggregate", "FixedTimeEncode",
-           "NeighborSequence"]
+           "NeighborSequence", "PairSequence"]

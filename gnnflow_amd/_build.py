@@ -14,7 +14,7 @@ LIB = os.path.join(CSRC, "libgnnflow_hip.so")
 SOURCES = ["capi.hip", "capi_graph.hip", "capi_sampler.hip", "capi_cache.hip", "capi_comm.hip",
            "enqueue_worker.hip", "profile.hip", "edge_store.hip", "edge_store_ingest.hip", "sampler.hip", "sample_layer.hip", "sample_padded.hip", "sample_merge.hip", "sampler_group.hip",
            "feature_cache.hip", "gather.hip", "cache_staging.hip", "cache_pull.hip",
-           "cache_select.hip", "cache_lru.hip", "cache_lru_fused.hip", "cache_lru_queue.hip", "memory_ops.hip", "block_ops.hip", "block_attention.hip", "block_gat.hip", "time_encode.hip", "edge_score.hip", "edge_rank.hip", "layer_epilogue.hip", "gru_cell.hip", "link_metrics.hip", "link_loss.hip", "batch_stream.hip", "hist_negatives.hip", "seen_mask.hip", "pair_history.hip", "common_neighbors.hip", "neighbor_cooccurrence.hip", "neighbor_aggregate.hip", "neighbor_sequence.hip", "temporal_walk.hip", "walk_positions.hip", "partition.hip", "ingest_sort.hip", "comm.hip"]
+           "cache_select.hip", "cache_lru.hip", "cache_lru_fused.hip", "cache_lru_queue.hip", "memory_ops.hip", "block_ops.hip", "block_attention.hip", "block_gat.hip", "time_encode.hip", "edge_score.hip", "edge_rank.hip", "layer_epilogue.hip", "gru_cell.hip", "link_metrics.hip", "link_loss.hip", "batch_stream.hip", "hist_negatives.hip", "seen_mask.hip", "pair_history.hip", "common_neighbors.hip", "neighbor_cooccurrence.hip", "neighbor_aggregate.hip", "neighbor_sequence.hip", "pair_sequence.hip", "temporal_walk.hip", "walk_positions.hip", "partition.hip", "ingest_sort.hip", "comm.hip"]
 # every header under csrc/ (a new one is picked up without touching this file) + the public ones
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith((".hpp", ".h"))) + [
     os.path.join("..", "..", "include", "gnnflow_hip.h"),

@@ -345,6 +345,9 @@ PROTOTYPES = {
                                               C.c_int, _p, _p, _p, C.c_int, _p]),
     "gf_graph_neighbor_sequence": (C.c_int, [_p, _p, _p, _p, _sz, _sz, _p, _sz, _sz, _p, _sz, _sz,
                                              _p, _p, _sz, _p, _p, _p, _p, _p, _p, C.c_int, _p]),
+    "gf_graph_pair_sequence": (C.c_int, [_p, _p, _p, _p, _p, _sz, _sz, _p, _sz, _sz, _p, _sz, _sz,
+                                         _p, _p, _sz, _p, _p, _p, _p, _p, _p, _p, _p, _p, C.c_int,
+                                         _p]),
     "gf_graph_temporal_walks": (C.c_int, [_p, _p, _p, _sz, _sz, _sz, _sz, _sz, C.c_uint64,
                                           C.c_uint64, C.c_uint64, _p, _p, _p, C.c_int, _p]),
     "gf_walk_position_counts": (C.c_int, [_p, _p, _sz, _sz, _sz, _sz, _sz, _p, C.c_int, _p]),

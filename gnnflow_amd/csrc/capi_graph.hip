@@ -7,6 +7,7 @@
 #include "neighbor_cooccurrence.hpp"
 #include "neighbor_sequence.hpp"
 #include "pair_history.hpp"
+#include "pair_sequence.hpp"
 #include "seen_mask.hpp"
 #include "temporal_walk.hpp"
 
@@ -179,6 +180,23 @@ int gf_graph_neighbor_sequence(const gf_graph* g, const int64_t* d_nodes, const 
                           edge_rows, de, d_node_feats, node_rows, dn, d_weight, d_bias, dim_time,
                           d_lengths, d_out_nodes, d_eids, d_times, d_delta_t, d_tokens, device,
                           as_stream(stream));
+  });
+}
+// reads the store's view NOW, as gf_batch_hist_negatives does
+int gf_graph_pair_sequence(const gf_graph* g, const int64_t* d_src, const int64_t* d_dst,
+                           const float* d_ts, const float* d_since, size_t num_rows,
+                           size_t length, const float* d_node_feats, size_t node_rows, size_t dn,
+                           const float* d_edge_feats, size_t edge_rows, size_t de,
+                           const float* d_weight, const float* d_bias, size_t dim_time,
+                           int32_t* d_lengths, int64_t* d_nodes, int64_t* d_eids, float* d_times,
+                           float* d_delta_t, int32_t* d_counts, float* d_node_out,
+                           float* d_edge_out, float* d_time_out, int device, void* stream) {
+  return guarded([&] {
+    GF_G(g);
+    gf::pair_sequence(g->impl.view(), d_src, d_dst, d_ts, d_since, num_rows, length,
+                      d_node_feats, node_rows, dn, d_edge_feats, edge_rows, de, d_weight, d_bias,
+                      dim_time, d_lengths, d_nodes, d_eids, d_times, d_delta_t, d_counts,
+                      d_node_out, d_edge_out, d_time_out, device, as_stream(stream));
   });
 }
 // reads the store's view NOW, as gf_batch_hist_negatives does

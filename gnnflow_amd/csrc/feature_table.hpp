@@ -1,6 +1,6 @@
 // What the readers of optional feature tables share (neighbor_aggregate.hip,
-// neighbor_sequence.hip): the host check of a float table [rows, width] as it arrives over the C
-// ABI, and the zero of a column of one float or four.  How a kernel sees a table stays with its
+// neighbor_sequence.hip, pair_sequence.hip): the host check of a float table [rows, width] as it
+// arrives over the C ABI, and the zero of a column of one float or four.  How a kernel sees a table stays with its
 // reader: each packs what it checked here into its own argument struct.
 #pragma once
 

@@ -1,9 +1,9 @@
 // "The edges of a node strictly before t": the one statement of the history window that the
 // edge-history readers share (hist_negatives.hip, seen_mask.hip, pair_history.hip,
 // temporal_walk.hip, common_neighbors.hip with temporal_degree, neighbor_cooccurrence.hip,
-// neighbor_aggregate.hip, neighbor_sequence.hip).  The store keeps one contiguous, chronologically
-// sorted run per node (edge_store.hpp); for node v, time t, optional lower end lo and bound H
-// (max_history, 0: none):
+// neighbor_aggregate.hip, neighbor_sequence.hip, pair_sequence.hip).  The store keeps one
+// contiguous, chronologically sorted run per node (edge_store.hpp); for node v, time t, optional
+// lower end lo and bound H (max_history, 0: none):
 //
 //   e  = table[v]                 v < 0, v >= table_len, e.size == 0: the window is empty
 //   c  = #{x in ts_pool[e.start .. e.start + e.size) : x < t}        float <: NaN t gives 0

@@ -1,7 +1,7 @@
 // The probing of a row's LDS table keyed by the 64-bit neighbour id, shared by the readers that
-// hash a row's two windows (common_neighbors.hip, neighbor_cooccurrence.hip).  Each file keeps its
-// own table struct, whose slots differ (20 bytes with pa, 16 without); what is shared is how a
-// slot is found: open addressing, linear probing, `cap` slots in use (a power of two, shift =
+// hash a row's two windows (common_neighbors.hip, neighbor_cooccurrence.hip, pair_sequence.hip).
+// Each file keeps its own table struct, whose slots differ (20 bytes with pa, 16 without); what
+// is shared is how a slot is found: open addressing, linear probing, `cap` slots in use (a power of two, shift =
 // 64 - log2(cap)), the empty mark -1, which no neighbour is.  A table type T has `int64_t key[]`
 // with at least cap elements, all kIdEmpty before the first claim.
 //

@@ -1,7 +1,8 @@
 // cos(w * t + b), the time encoding's one expression: time_encode.hip (forward and, through
-// te_arg, backward) and neighbor_sequence.hip (the time part of a token) evaluate it through this
-// header and nowhere else, so that the two agree bit for bit.  The library is built with
-// -ffp-contract=off and without fast-math: the argument is one multiply and one add, each rounded.
+// te_arg, backward), neighbor_sequence.hip (the time part of a token) and pair_sequence.hip (the
+// time part of a pair's slots) evaluate it through this header and nowhere else, so that they
+// agree bit for bit.  The library is built with -ffp-contract=off and without fast-math: the
+// argument is one multiply and one add, each rounded.
 // cosf is the precise form: a real timestamp times the first frequency is an argument of 1e6 rad
 // and more, where __cosf is wrong in the first digit.
 #pragma once

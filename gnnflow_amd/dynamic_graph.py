@@ -10,13 +10,14 @@ import numpy as np
 
 from . import _capi
 from .history import (AGG_MAX_WIDTH, CN_MAX_HISTORY, COOC_MAX_LENGTH,  # noqa: F401
-                      SEQ_MAX_LENGTH, SEQ_MAX_WIDTH, WALK_MAX_LENGTH, WALK_MAX_RECENCY,
-                      CommonNeighbors, HistoryReaders, NeighborAggregate, NeighborCooccurrence,
-                      NeighborSequence, PairHistory, TemporalWalks, check_common_neighbors_args,
+                      PAIRSEQ_MAX_LENGTH, PAIRSEQ_MAX_WIDTH, SEQ_MAX_LENGTH, SEQ_MAX_WIDTH,
+                      WALK_MAX_LENGTH, WALK_MAX_RECENCY, CommonNeighbors, HistoryReaders,
+                      NeighborAggregate, NeighborCooccurrence, NeighborSequence, PairHistory,
+                      PairSequence, TemporalWalks, check_common_neighbors_args,
                       check_neighbor_aggregate_args, check_neighbor_cooccurrence_args,
                       check_neighbor_sequence_args, check_pair_history_args,
-                      check_seen_mask_args, check_temporal_degree_args,
-                      check_temporal_walk_args)
+                      check_pair_sequence_args, check_seen_mask_args,
+                      check_temporal_degree_args, check_temporal_walk_args)
 
 
 def _i64(a):

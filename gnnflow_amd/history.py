@@ -1,5 +1,5 @@
 """The edge-history readers of DynamicGraph (seen_mask, pair_history, common_neighbors,
-temporal_degree, neighbor_cooccurrence, neighbor_aggregate, neighbor_sequence,
+temporal_degree, neighbor_cooccurrence, neighbor_aggregate, neighbor_sequence, pair_sequence,
 temporal_random_walk): their argument checkers, result types and limits, and HistoryReaders, the
 base class that gives DynamicGraph the methods.  dynamic_graph.py re-exports the public names."""
 from typing import NamedTuple, Optional
@@ -308,21 +308,65 @@ def check_neighbor_sequence_args(nodes, ts, since=None, length=32, edge_feats=No
     L = _int_arg(length, "length", 1, SEQ_MAX_LENGTH + 1)
     N = _table_rows(tensors, "neighbor_sequence")
     width = _feature_tables(tables, SEQ_MAX_WIDTH)
-    dT = 0
-    if encoder:
-        weight, bias = encoder[0][1], encoder[1][1]
-        if bias.dim() != 1:
-            raise ValueError("time_encoder's bias must be [dT], got shape {}".format(
-                tuple(bias.shape)))
-        dT = int(bias.shape[0])
-        if not 1 <= dT <= SEQ_MAX_WIDTH:
-            raise ValueError("time_encoder must have 1 to {} columns, got {}".format(
-                SEQ_MAX_WIDTH, dT))
-        if tuple(weight.shape) not in ((dT, 1), (dT,)):
-            raise ValueError("time_encoder's weight must be [dT, 1] or [dT] with dT = {}, got "
-                             "shape {}".format(dT, tuple(weight.shape)))
+    dT = _encoder_width(encoder, SEQ_MAX_WIDTH)
     _same_device(tensors)
     return N, L, width.get("edge_feats", 0), width.get("node_feats", 0), dT
+
+
+PAIRSEQ_MAX_LENGTH = 512      # GF_PAIRSEQ_MAX_LENGTH
+PAIRSEQ_MAX_WIDTH = 1024      # GF_PAIRSEQ_MAX_WIDTH
+
+
+class PairSequence(NamedTuple):
+    """What DynamicGraph.pair_sequence returns, one row per (src, dst, ts) row; side 0 is src's
+    sequence, side 1 dst's, L = length slots each: the self slot, then oldest first, then padding."""
+    lengths: torch.Tensor            # int32 [N, 2]; filled slots of each side, the self slot included
+    nodes: torch.Tensor              # int64 [N, 2, L]; the sequence's nodes, then -1
+    eids: torch.Tensor               # int64 [N, 2, L]; the edges' ids; -1 for the self slot, padding
+    times: torch.Tensor              # float32 [N, 2, L]; the edges' times; ts for the self slot; then 0
+    delta_t: torch.Tensor            # float32 [N, 2, L]; ts[i] - times on a filled slot, then 0
+    counts: torch.Tensor             # int32 [N, 2, L, 2]; occurrences in src's, in dst's sequence
+    node: Optional[torch.Tensor]     # float32 [N, 2, L, dn], zeros in the padding, or None
+    edge: Optional[torch.Tensor]     # float32 [N, 2, L, de], zeros in the padding, or None
+    time: Optional[torch.Tensor]     # float32 [N, 2, L, dT], zeros in the padding, or None
+
+
+def _encoder_width(encoder, max_width):
+    """dT of the (name, tensor, dtype) triples of a time encoder's weight and bias; 0 without."""
+    if not encoder:
+        return 0
+    weight, bias = encoder[0][1], encoder[1][1]
+    if bias.dim() != 1:
+        raise ValueError("time_encoder's bias must be [dT], got shape {}".format(
+            tuple(bias.shape)))
+    dT = int(bias.shape[0])
+    if not 1 <= dT <= max_width:
+        raise ValueError("time_encoder must have 1 to {} columns, got {}".format(max_width, dT))
+    if tuple(weight.shape) not in ((dT, 1), (dT,)):
+        raise ValueError("time_encoder's weight must be [dT, 1] or [dT] with dT = {}, got "
+                         "shape {}".format(dT, tuple(weight.shape)))
+    return dT
+
+
+def check_pair_sequence_args(src, dst, ts, since=None, length=32, node_feats=None,
+                             edge_feats=None, time_encoder=None):
+    """Arguments of DynamicGraph.pair_sequence, checked before anything is launched or
+    allocated: the kernel takes raw pointers and trusts them.  Needs no device.
+    Returns (N, L, dn, de, dT), a width of 0 for a part that is not given."""
+    tables = _given_tables((("node_feats", node_feats), ("edge_feats", edge_feats)))
+    encoder = []
+    if time_encoder is not None:
+        weight, bias = _encoder_tensors(time_encoder)
+        encoder = [("time_encoder's weight", weight, torch.float32),
+                   ("time_encoder's bias", bias, torch.float32)]
+    tensors = _typed_tensors(_pair_tensors(src, dst, ts) + tables + encoder, since)
+    # length - 1 bounds the window behind the self slot, and a bound of 0 would be "no bound"
+    L = _int_arg(length, "length", 2, PAIRSEQ_MAX_LENGTH + 1)
+    N = _rows([t for t in tensors if t[0] in ("src", "dst", "ts", "since")], "pair_sequence")
+    width = _feature_tables(tables, PAIRSEQ_MAX_WIDTH)
+    dT = _encoder_width(encoder, PAIRSEQ_MAX_WIDTH)
+    _same_device(tensors)
+    return N, L, width.get("node_feats", 0), width.get("edge_feats", 0), dT
 
 
 WALK_MAX_LENGTH = 32      # GF_WALK_MAX_LENGTH
@@ -760,6 +804,88 @@ class HistoryReaders:
                              _ptr(w), _ptr(b), dT, lengths.data_ptr(), out_nodes.data_ptr(),
                              eids.data_ptr(), times.data_ptr(), delta_t.data_ptr(), _ptr(tokens))
         return NeighborSequence(lengths, out_nodes, eids, times, delta_t, tokens)
+
+    def pair_sequence(self, src: torch.Tensor, dst: torch.Tensor, ts: torch.Tensor, *,
+                      since=None, length: int = 32, node_feats: Optional[torch.Tensor] = None,
+                      edge_feats: Optional[torch.Tensor] = None,
+                      time_encoder=None) -> PairSequence:
+        """Everything DyGFormer concatenates for a pair, finished, from one launch:
+        PairSequence(lengths int32 [N, 2]; nodes, eids int64 [N, 2, L]; times, delta_t float32
+        [N, 2, L]; counts int32 [N, 2, L, 2]; node float32 [N, 2, L, dn] or None; edge float32
+        [N, 2, L, de] or None; time float32 [N, 2, L, dT] or None), L = length.  Side 0 is
+        src[i]'s sequence, side 1 dst[i]'s.  The pair reader with features (models.DyGFormer.
+        forward_graph), where neighbor_sequence is the per-node one.
+
+        - lengths, nodes, eids, times and counts are neighbor_cooccurrence(src, dst, ts,
+          since=since, length=L, include_self=True)'s, element for element and bit for bit: the
+          self slot is always there (position 0, eid -1, time ts[i], counted), the window behind
+          it is csrc/history_window.hpp's with the bound L - 1, oldest first, and the padding is
+          -1, -1, 0, (0, 0).
+        - delta_t[i, side, p] = ts[i] - times[i, side, p], one float32 subtraction on every
+          filled slot, the self slot included (ts[i] - ts[i]); the padding holds +0.0.
+        - node[i, side, p] = node_feats[nodes[i, side, p]] and edge[i, side, p] =
+          edge_feats[eids[i, side, p]] on a filled slot: copies of the rows, bit for bit; an id
+          without a row in its table (negative, or at or past its number of rows) gives zeros,
+          neighbor_aggregate's rule.  The self slot therefore has the node's own row in `node`
+          and a zero row in `edge`.
+        - time[i, side, p] = cos(w * delta_t[i, side, p] + b) on a filled slot, ops.time_encode's
+          expression evaluated by the same code: it equals ops.time_encode(delta_t.reshape(-1),
+          weight, bias) bit for bit there.  The self slot is the encoding of its own delta_t,
+          not zero.
+        - Every element of a padded slot is +0.0 in all three parts: what masked_fill(padding,
+          0.0) leaves.  A part that is not given is None.
+
+        Each part is its own contiguous tensor, because DyGFormer patches and projects each
+        channel on its own: part.reshape(N, 2, L // P, P * d) is a view.  src[i] == dst[i] is
+        legal.  "Strictly before" and "live" as for seen_mask.  The exact rule is in
+        include/gnnflow_hip.h (gf_graph_pair_sequence), and it is restated in numpy in
+        tests/pair_sequence_ref.py.
+
+        src, dst: int64 [N], ts: float32 [N]; since: None, a float or a float32 tensor [N];
+        2 <= length <= 512; node_feats, edge_feats: float32 [rows, 1 .. 1024], contiguous (a
+        non-contiguous table is a ValueError, not a silent copy of what may be gigabytes; a
+        float16 or bfloat16 table is a TypeError); time_encoder: a module that holds `weight`
+        [dT, 1] and `bias` [dT] (nn.FixedTimeEncode, nn.TimeEncode) or a (weight, bias) pair,
+        float32, 1 <= dT <= 1024; all tensors on the graph's device.  The tables and the
+        encoder are read detached: no gradient flows to them or to ts, and the outputs do not
+        require grad.  N == 0 returns empty tensors of these shapes without a launch; a graph
+        without nodes gives the self slots alone.
+
+        One kernel (csrc/pair_sequence.hip: neighbor_cooccurrence's LDS table and phases, then
+        the row's threads spread over the flattened (side, position, column) space of each
+        part; the same inputs give the same bits) on the current stream, memory from torch,
+        never synchronises.  Synchronise the streams that calls were launched on before
+        add_edges or offload_old_blocks, as for seen_mask.  The cost is the 2 * (length - 1)
+        records and table rows read per row and the 2 * length * (36 + 4 * (dn + de + dT))
+        bytes written."""
+        N, L, dn, de, dT = check_pair_sequence_args(src, dst, ts, since, length, node_feats,
+                                                    edge_feats, time_encoder)
+        dev = self._check_on_device(src.device)
+
+        def part(width):
+            return torch.empty((N, 2, L, width), dtype=torch.float32,
+                               device=dev) if width else None
+
+        with torch.cuda.device(self._device):
+            lengths = torch.empty((N, 2), dtype=torch.int32, device=dev)
+            nodes = torch.empty((N, 2, L), dtype=torch.int64, device=dev)
+            eids = torch.empty((N, 2, L), dtype=torch.int64, device=dev)
+            times = torch.empty((N, 2, L), dtype=torch.float32, device=dev)
+            delta_t = torch.empty((N, 2, L), dtype=torch.float32, device=dev)
+            counts = torch.empty((N, 2, L, 2), dtype=torch.int32, device=dev)
+            node, edge, time = part(dn), part(de), part(dT)
+            if N:
+                s, d, t = _row_tensors(src, dst, ts)
+                lo = self._since_tensor(since, (N,), dev)
+                w, b = (x.detach().reshape(dT).contiguous()
+                        for x in _encoder_tensors(time_encoder)) if dT else (None, None)
+                self._launch(self._lib.gf_graph_pair_sequence, s.data_ptr(), d.data_ptr(),
+                             t.data_ptr(), _ptr(lo), N, L, *_table(node_feats, dn),
+                             *_table(edge_feats, de), _ptr(w), _ptr(b), dT, lengths.data_ptr(),
+                             nodes.data_ptr(), eids.data_ptr(), times.data_ptr(),
+                             delta_t.data_ptr(), counts.data_ptr(), _ptr(node), _ptr(edge),
+                             _ptr(time))
+        return PairSequence(lengths, nodes, eids, times, delta_t, counts, node, edge, time)
 
     def temporal_random_walk(self, src: torch.Tensor, ts: torch.Tensor, length: int,
                              num_walks: int = 1, *, recency: int = 1, max_history: int = 0,

@@ -1664,6 +1664,61 @@ GF_API int gf_graph_neighbor_sequence(const gf_graph* g, const int64_t* d_nodes,
                                       int64_t* d_out_nodes, int64_t* d_eids, float* d_times,
                                       float* d_delta_t, float* d_tokens, int device, void* stream);
 
+/* Everything DyGFormer concatenates for each of num_rows pairs, finished, from one launch: the
+ * pair reader with features, where gf_graph_neighbor_sequence is the per-node one.  Row i has
+ * source s = d_src[i], destination d = d_dst[i], time t = d_ts[i] and, when d_since is not NULL,
+ * lower end lo = d_since[i]; side 0 is s's sequence, side 1 d's, L = length slots each.  All
+ * outputs are row-major and contiguous, and every element is written:
+ *   d_lengths, d_nodes, d_eids, d_times, d_counts
+ *               gf_graph_neighbor_cooccurrence's at (d_src, d_dst, d_ts, d_since, length,
+ *               include_self = 1), element for element and bit for bit: the self slot is
+ *               position 0 with eid -1 and time t and is counted, the window behind it has the
+ *               bound L - 1, oldest first, the padding is -1, -1, 0, (0, 0)
+ *   d_delta_t   float32 [num_rows, 2, L]   t - d_times[i, side, p], one float32 subtraction, on
+ *               every filled slot, the self slot included (t - t); +0.0 in the padding
+ *   d_node_out  float32 [num_rows, 2, L, dn]        d_node_feats[d_nodes[i, side, p], :]
+ *   d_edge_out  float32 [num_rows, 2, L, de]        d_edge_feats[d_eids[i, side, p], :]
+ *   d_time_out  float32 [num_rows, 2, L, dim_time]  cosf(d_weight[j] * d_delta_t[i, side, p] + d_bias[j])
+ *               on a filled slot, and +0.0 in every element of a padded slot of the three
+ * The table parts are copies of the rows, bit for bit; an id without a row in its table (id < 0
+ * or id >= node_rows / edge_rows) gives a zero part, the rule of gf_graph_neighbor_aggregate: the
+ * self slot has the node's own row in d_node_out and a zero row in d_edge_out.  The time part is
+ * gf_time_encode_cat's expression evaluated by the same code (one multiply, one add, the precise
+ * cosf): it equals that call on d_delta_t bit for bit, the self slot being the encoding of its
+ * own delta.  Each of the three parts is its own tensor and may be absent, as NULL with width 0
+ * (d_weight and d_bias are given together); the output of an absent part is not touched and may
+ * be NULL.  Tables are row-major and contiguous; widths are 1 .. GF_PAIRSEQ_MAX_WIDTH, length is
+ * 2 .. GF_PAIRSEQ_MAX_LENGTH.
+ * One launch on `stream`: gf_graph_neighbor_cooccurrence's geometry, LDS table and phases (a wave
+ * per row up to L = 128, four waves on a row above), the emit writing the six planes; behind it
+ * the row's threads are spread over the flattened (side, position, column) space of each part
+ * (float4 columns where that part's width is a multiple of 4 and its table and output are 16-byte
+ * aligned, scalar columns otherwise, decided per part), one writer per element, plain loads and
+ * stores, no atomics on global memory: the same inputs give the same bits.  Index arithmetic on
+ * [num_rows, 2, L, width] is 64-bit.  d_counts must be 8-byte aligned.  Ordering against
+ * gf_graph_add_edges / gf_graph_offload_old_blocks: as gf_batch_hist_negatives (reads the store's
+ * view NOW).
+ * A NULL graph, length outside [2, GF_PAIRSEQ_MAX_LENGTH], a NULL part with a width other than
+ * 0, a width outside [1, GF_PAIRSEQ_MAX_WIDTH] of a part that is given, only one of d_weight and
+ * d_bias, num_rows >= 2^31, and with num_rows > 0 a NULL d_src, d_dst, d_ts or plane, a
+ * misaligned d_counts, or a NULL output of a part that is given: GF_ERR_INVALID_ARGUMENT, nothing
+ * launched.  num_rows == 0: GF_OK, nothing launched. */
+#define GF_PAIRSEQ_MAX_LENGTH 512
+#define GF_PAIRSEQ_MAX_WIDTH 1024
+GF_API int gf_graph_pair_sequence(const gf_graph* g, const int64_t* d_src, const int64_t* d_dst,
+                                  const float* d_ts,
+                                  const float* d_since /* NULL: no lower end */,
+                                  size_t num_rows, size_t length,
+                                  const float* d_node_feats /* NULL: no node table */,
+                                  size_t node_rows, size_t dn,
+                                  const float* d_edge_feats /* NULL: no edge table */,
+                                  size_t edge_rows, size_t de,
+                                  const float* d_weight /* NULL: no time part */,
+                                  const float* d_bias, size_t dim_time, int32_t* d_lengths,
+                                  int64_t* d_nodes, int64_t* d_eids, float* d_times,
+                                  float* d_delta_t, int32_t* d_counts, float* d_node_out,
+                                  float* d_edge_out, float* d_time_out, int device, void* stream);
+
 /* Backward-in-time random walks over the temporal edge store: W = num_walks walks of L = length
  * steps from each of num_rows roots.  Walk (i, w) starts at v_0 = d_src[i], t_0 = d_ts[i];
  * d_nodes[i, w, 0] = d_src[i] always.  Step j = 0 .. L - 1:
