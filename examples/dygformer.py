@@ -37,7 +37,7 @@ from gnnflow_amd.utils import build_dynamic_graph
 
 
 def main(num_batches=5, eval_batches=2, batch_size=200, negatives=1, length=32, patch_size=1,
-         dim=16, num_edges=20000, seed=0, lr=1e-3, verbose=True):
+         dim=16, num_edges=20000, seed=0, lr=1e-3, verbose=True, fused_patches=False):
     import pandas as pd
     dev = torch.device("cuda", 0)
     g = synthetic.reddit_like(seed=42, num_edges=num_edges)
@@ -49,7 +49,7 @@ def main(num_batches=5, eval_batches=2, batch_size=200, negatives=1, length=32, 
     edge_feats = torch.randn(g["num_edges"], dim).to(dev)
     dsts = torch.from_numpy(np.unique(df["dst"].to_numpy()).astype(np.int64)).to(dev)
     model = DyGFormer(dim, dim, dim_time=dim, channel_dim=dim, patch_size=patch_size,
-                      max_length=length, dim_embed=dim).to(dev)
+                      max_length=length, dim_embed=dim, fused_patches=fused_patches).to(dev)
     optimizer = torch.optim.Adam(model.parameters(), lr=lr)
     criterion = gnnflow_amd.LinkLoss()
     metrics = gnnflow_amd.LinkMetrics(dev)
@@ -110,5 +110,8 @@ if __name__ == "__main__":
     ap.add_argument("--patch", type=int, default=1)
     ap.add_argument("--dim", type=int, default=16)
     ap.add_argument("--edges", type=int, default=20000)
+    ap.add_argument("--fused-patches", action="store_true",
+                    help="project the node, edge and time channels with ops.patch_project")
     a = ap.parse_args()
-    main(a.batches, a.eval_batches, a.batch_size, a.negatives, a.length, a.patch, a.dim, a.edges)
+    main(a.batches, a.eval_batches, a.batch_size, a.negatives, a.length, a.patch, a.dim, a.edges,
+         fused_patches=a.fused_patches)

@@ -296,6 +296,11 @@ PROTOTYPES = {
                                           C.c_int, _p]),
     "gf_time_encode_backward_bf16": (C.c_int, [_p, _p, _p, _sz, _sz, _p, _sz, _sz, _p, _sz, _p, _p,
                                                C.c_int, _p]),
+    "gf_patch_project": (C.c_int, [_p, _p, _sz, _p, _p, _p, _p, _sz, _sz, _sz, _sz, _p, _p, _sz, _p,
+                                   C.c_int, _p]),
+    "gf_patch_project_backward_partial_rows": (C.c_int, [_sz, _sz, _sz, C.POINTER(_sz)]),
+    "gf_patch_project_backward": (C.c_int, [_p, _p, _sz, _p, _p, _p, _p, _sz, _sz, _sz, _sz, _sz,
+                                            _p, _p, _sz, _p, _p, C.c_int, _p]),
     "gf_edge_score": (C.c_int, [_p, _p, _p, _p, _sz, _sz, _sz, _p, C.c_int, _p]),
     "gf_edge_score_bf16": (C.c_int, [_p, _p, _p, _p, _sz, _sz, _sz, _p, C.c_int, _p]),
     "gf_edge_score_backward_partial_rows": (C.c_int, [_sz, C.POINTER(_sz)]),

@@ -5,6 +5,7 @@
 #include "block_ops.hpp"
 #include "capi_handles.hpp"
 #include "partition.hpp"
+#include "patch_project.hpp"
 #include "temporal_walk.hpp"
 
 namespace gf {
@@ -353,6 +354,47 @@ int gf_edge_score_backward_bf16(const uint16_t* d_src, const uint16_t* d_dst, co
     gf::edge_score_bf16_backward(d_src, d_dst, d_w, num_src, num_dst, dim, d_grad_out, d_partials,
                                  partial_rows, d_grad_src, d_grad_dst, d_grad_w, d_grad_bias,
                                  device, as_stream(stream));
+  });
+}
+
+static_assert(GF_PATCH_MAX_LENGTH == gf::kPatchMaxLength && GF_PATCH_MAX_WIDTH == gf::kPatchMaxWidth &&
+                  GF_PATCH_MAX_PATCH_WIDTH == gf::kPatchMaxPatchWidth &&
+                  GF_PATCH_MAX_CHANNELS == gf::kPatchMaxChannels &&
+                  GF_PATCH_MAX_PARTIAL_ROWS == gf::kPatchMaxPartialRows,
+              "gnnflow_hip.h and patch_project.hpp disagree on the limits");
+int gf_patch_project(const int64_t* d_ids, const float* d_table, size_t table_rows,
+                     const float* d_delta_t, const float* d_time_weight,
+                     const float* d_time_bias, const int32_t* d_lengths, size_t num_rows,
+                     size_t length, size_t patch, size_t dim, const float* d_weight,
+                     const float* d_bias, size_t channels, float* d_out, int device,
+                     void* stream) {
+  return guarded([&] {
+    const gf::PatchSource src = {d_ids, d_table, table_rows, d_delta_t, d_time_weight,
+                                 d_time_bias, d_lengths};
+    gf::patch_project_forward(src, num_rows, length, patch, dim, d_weight, d_bias, channels,
+                              d_out, device, as_stream(stream));
+  });
+}
+int gf_patch_project_backward_partial_rows(size_t num_patches, size_t channels,
+                                           size_t patch_width, size_t* rows) {
+  return guarded([&] {
+    GF_REQUIRE(rows != nullptr, "gf_patch_project_backward_partial_rows: null output");
+    *rows = gf::patch_project_backward_partial_rows(num_patches, channels, patch_width);
+  });
+}
+int gf_patch_project_backward(const int64_t* d_ids, const float* d_table, size_t table_rows,
+                              const float* d_delta_t, const float* d_time_weight,
+                              const float* d_time_bias, const int32_t* d_lengths,
+                              size_t num_rows, size_t length, size_t patch, size_t dim,
+                              size_t channels, const float* d_grad_out, float* d_partials,
+                              size_t partial_rows, float* d_grad_weight, float* d_grad_bias,
+                              int device, void* stream) {
+  return guarded([&] {
+    const gf::PatchSource src = {d_ids, d_table, table_rows, d_delta_t, d_time_weight,
+                                 d_time_bias, d_lengths};
+    gf::patch_project_backward(src, num_rows, length, patch, dim, channels, d_grad_out,
+                               d_partials, partial_rows, d_grad_weight, d_grad_bias, device,
+                               as_stream(stream));
   });
 }
 

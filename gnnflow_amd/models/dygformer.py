@@ -6,7 +6,9 @@ channel, concatenated and run through one transformer encoder over both sides' p
 channels come finished from DynamicGraph.pair_sequence(..., node_feats=, edge_feats=,
 time_encoder=model.time_enc) -- one kernel, padding already zero -- into forward_parts; forward
 builds the same parts in torch from ids, time deltas and lengths.  Plain torch modules; the GEMMs
-are torch's."""
+are torch's -- except with fused_patches=True, where the node, edge and time channels are never
+built: ops.patch_project gathers (encodes) their rows and applies proj in one kernel, from the id
+and time planes alone."""
 from typing import Optional
 
 import torch
@@ -62,12 +64,19 @@ class DyGFormer(nn.Module):
         edge_predictor   the link-prediction head; row i pairs src[i] with dst[i]
 
     dim_node == 0 or dim_edge == 0 drops that channel (node_x / edge_x are then ignored).
+
+    fused_patches=True (off by default; README "patch_project" has the measurements) makes
+    forward and forward_graph, on a GPU, take the node and edge channels' patches from
+    ops.patch_project and the time channel's from ops.patch_project_time (with learn_time the
+    time channel stays on the torch route, so that TimeEncode trains); forward_graph then asks
+    pair_sequence for the planes only.  The parameters, the state_dict and forward_parts are the
+    same either way.
     """
 
     def __init__(self, dim_node: int, dim_edge: int, dim_time: int = 100, channel_dim: int = 50,
                  patch_size: int = 1, num_layers: int = 2, num_heads: int = 2,
                  dropout: float = 0.1, max_length: int = 32, dim_embed: int = 100,
-                 learn_time: bool = False):
+                 learn_time: bool = False, fused_patches: bool = False):
         super().__init__()
         for name, value, lo in (("dim_node", dim_node, 0), ("dim_edge", dim_edge, 0),
                                 ("dim_time", dim_time, 1), ("channel_dim", channel_dim, 1),
@@ -88,6 +97,20 @@ class DyGFormer(nn.Module):
         self.dim_node, self.dim_edge, self.dim_time = dim_node, dim_edge, dim_time
         self.channel_dim, self.patch_size, self.max_length = channel_dim, patch_size, max_length
         self.dim_embed, self.learn_time = dim_embed, bool(learn_time)
+        self.fused_patches = bool(fused_patches)      # a route, not state: no parameter or buffer
+        if self.fused_patches:      # ops.patch_project's limits, here and not at the first call
+            fused = [n for n in self.channels if n in ("node", "edge") or
+                     (n == "time" and not learn_time)]
+            wide = [n for n in fused if widths[n] > ops.PATCH_MAX_WIDTH or
+                    patch_size * widths[n] > ops.PATCH_MAX_PATCH_WIDTH]
+            if wide or channel_dim > ops.PATCH_MAX_CHANNELS or max_length > ops.PATCH_MAX_LENGTH:
+                raise ValueError(
+                    "fused_patches takes channels of up to {} columns and patch_size * columns "
+                    "up to {}, channel_dim up to {} and max_length up to {}; got {}, "
+                    "patch_size {}, channel_dim {}, max_length {}".format(
+                        ops.PATCH_MAX_WIDTH, ops.PATCH_MAX_PATCH_WIDTH, ops.PATCH_MAX_CHANNELS,
+                        ops.PATCH_MAX_LENGTH, {n: widths[n] for n in fused}, patch_size,
+                        channel_dim, max_length))
         self.time_enc = TimeEncode(dim_time) if learn_time else FixedTimeEncode(dim_time)
         self.cooc_enc = NeighborCooccurrenceEncoder(channel_dim, max_count=max_length)
         self.proj = nn.ModuleDict({name: nn.Linear(patch_size * widths[name], channel_dim)
@@ -125,6 +148,9 @@ class DyGFormer(nn.Module):
             return_embed: return (emb_src, emb_dst), [N, dim_embed] each, instead of the scores
         """
         self._check_length(delta_t.shape[2])
+        if self.fused_patches and delta_t.is_cuda:
+            return self._forward_fused(nodes, eids, delta_t, counts, lengths, node_feats,
+                                       edge_feats, return_embed)
         padding = self._padding(lengths, delta_t.shape[2])
         node_x = edge_x = None
         if self.dim_node:
@@ -141,7 +167,12 @@ class DyGFormer(nn.Module):
         """forward() on what graph.pair_sequence(src, dst, ts, since=since, length=max_length)
         reads: one launch gives the planes and the finished parts.  With learn_time the reader
         is asked for no time part and the returned delta_t is encoded here, so that the
-        encoder trains; no gradient flows to the tables either way."""
+        encoder trains; no gradient flows to the tables either way.  With fused_patches the
+        reader is asked for the planes alone and forward() projects from them."""
+        if self.fused_patches and src.is_cuda:
+            seq = graph.pair_sequence(src, dst, ts, since=since, length=self.max_length)
+            return self._forward_fused(seq.nodes, seq.eids, seq.delta_t, seq.counts, seq.lengths,
+                                       node_feats, edge_feats, return_embed)
         seq = graph.pair_sequence(
             src, dst, ts, since=since, length=self.max_length,
             node_feats=node_feats if self.dim_node else None,
@@ -152,6 +183,32 @@ class DyGFormer(nn.Module):
             time_x = self._encode_time(seq.delta_t, self._padding(seq.lengths, self.max_length))
         return self.forward_parts(seq.node, seq.edge, time_x, seq.counts, seq.lengths,
                                   return_embed)
+
+    def _forward_fused(self, nodes, eids, delta_t, counts, lengths, node_feats, edge_feats,
+                       return_embed):
+        """forward() without the node, edge and time parts: each of those channels' patches
+        [N, 2, L / P, channel_dim] comes from ops.patch_project(_time) on the planes."""
+        if counts.dim() != 4:
+            raise ValueError("counts must be [N, 2, L, 2], got shape {}".format(
+                tuple(counts.shape)))
+        N, L, P = counts.shape[0], counts.shape[2], self.patch_size
+        self._check_length(L)
+        planes = {"node": (nodes, node_feats), "edge": (eids, edge_feats)}
+        projected = []
+        for name in self.channels:
+            proj = self.proj[name]
+            if name in planes:
+                ids, table = planes[name]
+                projected.append(ops.patch_project(ids, lengths, table, proj.weight, proj.bias, P))
+            elif name == "time" and not self.learn_time:
+                projected.append(ops.patch_project_time(
+                    delta_t, lengths, self.time_enc.weight, self.time_enc.bias, proj.weight,
+                    proj.bias, P))
+            else:
+                x = self.cooc_enc(counts, lengths) if name == "cooc" else \
+                    self._encode_time(delta_t, self._padding(lengths, L))
+                projected.append(proj(x.reshape(N, 2, L // P, P * x.shape[3])))
+        return self._encode_patches(projected, N, L, return_embed)
 
     def forward_parts(self, node_x: Optional[torch.Tensor], edge_x: Optional[torch.Tensor],
                       time_x: torch.Tensor, counts: torch.Tensor, lengths: torch.Tensor,
@@ -179,6 +236,11 @@ class DyGFormer(nn.Module):
                 raise ValueError("the {} part must be [{}, 2, {}, {}], got {}".format(
                     name, N, L, width, tuple(x.shape)))
             projected.append(self.proj[name](x.reshape(N, 2, L // P, P * width)))
+        return self._encode_patches(projected, N, L, return_embed)
+
+    def _encode_patches(self, projected, N: int, L: int, return_embed: bool):
+        """the model behind the channels' projections, [N, 2, L / P, channel_dim] each"""
+        P = self.patch_size
         x = torch.cat(projected, dim=3)                       # [N, 2, L / P, C]
         x = x.reshape(N, 2 * (L // P), x.shape[3])
         for block in self.blocks:

@@ -41,6 +41,13 @@ make on a sampled block, on HIP segment kernels (csrc/block_ops.hip) with autogr
                                            set-based anonymisation (csrc/walk_positions.hip); integers,
                                            no autograd
 
+    patch_project(ids, lengths, table,     DyGFormer's patching and channel Linear (proj[name](x.reshape(
+      weight, bias, P)                     N, 2, L // P, P * d))) straight from the id planes of
+    patch_project_time(delta_t, ...)       DynamicGraph.pair_sequence: rows gathered (time rows encoded)
+                                           into LDS and multiplied on the float32 matrix instructions,
+                                           the [N, 2, L, d] channel never stored
+                                           (csrc/patch_project.hip); float32 only
+
 block_attention, block_reduce, block_max, block_gat, time_encode_cat, edge_score, link_loss,
 gru_cell and dropout_relu_layer_norm also run on bfloat16 (the tensors autocast hands them), by one rule: float32 arithmetic, one rounding on
 store.  Every bfloat16 element is widened to float32 where it is loaded (exact), the arithmetic is
@@ -61,7 +68,8 @@ The ops live in one module per kernel family, split as the csrc/ sources are: bl
 (block_ops.hip), attention.py (block_attention.hip, block_gat.hip), time_encoding.py
 (time_encode.hip; not time_encode.py, which the op of that name would shadow), edge.py
 (edge_score.hip, edge_rank.hip), layer.py (layer_epilogue.hip, gru_cell.hip), link.py
-(link_loss.hip, link_metrics.hip), walks.py (walk_positions.hip); _common.py holds the one path
+(link_loss.hip, link_metrics.hip), walks.py (walk_positions.hip), patch.py
+(patch_project.hip); _common.py holds the one path
 to a native launch and the argument checks they share.  This file only re-exports: callers look
 an op up as an attribute of this package at call time (`ops.block_attention(...)`), which is
 where a replacement of it is seen; nothing binds an op with `from .ops import ...`.
@@ -87,6 +95,9 @@ from .link import (_LINK_METRICS_PARTIAL_WORDS, LINK_LOSS_ACC_FIELDS,
                    LINK_LOSS_MAX_PARTIAL_ROWS, LINK_LOSS_SINGLE_TILES, LINK_LOSS_TILE,
                    LINK_METRICS_MAX_SCORES, LINK_METRICS_TILE, _LinkLoss, link_loss,
                    link_metrics)
+from .patch import (PATCH_MAX_CHANNELS, PATCH_MAX_LENGTH, PATCH_MAX_PARTIAL_ROWS,
+                    PATCH_MAX_PATCH_WIDTH, PATCH_MAX_WIDTH, _PatchProject, patch_project,
+                    patch_project_time)
 from .time_encoding import _time_encode_cat, _TimeEncodeCat, time_encode, time_encode_cat
 from .walks import WALK_MAX_REF_ENTRIES, check_walk_position_counts_args, walk_position_counts
 

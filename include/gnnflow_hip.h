@@ -1038,6 +1038,56 @@ GF_API int gf_edge_score_backward_bf16(const uint16_t* d_src, const uint16_t* d_
                                        uint16_t* d_grad_dst, float* d_grad_w, float* d_grad_bias,
                                        int device, void* stream);
 
+/* Gather + patch projection (DyGFormer's patching and per-channel Linear without the channel
+ * tensor).  With r < num_rows, Q = length / patch patches per row, K = patch * dim and
+ * m = r * Q + q:
+ *   x[r, l, :] = d_table[d_ids[r, l], :]     if l < d_lengths[r] and 0 <= d_ids[r, l] < table_rows
+ *              = cosf(d_time_weight[:] * d_delta_t[r, l] + d_time_bias[:])     (time form, the
+ *                expression of gf_time_encode) if l < d_lengths[r]
+ *              = 0                            otherwise
+ *   out[m, c]  = d_bias[c] + sum_{k < K} x[r, q * patch + k / dim, k % dim] * d_weight[c, k]
+ * x is never stored.  Table form: d_ids int64 [num_rows, length] and d_table fp32 [table_rows,
+ * dim] are given and d_delta_t, d_time_weight, d_time_bias are NULL; time form: d_delta_t fp32
+ * [num_rows, length] and d_time_weight, d_time_bias [dim] are given and d_ids, d_table are NULL.
+ * d_lengths int32 [num_rows] or NULL (every slot filled; a length above `length` counts as
+ * `length`); d_weight fp32 [channels, K], d_bias [channels], d_out [num_rows * Q, channels]; all
+ * row-major and contiguous.  float32 arithmetic on the float32 matrix instructions; the order of
+ * summation depends on the shapes alone, not on the alignment of the table.  1 <= dim <=
+ * GF_PATCH_MAX_WIDTH, 1 <= length <= GF_PATCH_MAX_LENGTH a multiple of patch, patch * dim <=
+ * GF_PATCH_MAX_PATCH_WIDTH, 1 <= channels <= GF_PATCH_MAX_CHANNELS, fewer than 2^31 patches, else
+ * GF_ERR_INVALID_ARGUMENT; num_rows == 0 launches nothing. */
+#define GF_PATCH_MAX_LENGTH 512
+#define GF_PATCH_MAX_WIDTH 1024
+#define GF_PATCH_MAX_PATCH_WIDTH 4096
+#define GF_PATCH_MAX_CHANNELS 128
+#define GF_PATCH_MAX_PARTIAL_ROWS 256
+GF_API int gf_patch_project(const int64_t* d_ids, const float* d_table, size_t table_rows,
+                            const float* d_delta_t, const float* d_time_weight,
+                            const float* d_time_bias, const int32_t* d_lengths, size_t num_rows,
+                            size_t length, size_t patch, size_t dim, const float* d_weight,
+                            const float* d_bias, size_t channels, float* d_out, int device,
+                            void* stream);
+/* Rows of the caller-owned partials buffer gf_patch_project_backward needs for num_patches
+ * patches: the buffer holds rows * channels * (patch_width + 1) floats, patch_width = patch *
+ * dim; at most GF_PATCH_MAX_PARTIAL_ROWS rows and 64 MiB. */
+GF_API int gf_patch_project_backward_partial_rows(size_t num_patches, size_t channels,
+                                                  size_t patch_width, size_t* rows);
+/* Gradients of gf_patch_project's weight and bias from g = d_grad_out [num_rows * Q, channels],
+ * x re-gathered (re-encoded) from the same source arguments:
+ *   grad_weight[c, k] = sum_m g[m, c] * x[r, q * patch + k / dim, k % dim]
+ *   grad_bias[c]      = sum_m g[m, c]
+ * in two launches, summed in a fixed order without atomics (bit-identical from run to run).
+ * Either of d_grad_weight [channels, K], d_grad_bias [channels] may be NULL (skipped); with both
+ * NULL nothing is launched.  The same checks as gf_patch_project. */
+GF_API int gf_patch_project_backward(const int64_t* d_ids, const float* d_table,
+                                     size_t table_rows, const float* d_delta_t,
+                                     const float* d_time_weight, const float* d_time_bias,
+                                     const int32_t* d_lengths, size_t num_rows, size_t length,
+                                     size_t patch, size_t dim, size_t channels,
+                                     const float* d_grad_out, float* d_partials,
+                                     size_t partial_rows, float* d_grad_weight,
+                                     float* d_grad_bias, int device, void* stream);
+
 /* Fused epilogue of the reference's TemporalAttentionLayer (layers.py: layer_norm(relu(dropout(
  * w_out(rst)))), after the GEMM): d_x [num_rows, dim], d_gamma and d_beta [dim], d_out
  * [num_rows, dim], d_mean and d_rstd [num_rows], all fp32, row-major and contiguous.  With p an
