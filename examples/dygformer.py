@@ -19,7 +19,7 @@ REDDIT-shaped data; a usage example, not a benchmark.
 
     python examples/dygformer.py [--batches 5] [--eval-batches 2] [--batch-size 200]
                                  [--negatives 1] [--length 32] [--patch 1] [--dim 16]
-                                 [--edges 20000]
+                                 [--edges 20000] [--fused-patches] [--fused-attention]
 """
 import argparse
 import os
@@ -37,7 +37,8 @@ from gnnflow_amd.utils import build_dynamic_graph
 
 
 def main(num_batches=5, eval_batches=2, batch_size=200, negatives=1, length=32, patch_size=1,
-         dim=16, num_edges=20000, seed=0, lr=1e-3, verbose=True, fused_patches=False):
+         dim=16, num_edges=20000, seed=0, lr=1e-3, verbose=True, fused_patches=False,
+         fused_attention=False):
     import pandas as pd
     dev = torch.device("cuda", 0)
     g = synthetic.reddit_like(seed=42, num_edges=num_edges)
@@ -49,7 +50,8 @@ def main(num_batches=5, eval_batches=2, batch_size=200, negatives=1, length=32, 
     edge_feats = torch.randn(g["num_edges"], dim).to(dev)
     dsts = torch.from_numpy(np.unique(df["dst"].to_numpy()).astype(np.int64)).to(dev)
     model = DyGFormer(dim, dim, dim_time=dim, channel_dim=dim, patch_size=patch_size,
-                      max_length=length, dim_embed=dim, fused_patches=fused_patches).to(dev)
+                      max_length=length, dim_embed=dim, fused_patches=fused_patches,
+                      fused_attention=fused_attention).to(dev)
     optimizer = torch.optim.Adam(model.parameters(), lr=lr)
     criterion = gnnflow_amd.LinkLoss()
     metrics = gnnflow_amd.LinkMetrics(dev)
@@ -112,6 +114,8 @@ if __name__ == "__main__":
     ap.add_argument("--edges", type=int, default=20000)
     ap.add_argument("--fused-patches", action="store_true",
                     help="project the node, edge and time channels with ops.patch_project")
+    ap.add_argument("--fused-attention", action="store_true",
+                    help="run the encoder blocks' self-attention in ops.sequence_attention")
     a = ap.parse_args()
     main(a.batches, a.eval_batches, a.batch_size, a.negatives, a.length, a.patch, a.dim, a.edges,
-         fused_patches=a.fused_patches)
+         fused_patches=a.fused_patches, fused_attention=a.fused_attention)

@@ -6,6 +6,7 @@
 #include "capi_handles.hpp"
 #include "partition.hpp"
 #include "patch_project.hpp"
+#include "sequence_attention.hpp"
 #include "temporal_walk.hpp"
 
 namespace gf {
@@ -395,6 +396,28 @@ int gf_patch_project_backward(const int64_t* d_ids, const float* d_table, size_t
     gf::patch_project_backward(src, num_rows, length, patch, dim, channels, d_grad_out,
                                d_partials, partial_rows, d_grad_weight, d_grad_bias, device,
                                as_stream(stream));
+  });
+}
+
+static_assert(GF_SEQ_ATTENTION_MAX_LENGTH == gf::kSeqAttentionMaxLength &&
+                  GF_SEQ_ATTENTION_MAX_HEAD_DIM == gf::kSeqAttentionMaxHeadDim &&
+                  GF_SEQ_ATTENTION_MAX_WIDTH == gf::kSeqAttentionMaxWidth,
+              "gnnflow_hip.h and sequence_attention.hpp disagree on the limits");
+int gf_sequence_attention(const float* d_qkv, size_t num_rows, size_t length, size_t heads,
+                          size_t head_dim, float p, uint64_t seed, float* d_out, float* d_lse,
+                          int device, void* stream) {
+  return guarded([&] {
+    gf::sequence_attention_forward(d_qkv, num_rows, length, heads, head_dim, p, seed, d_out,
+                                   d_lse, device, as_stream(stream));
+  });
+}
+int gf_sequence_attention_backward(const float* d_qkv, const float* d_lse, size_t num_rows,
+                                   size_t length, size_t heads, size_t head_dim, float p,
+                                   uint64_t seed, const float* d_grad_out, float* d_grad_qkv,
+                                   int device, void* stream) {
+  return guarded([&] {
+    gf::sequence_attention_backward(d_qkv, d_lse, num_rows, length, heads, head_dim, p, seed,
+                                    d_grad_out, d_grad_qkv, device, as_stream(stream));
   });
 }
 

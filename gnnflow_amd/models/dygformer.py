@@ -8,7 +8,8 @@ time_encoder=model.time_enc) -- one kernel, padding already zero -- into forward
 builds the same parts in torch from ids, time deltas and lengths.  Plain torch modules; the GEMMs
 are torch's -- except with fused_patches=True, where the node, edge and time channels are never
 built: ops.patch_project gathers (encodes) their rows and applies proj in one kernel, from the id
-and time planes alone."""
+and time planes alone -- and with fused_attention=True, where the encoder blocks' self-attention
+between in_proj and out_proj is one ops.sequence_attention call."""
 from typing import Optional
 
 import torch
@@ -21,10 +22,20 @@ from ..nn import EdgePredictor, FixedTimeEncode, NeighborCooccurrenceEncoder, Ti
 
 class EncoderBlock(nn.Module):
     """One pre-norm transformer encoder block over x [n, S, C]: x + drop(MHA(LN(x))), then
-    x + drop(W2 drop(gelu(W1 LN(x)))) with a hidden width of 4 C.  No padding mask."""
+    x + drop(W2 drop(gelu(W1 LN(x)))) with a hidden width of 4 C.  No padding mask.
 
-    def __init__(self, dim: int, num_heads: int, dropout: float):
+    fused_attention=True (a route, not state: the same parameters and state_dict) computes the
+    attention of a float32 x on a GPU as out_proj(ops.sequence_attention(in_proj(h), num_heads,
+    p, seed)): p is att.dropout in training and 0 otherwise, the seed is drawn per forward from
+    torch's default CPU generator (no device sync; reproducible under torch.manual_seed, but not
+    the mask torch's own dropout would draw).  Any other x takes the torch route."""
+
+    def __init__(self, dim: int, num_heads: int, dropout: float, fused_attention: bool = False):
         super().__init__()
+        self.fused_attention = bool(fused_attention)
+        if self.fused_attention and dim // num_heads > ops.SEQ_ATTENTION_MAX_HEAD_DIM:
+            raise ValueError("fused_attention takes heads of up to {} columns, got dim {} / "
+                             "num_heads {}".format(ops.SEQ_ATTENTION_MAX_HEAD_DIM, dim, num_heads))
         self.att_norm = nn.LayerNorm(dim)
         self.att = nn.MultiheadAttention(dim, num_heads, dropout=dropout, batch_first=True)
         self.ff_norm = nn.LayerNorm(dim)
@@ -34,7 +45,16 @@ class EncoderBlock(nn.Module):
 
     def forward(self, x):
         h = self.att_norm(x)
-        x = x + self.drop(self.att(h, h, h, need_weights=False)[0])
+        if self.fused_attention and x.is_cuda and x.dtype == torch.float32 and \
+                not torch.is_autocast_enabled():
+            att = self.att
+            p = att.dropout if self.training else 0.0
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64)) if p > 0 else None
+            qkv = F.linear(h, att.in_proj_weight, att.in_proj_bias)
+            a = att.out_proj(ops.sequence_attention(qkv, att.num_heads, p, seed))
+        else:
+            a = self.att(h, h, h, need_weights=False)[0]
+        x = x + self.drop(a)
         return x + self.drop(self.w2(self.drop(F.gelu(self.w1(self.ff_norm(x))))))
 
 
@@ -71,12 +91,17 @@ class DyGFormer(nn.Module):
     time channel stays on the torch route, so that TimeEncode trains); forward_graph then asks
     pair_sequence for the planes only.  The parameters, the state_dict and forward_parts are the
     same either way.
+
+    fused_attention=True (off by default; README "sequence_attention" has the measurements) makes
+    every EncoderBlock take its self-attention from ops.sequence_attention on a GPU, with the
+    attention dropout inside the kernel.  A route too: nothing in the state changes.
     """
 
     def __init__(self, dim_node: int, dim_edge: int, dim_time: int = 100, channel_dim: int = 50,
                  patch_size: int = 1, num_layers: int = 2, num_heads: int = 2,
                  dropout: float = 0.1, max_length: int = 32, dim_embed: int = 100,
-                 learn_time: bool = False, fused_patches: bool = False):
+                 learn_time: bool = False, fused_patches: bool = False,
+                 fused_attention: bool = False):
         super().__init__()
         for name, value, lo in (("dim_node", dim_node, 0), ("dim_edge", dim_edge, 0),
                                 ("dim_time", dim_time, 1), ("channel_dim", channel_dim, 1),
@@ -111,11 +136,19 @@ class DyGFormer(nn.Module):
                         ops.PATCH_MAX_WIDTH, ops.PATCH_MAX_PATCH_WIDTH, ops.PATCH_MAX_CHANNELS,
                         ops.PATCH_MAX_LENGTH, {n: widths[n] for n in fused}, patch_size,
                         channel_dim, max_length))
+        self.fused_attention = bool(fused_attention)
+        if self.fused_attention and (2 * max_length // patch_size > ops.SEQ_ATTENTION_MAX_LENGTH
+                                     or dim // num_heads > ops.SEQ_ATTENTION_MAX_HEAD_DIM):
+            raise ValueError(
+                "fused_attention takes sequences of up to {} patches and heads of up to {} "
+                "columns; got 2 * max_length / patch_size = {} and dim / num_heads = {}".format(
+                    ops.SEQ_ATTENTION_MAX_LENGTH, ops.SEQ_ATTENTION_MAX_HEAD_DIM,
+                    2 * max_length // patch_size, dim // num_heads))
         self.time_enc = TimeEncode(dim_time) if learn_time else FixedTimeEncode(dim_time)
         self.cooc_enc = NeighborCooccurrenceEncoder(channel_dim, max_count=max_length)
         self.proj = nn.ModuleDict({name: nn.Linear(patch_size * widths[name], channel_dim)
                                    for name in self.channels})
-        self.blocks = nn.ModuleList(EncoderBlock(dim, num_heads, dropout)
+        self.blocks = nn.ModuleList(EncoderBlock(dim, num_heads, dropout, self.fused_attention)
                                     for _ in range(num_layers))
         self.out_fc = nn.Linear(dim, dim_embed)
         self.edge_predictor = EdgePredictor(dim_embed)

@@ -47,6 +47,11 @@ make on a sampled block, on HIP segment kernels (csrc/block_ops.hip) with autogr
                                            into LDS and multiplied on the float32 matrix instructions,
                                            the [N, 2, L, d] channel never stored
                                            (csrc/patch_project.hip); float32 only
+    sequence_attention(qkv, num_heads)     the self-attention of DyGFormer's EncoderBlock between in_proj
+      ... dropout_p=, dropout_seed=        and out_proj, from the packed in_proj rows: one workgroup per
+                                           (row, head), both products on the float32 matrix instructions,
+                                           the [S, S] weights and the Philox dropout mask never stored
+                                           (csrc/sequence_attention.hip); float32 only, S and dh <= 128
 
 block_attention, block_reduce, block_max, block_gat, time_encode_cat, edge_score, link_loss,
 gru_cell and dropout_relu_layer_norm also run on bfloat16 (the tensors autocast hands them), by one rule: float32 arithmetic, one rounding on
@@ -69,7 +74,7 @@ The ops live in one module per kernel family, split as the csrc/ sources are: bl
 (time_encode.hip; not time_encode.py, which the op of that name would shadow), edge.py
 (edge_score.hip, edge_rank.hip), layer.py (layer_epilogue.hip, gru_cell.hip), link.py
 (link_loss.hip, link_metrics.hip), walks.py (walk_positions.hip), patch.py
-(patch_project.hip); _common.py holds the one path
+(patch_project.hip), sequence.py (sequence_attention.hip); _common.py holds the one path
 to a native launch and the argument checks they share.  This file only re-exports: callers look
 an op up as an attribute of this package at call time (`ops.block_attention(...)`), which is
 where a replacement of it is seen; nothing binds an op with `from .ops import ...`.
@@ -98,6 +103,8 @@ from .link import (_LINK_METRICS_PARTIAL_WORDS, LINK_LOSS_ACC_FIELDS,
 from .patch import (PATCH_MAX_CHANNELS, PATCH_MAX_LENGTH, PATCH_MAX_PARTIAL_ROWS,
                     PATCH_MAX_PATCH_WIDTH, PATCH_MAX_WIDTH, _PatchProject, patch_project,
                     patch_project_time)
+from .sequence import (SEQ_ATTENTION_MAX_HEAD_DIM, SEQ_ATTENTION_MAX_LENGTH,
+                       SEQ_ATTENTION_MAX_WIDTH, _SequenceAttention, sequence_attention)
 from .time_encoding import _time_encode_cat, _TimeEncodeCat, time_encode, time_encode_cat
 from .walks import WALK_MAX_REF_ENTRIES, check_walk_position_counts_args, walk_position_counts
 

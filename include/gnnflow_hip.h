@@ -1088,6 +1088,38 @@ GF_API int gf_patch_project_backward(const int64_t* d_ids, const float* d_table,
                                      size_t partial_rows, float* d_grad_weight,
                                      float* d_grad_bias, int device, void* stream);
 
+/* Unmasked multi-head self-attention over short sequences (DyGFormer's encoder block behind
+ * in_proj).  d_qkv fp32 [num_rows, length, 3 * heads * head_dim], the last dimension [q | k | v],
+ * each [heads, head_dim] (torch's nn.MultiheadAttention in_proj layout, read in place); d_out fp32
+ * [num_rows, length, heads * head_dim]; d_lse fp32 [num_rows, heads, length]; row-major and
+ * contiguous.  With S = length, sc = 1 / sqrtf(head_dim), p an fp32 value in [0, 1),
+ * T = (uint32_t)((double)p * 4294967296.0):
+ *   s[r,h,i,j]   = (sum_c q[r,i,h,c] * k[r,j,h,c]) * sc
+ *   a[r,h,i,:]   = softmax_j(s[r,h,i,:])          lse[r,h,i] = log(sum_j exp(s[r,h,i,j]))
+ *   keep         = gf_philox4x32_10_first(seed, ((r * heads + h) * S + i) * S + j, 0) >= T
+ *   w            = keep ? 1.0f / (1.0f - p) : 0       p == 0: w = 1, seed unused
+ *   out[r,i,h,:] = sum_j (a * w)[r,h,i,j] * v[r,j,h,:]
+ * in one launch, one workgroup per (row, head), float32 arithmetic on the float32 matrix
+ * instructions; s, a and the mask are never stored.  The bits depend on the shapes alone, not on
+ * the alignment of the pointers.  1 <= length <= GF_SEQ_ATTENTION_MAX_LENGTH, 1 <= head_dim <=
+ * GF_SEQ_ATTENTION_MAX_HEAD_DIM, heads * head_dim <= GF_SEQ_ATTENTION_MAX_WIDTH, num_rows * heads
+ * < 2^31, else GF_ERR_INVALID_ARGUMENT; num_rows == 0 launches nothing. */
+#define GF_SEQ_ATTENTION_MAX_LENGTH 128
+#define GF_SEQ_ATTENTION_MAX_HEAD_DIM 128
+#define GF_SEQ_ATTENTION_MAX_WIDTH 1024
+GF_API int gf_sequence_attention(const float* d_qkv, size_t num_rows, size_t length, size_t heads,
+                                 size_t head_dim, float p, uint64_t seed, float* d_out,
+                                 float* d_lse, int device, void* stream);
+/* d_grad_qkv [num_rows, length, 3 * heads * head_dim] from d_grad_out [num_rows, length, heads *
+ * head_dim]: a recomputed as exp(s - lse), the mask drawn again from (p, seed),
+ *   dV = (a w)^T dO    dA = (dO V^T) w    dS = a (dA - sum_j a dA)    dQ = dS K sc    dK = dS^T Q sc
+ * in one launch; every element has one writer, so nothing is atomic and the same inputs give the
+ * same bits.  The same checks. */
+GF_API int gf_sequence_attention_backward(const float* d_qkv, const float* d_lse, size_t num_rows,
+                                          size_t length, size_t heads, size_t head_dim, float p,
+                                          uint64_t seed, const float* d_grad_out,
+                                          float* d_grad_qkv, int device, void* stream);
+
 /* Fused epilogue of the reference's TemporalAttentionLayer (layers.py: layer_norm(relu(dropout(
  * w_out(rst)))), after the GEMM): d_x [num_rows, dim], d_gamma and d_beta [dim], d_out
  * [num_rows, dim], d_mean and d_rstd [num_rows], all fp32, row-major and contiguous.  With p an
