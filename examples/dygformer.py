@@ -20,6 +20,7 @@ REDDIT-shaped data; a usage example, not a benchmark.
     python examples/dygformer.py [--batches 5] [--eval-batches 2] [--batch-size 200]
                                  [--negatives 1] [--length 32] [--patch 1] [--dim 16]
                                  [--edges 20000] [--fused-patches] [--fused-attention]
+                                 [--fused-feed-forward]
 """
 import argparse
 import os
@@ -38,7 +39,7 @@ from gnnflow_amd.utils import build_dynamic_graph
 
 def main(num_batches=5, eval_batches=2, batch_size=200, negatives=1, length=32, patch_size=1,
          dim=16, num_edges=20000, seed=0, lr=1e-3, verbose=True, fused_patches=False,
-         fused_attention=False):
+         fused_attention=False, fused_feed_forward=False):
     import pandas as pd
     dev = torch.device("cuda", 0)
     g = synthetic.reddit_like(seed=42, num_edges=num_edges)
@@ -51,7 +52,8 @@ def main(num_batches=5, eval_batches=2, batch_size=200, negatives=1, length=32, 
     dsts = torch.from_numpy(np.unique(df["dst"].to_numpy()).astype(np.int64)).to(dev)
     model = DyGFormer(dim, dim, dim_time=dim, channel_dim=dim, patch_size=patch_size,
                       max_length=length, dim_embed=dim, fused_patches=fused_patches,
-                      fused_attention=fused_attention).to(dev)
+                      fused_attention=fused_attention,
+                      fused_feed_forward=fused_feed_forward).to(dev)
     optimizer = torch.optim.Adam(model.parameters(), lr=lr)
     criterion = gnnflow_amd.LinkLoss()
     metrics = gnnflow_amd.LinkMetrics(dev)
@@ -116,6 +118,9 @@ if __name__ == "__main__":
                     help="project the node, edge and time channels with ops.patch_project")
     ap.add_argument("--fused-attention", action="store_true",
                     help="run the encoder blocks' self-attention in ops.sequence_attention")
+    ap.add_argument("--fused-feed-forward", action="store_true",
+                    help="run the encoder blocks' feed-forward in ops.feed_forward")
     a = ap.parse_args()
     main(a.batches, a.eval_batches, a.batch_size, a.negatives, a.length, a.patch, a.dim, a.edges,
-         fused_patches=a.fused_patches, fused_attention=a.fused_attention)
+         fused_patches=a.fused_patches, fused_attention=a.fused_attention,
+         fused_feed_forward=a.fused_feed_forward)

@@ -17,7 +17,7 @@ loss is `nn.LinkLoss`, the metrics `LinkMetrics`; nothing waits for the GPU unti
 `compute()` calls at the end.  Synthetic REDDIT-shaped data; a usage example, not a benchmark.
 
     python examples/graphmixer.py [--batches 5] [--batch-size 200] [--tokens 32] [--history 64]
-                                  [--dim 16] [--edges 20000]
+                                  [--dim 16] [--edges 20000] [--fused-feed-forward]
 """
 import argparse
 import os
@@ -35,7 +35,7 @@ from gnnflow_amd.utils import build_dynamic_graph
 
 
 def main(num_batches=5, batch_size=200, num_tokens=32, max_history=64, dim=16, num_edges=20000,
-         seed=0, lr=1e-3, verbose=True):
+         seed=0, lr=1e-3, verbose=True, fused_feed_forward=False):
     import pandas as pd
     dev = torch.device("cuda", 0)
     g = synthetic.reddit_like(seed=42, num_edges=num_edges)
@@ -47,7 +47,8 @@ def main(num_batches=5, batch_size=200, num_tokens=32, max_history=64, dim=16, n
     edge_feats = torch.randn(g["num_edges"], dim).to(dev)
     dsts = torch.from_numpy(np.unique(df["dst"].to_numpy()).astype(np.int64)).to(dev)
     K = num_tokens
-    model = GraphMixer(dim, dim, dim_time=dim, dim_embed=dim, num_tokens=K).to(dev)
+    model = GraphMixer(dim, dim, dim_time=dim, dim_embed=dim, num_tokens=K,
+                       fused_feed_forward=fused_feed_forward).to(dev)
     optimizer = torch.optim.Adam(model.parameters(), lr=lr)
     criterion = gnnflow_amd.LinkLoss()
     metrics = gnnflow_amd.LinkMetrics(dev)
@@ -103,5 +104,8 @@ if __name__ == "__main__":
     ap.add_argument("--history", type=int, default=64)
     ap.add_argument("--dim", type=int, default=16)
     ap.add_argument("--edges", type=int, default=20000)
+    ap.add_argument("--fused-feed-forward", action="store_true",
+                    help="run the mixer blocks' channel MLP in ops.feed_forward")
     a = ap.parse_args()
-    main(a.batches, a.batch_size, a.tokens, a.history, a.dim, a.edges)
+    main(a.batches, a.batch_size, a.tokens, a.history, a.dim, a.edges,
+         fused_feed_forward=a.fused_feed_forward)

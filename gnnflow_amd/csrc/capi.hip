@@ -4,6 +4,7 @@
 #include "batch_stream.hpp"
 #include "block_ops.hpp"
 #include "capi_handles.hpp"
+#include "feed_forward.hpp"
 #include "partition.hpp"
 #include "patch_project.hpp"
 #include "sequence_attention.hpp"
@@ -418,6 +419,37 @@ int gf_sequence_attention_backward(const float* d_qkv, const float* d_lse, size_
   return guarded([&] {
     gf::sequence_attention_backward(d_qkv, d_lse, num_rows, length, heads, head_dim, p, seed,
                                     d_grad_out, d_grad_qkv, device, as_stream(stream));
+  });
+}
+
+static_assert(GF_FEED_FORWARD_MAX_WIDTH == gf::kFeedForwardMaxWidth &&
+                  GF_FEED_FORWARD_MAX_PARTIAL_ROWS == gf::kFeedForwardMaxPartialRows,
+              "gnnflow_hip.h and feed_forward.hpp disagree on the limits");
+int gf_feed_forward(const float* d_x, const float* d_w1, const float* d_b1, const float* d_w2,
+                    const float* d_b2, size_t num_rows, size_t width, size_t hidden, float p,
+                    uint64_t seed, float* d_y, int device, void* stream) {
+  return guarded([&] {
+    gf::feed_forward_forward(d_x, d_w1, d_b1, d_w2, d_b2, num_rows, width, hidden, p, seed, d_y,
+                             device, as_stream(stream));
+  });
+}
+int gf_feed_forward_backward_partial_rows(size_t num_rows, size_t width, size_t hidden,
+                                          size_t* rows) {
+  return guarded([&] {
+    GF_REQUIRE(rows != nullptr, "gf_feed_forward_backward_partial_rows: null output");
+    *rows = gf::feed_forward_backward_partial_rows(num_rows, width, hidden);
+  });
+}
+int gf_feed_forward_backward(const float* d_x, const float* d_w1, const float* d_b1,
+                             const float* d_w2, size_t num_rows, size_t width, size_t hidden,
+                             float p, uint64_t seed, const float* d_grad_y, float* d_partials,
+                             size_t partial_rows, float* d_grad_x, float* d_grad_w1,
+                             float* d_grad_b1, float* d_grad_w2, float* d_grad_b2, int device,
+                             void* stream) {
+  return guarded([&] {
+    gf::feed_forward_backward(d_x, d_w1, d_b1, d_w2, num_rows, width, hidden, p, seed, d_grad_y,
+                              d_partials, partial_rows, d_grad_x, d_grad_w1, d_grad_b1, d_grad_w2,
+                              d_grad_b2, device, as_stream(stream));
   });
 }
 

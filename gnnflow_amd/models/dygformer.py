@@ -9,7 +9,9 @@ builds the same parts in torch from ids, time deltas and lengths.  Plain torch m
 are torch's -- except with fused_patches=True, where the node, edge and time channels are never
 built: ops.patch_project gathers (encodes) their rows and applies proj in one kernel, from the id
 and time planes alone -- and with fused_attention=True, where the encoder blocks' self-attention
-between in_proj and out_proj is one ops.sequence_attention call."""
+between in_proj and out_proj is one ops.sequence_attention call -- and with
+fused_feed_forward=True, where the blocks' Linear-GELU-dropout-Linear is one ops.feed_forward
+call."""
 from typing import Optional
 
 import torch
@@ -28,11 +30,22 @@ class EncoderBlock(nn.Module):
     attention of a float32 x on a GPU as out_proj(ops.sequence_attention(in_proj(h), num_heads,
     p, seed)): p is att.dropout in training and 0 otherwise, the seed is drawn per forward from
     torch's default CPU generator (no device sync; reproducible under torch.manual_seed, but not
-    the mask torch's own dropout would draw).  Any other x takes the torch route."""
+    the mask torch's own dropout would draw).  Any other x takes the torch route.
 
-    def __init__(self, dim: int, num_heads: int, dropout: float, fused_attention: bool = False):
+    fused_feed_forward=True (a route too) makes the second residual of such an x
+    x + drop(ops.feed_forward(ff_norm(x), w1.weight, w1.bias, w2.weight, w2.bias, p, seed)), with
+    p = drop.p in training and 0 otherwise and a seed drawn the same way: the inner dropout is
+    inside the kernel and the [n, S, 4 C] hidden tensors are never stored; LayerNorm, the outer
+    dropout and the residual stay in torch."""
+
+    def __init__(self, dim: int, num_heads: int, dropout: float, fused_attention: bool = False,
+                 fused_feed_forward: bool = False):
         super().__init__()
         self.fused_attention = bool(fused_attention)
+        self.fused_feed_forward = bool(fused_feed_forward)
+        if self.fused_feed_forward and dim > ops.FEED_FORWARD_MAX_WIDTH:
+            raise ValueError("fused_feed_forward takes a dim of up to {}, got {}".format(
+                ops.FEED_FORWARD_MAX_WIDTH, dim))
         if self.fused_attention and dim // num_heads > ops.SEQ_ATTENTION_MAX_HEAD_DIM:
             raise ValueError("fused_attention takes heads of up to {} columns, got dim {} / "
                              "num_heads {}".format(ops.SEQ_ATTENTION_MAX_HEAD_DIM, dim, num_heads))
@@ -43,18 +56,27 @@ class EncoderBlock(nn.Module):
         self.w2 = nn.Linear(4 * dim, dim)
         self.drop = nn.Dropout(dropout)
 
+    @staticmethod
+    def _seed(p):
+        return int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64)) if p > 0 else None
+
     def forward(self, x):
         h = self.att_norm(x)
-        if self.fused_attention and x.is_cuda and x.dtype == torch.float32 and \
-                not torch.is_autocast_enabled():
+        fusable = x.is_cuda and x.dtype == torch.float32 and not torch.is_autocast_enabled()
+        if self.fused_attention and fusable:
             att = self.att
             p = att.dropout if self.training else 0.0
-            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64)) if p > 0 else None
+            seed = self._seed(p)
             qkv = F.linear(h, att.in_proj_weight, att.in_proj_bias)
             a = att.out_proj(ops.sequence_attention(qkv, att.num_heads, p, seed))
         else:
             a = self.att(h, h, h, need_weights=False)[0]
         x = x + self.drop(a)
+        if self.fused_feed_forward and fusable:
+            p = self.drop.p if self.training else 0.0
+            return x + self.drop(ops.feed_forward(
+                self.ff_norm(x).contiguous(), self.w1.weight, self.w1.bias, self.w2.weight,
+                self.w2.bias, p, self._seed(p)))
         return x + self.drop(self.w2(self.drop(F.gelu(self.w1(self.ff_norm(x))))))
 
 
@@ -95,13 +117,17 @@ class DyGFormer(nn.Module):
     fused_attention=True (off by default; README "sequence_attention" has the measurements) makes
     every EncoderBlock take its self-attention from ops.sequence_attention on a GPU, with the
     attention dropout inside the kernel.  A route too: nothing in the state changes.
+
+    fused_feed_forward=True (off by default; README "feed_forward" has the measurements) makes
+    every EncoderBlock take its feed-forward from ops.feed_forward on a GPU, with the inner
+    dropout inside the kernel and no [N, S, 4 C] tensor stored.  A route as well.
     """
 
     def __init__(self, dim_node: int, dim_edge: int, dim_time: int = 100, channel_dim: int = 50,
                  patch_size: int = 1, num_layers: int = 2, num_heads: int = 2,
                  dropout: float = 0.1, max_length: int = 32, dim_embed: int = 100,
                  learn_time: bool = False, fused_patches: bool = False,
-                 fused_attention: bool = False):
+                 fused_attention: bool = False, fused_feed_forward: bool = False):
         super().__init__()
         for name, value, lo in (("dim_node", dim_node, 0), ("dim_edge", dim_edge, 0),
                                 ("dim_time", dim_time, 1), ("channel_dim", channel_dim, 1),
@@ -144,11 +170,17 @@ class DyGFormer(nn.Module):
                 "columns; got 2 * max_length / patch_size = {} and dim / num_heads = {}".format(
                     ops.SEQ_ATTENTION_MAX_LENGTH, ops.SEQ_ATTENTION_MAX_HEAD_DIM,
                     2 * max_length // patch_size, dim // num_heads))
+        self.fused_feed_forward = bool(fused_feed_forward)
+        if self.fused_feed_forward and dim > ops.FEED_FORWARD_MAX_WIDTH:
+            raise ValueError(
+                "fused_feed_forward takes up to {} columns; got {} channels of channel_dim "
+                "{}".format(ops.FEED_FORWARD_MAX_WIDTH, len(self.channels), channel_dim))
         self.time_enc = TimeEncode(dim_time) if learn_time else FixedTimeEncode(dim_time)
         self.cooc_enc = NeighborCooccurrenceEncoder(channel_dim, max_count=max_length)
         self.proj = nn.ModuleDict({name: nn.Linear(patch_size * widths[name], channel_dim)
                                    for name in self.channels})
-        self.blocks = nn.ModuleList(EncoderBlock(dim, num_heads, dropout, self.fused_attention)
+        self.blocks = nn.ModuleList(EncoderBlock(dim, num_heads, dropout, self.fused_attention,
+                                                 self.fused_feed_forward)
                                     for _ in range(num_layers))
         self.out_fc = nn.Linear(dim, dim_embed)
         self.edge_predictor = EdgePredictor(dim_embed)

@@ -4,39 +4,60 @@ over a node's newest K interactions, the node encoder is the node's own features
 the features of the nodes it met (DynamicGraph.neighbor_aggregate).  The link encoder's tokens
 come finished from DynamicGraph.neighbor_sequence(..., edge_feats=, time_encoder=model.time_enc)
 -- one kernel, padding already zero -- into forward_tokens; forward builds the same tokens in
-torch from edge features, time deltas and lengths.  Plain torch modules; the GEMMs are torch's."""
+torch from edge features, time deltas and lengths.  Plain torch modules; the GEMMs are torch's --
+except with fused_feed_forward=True, where each mixer block's channel MLP is one ops.feed_forward
+call."""
 from typing import Optional
 
 import torch
 import torch.nn as nn
 
+from .. import ops
 from ..nn import EdgePredictor, FixedTimeEncode
 
 
 class _FeedForward(nn.Module):
-    """Linear -> GELU -> dropout -> Linear -> dropout over the last dimension."""
+    """Linear -> GELU -> dropout -> Linear -> dropout over the last dimension.
 
-    def __init__(self, dim: int, expansion: float, dropout: float):
+    fused=True (a route, not state: the same parameters and state_dict keys) takes everything but
+    the trailing dropout of a float32 x on a GPU, outside autocast, from ops.feed_forward: the
+    inner Dropout's p in training and 0 otherwise, the seed drawn per forward from torch's
+    default CPU generator (no device sync).  Any other x takes the torch route."""
+
+    def __init__(self, dim: int, expansion: float, dropout: float, fused: bool = False):
         super().__init__()
         hidden = max(1, int(expansion * dim))
+        self.fused = bool(fused)
+        if self.fused and dim > ops.FEED_FORWARD_MAX_WIDTH:
+            raise ValueError("fused_feed_forward takes a width of up to {}, got {}".format(
+                ops.FEED_FORWARD_MAX_WIDTH, dim))
         self.net = nn.Sequential(nn.Linear(dim, hidden), nn.GELU(), nn.Dropout(dropout),
                                  nn.Linear(hidden, dim), nn.Dropout(dropout))
 
     def forward(self, x):
+        if self.fused and x.is_cuda and x.dtype == torch.float32 and \
+                not torch.is_autocast_enabled():
+            w1, _, drop, w2, last = self.net
+            p = drop.p if self.training else 0.0
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64)) if p > 0 else None
+            return last(ops.feed_forward(x.contiguous(), w1.weight, w1.bias, w2.weight, w2.bias,
+                                         p, seed))
         return self.net(x)
 
 
 class MixerBlock(nn.Module):
     """One MLP-Mixer block over x [n, K, C]: x + token MLP over K of LayerNorm(x), then
-    x + channel MLP over C of LayerNorm(x)."""
+    x + channel MLP over C of LayerNorm(x).  fused_feed_forward=True routes the channel MLP
+    through ops.feed_forward; the token MLP over the transposed [n, C, K] view (K tokens, a
+    hidden width of K / 2) is not routed: it stays in torch."""
 
     def __init__(self, num_tokens: int, dim: int, token_expansion: float,
-                 channel_expansion: float, dropout: float):
+                 channel_expansion: float, dropout: float, fused_feed_forward: bool = False):
         super().__init__()
         self.token_norm = nn.LayerNorm(dim)
         self.token_mlp = _FeedForward(num_tokens, token_expansion, dropout)
         self.channel_norm = nn.LayerNorm(dim)
-        self.channel_mlp = _FeedForward(dim, channel_expansion, dropout)
+        self.channel_mlp = _FeedForward(dim, channel_expansion, dropout, fused_feed_forward)
 
     def forward(self, x):
         x = x + self.token_mlp(self.token_norm(x).transpose(1, 2)).transpose(1, 2)
@@ -61,18 +82,26 @@ class GraphMixer(nn.Module):
     The padded slots are replaced, not multiplied: whatever they hold (NaN too) leaves the result
     unchanged.  dim_node == 0 drops the node part (node_x and nbr_mean are then ignored), and
     dim_edge == 0 leaves the time encoding as the token (edge_x is then ignored).
+
+    fused_feed_forward=True (off by default; README "feed_forward" has the measurements) takes
+    every mixer block's channel MLP from ops.feed_forward on a GPU, the [n, K, 4 C] hidden
+    tensors never stored.  A route, not state: the parameters and the state_dict are the same.
+    The token MLP is not routed.  dim_embed may then be at most ops.FEED_FORWARD_MAX_WIDTH.
     """
 
     def __init__(self, dim_node: int, dim_edge: int, dim_time: int = 100, dim_embed: int = 100,
                  num_tokens: int = 32, num_layers: int = 2, token_expansion: float = 0.5,
-                 channel_expansion: float = 4.0, dropout: float = 0.1):
+                 channel_expansion: float = 4.0, dropout: float = 0.1,
+                 fused_feed_forward: bool = False):
         super().__init__()
+        self.fused_feed_forward = bool(fused_feed_forward)
         self.dim_node, self.dim_edge, self.dim_time = dim_node, dim_edge, dim_time
         self.dim_embed, self.num_tokens, self.num_layers = dim_embed, num_tokens, num_layers
         self.time_enc = FixedTimeEncode(dim_time)
         self.link_in = nn.Linear(dim_edge + dim_time, dim_embed)
         self.mixers = nn.ModuleList(
-            MixerBlock(num_tokens, dim_embed, token_expansion, channel_expansion, dropout)
+            MixerBlock(num_tokens, dim_embed, token_expansion, channel_expansion, dropout,
+                       self.fused_feed_forward)
             for _ in range(num_layers))
         self.out_fc = nn.Linear(dim_embed + dim_node, dim_embed)
         self.edge_predictor = EdgePredictor(dim_embed)

@@ -52,6 +52,12 @@ make on a sampled block, on HIP segment kernels (csrc/block_ops.hip) with autogr
                                            (row, head), both products on the float32 matrix instructions,
                                            the [S, S] weights and the Philox dropout mask never stored
                                            (csrc/sequence_attention.hip); float32 only, S and dh <= 128
+    feed_forward(x, w1, b1, w2, b2)        w2(drop(gelu(w1(x)))), the feed-forward of DyGFormer's
+      ... dropout_p=, dropout_seed=        EncoderBlock and GraphMixer's channel MLP: two chained GEMMs on
+                                           the float32 matrix instructions per pass, the [M, Hd] hidden
+                                           activation and its Philox dropout mask never stored, u
+                                           recomputed in the backward (csrc/feed_forward.hip); float32
+                                           only, C <= 256
 
 block_attention, block_reduce, block_max, block_gat, time_encode_cat, edge_score, link_loss,
 gru_cell and dropout_relu_layer_norm also run on bfloat16 (the tensors autocast hands them), by one rule: float32 arithmetic, one rounding on
@@ -74,7 +80,8 @@ The ops live in one module per kernel family, split as the csrc/ sources are: bl
 (time_encode.hip; not time_encode.py, which the op of that name would shadow), edge.py
 (edge_score.hip, edge_rank.hip), layer.py (layer_epilogue.hip, gru_cell.hip), link.py
 (link_loss.hip, link_metrics.hip), walks.py (walk_positions.hip), patch.py
-(patch_project.hip), sequence.py (sequence_attention.hip); _common.py holds the one path
+(patch_project.hip), sequence.py (sequence_attention.hip), feed_forward.py (feed_forward.hip; the
+op of that name replaces the module as this package's attribute); _common.py holds the one path
 to a native launch and the argument checks they share.  This file only re-exports: callers look
 an op up as an attribute of this package at call time (`ops.block_attention(...)`), which is
 where a replacement of it is seen; nothing binds an op with `from .ops import ...`.
@@ -94,6 +101,7 @@ from .attention import (MAX_ATTENTION_WIDTH, _BlockAttention, _BlockGat, _NoEdge
 from .block import (_BlockMax, _BlockReduce, _EdgeSoftmax, _src_dtype, block_max, block_reduce,
                     edge_softmax)
 from .edge import EDGE_RANK_CHUNK, EDGE_RANK_MAX_K, EdgeRank, _EdgeScore, edge_rank, edge_score
+from .feed_forward import FEED_FORWARD_MAX_WIDTH, _FeedForward, feed_forward
 from .layer import (LAYER_EPILOGUE_MAX_WIDTH, _DropoutReluLayerNorm, _GruCell,
                     dropout_relu_layer_norm, gru_cell)
 from .link import (_LINK_METRICS_PARTIAL_WORDS, LINK_LOSS_ACC_FIELDS,

@@ -1120,6 +1120,48 @@ GF_API int gf_sequence_attention_backward(const float* d_qkv, const float* d_lse
                                           uint64_t seed, const float* d_grad_out,
                                           float* d_grad_qkv, int device, void* stream);
 
+/* The feed-forward of a transformer block (DyGFormer's EncoderBlock, GraphMixer's channel MLP):
+ * two nn.Linear around GELU and dropout in one launch, the hidden activation never stored.  d_x
+ * fp32 [num_rows, width], d_w1 [hidden, width], d_b1 [hidden], d_w2 [width, hidden], d_b2 [width],
+ * d_y [num_rows, width]; row-major and contiguous.  With p an fp32 value in [0, 1),
+ * T = (uint32_t)((double)p * 4294967296.0):
+ *   u[m,j] = b1[j] + sum_c x[m,c] * w1[j,c]
+ *   g[m,j] = 0.5 * u * (1 + erff(u / sqrt 2))
+ *   w[m,j] = gf_philox4x32_10_first(seed, m * hidden + j, 0) >= T ? 1.0f / (1.0f - p) : 0
+ *            p == 0: w = 1, seed unused
+ *   y[m,c] = b2[c] + sum_j (g * w)[m,j] * w2[c,j]
+ * float32 arithmetic on the float32 matrix instructions; u, g and the mask are never stored.  The
+ * bits depend on the shapes alone, not on the alignment of the pointers.  1 <= width <=
+ * GF_FEED_FORWARD_MAX_WIDTH, 1 <= hidden < 2^36, num_rows <= 2^36 and num_rows * hidden <= 2^63,
+ * else GF_ERR_INVALID_ARGUMENT; num_rows == 0 launches nothing. */
+#define GF_FEED_FORWARD_MAX_WIDTH 256
+#define GF_FEED_FORWARD_MAX_PARTIAL_ROWS 256
+GF_API int gf_feed_forward(const float* d_x, const float* d_w1, const float* d_b1,
+                           const float* d_w2, const float* d_b2, size_t num_rows, size_t width,
+                           size_t hidden, float p, uint64_t seed, float* d_y, int device,
+                           void* stream);
+/* Rows of the caller-owned partials buffer gf_feed_forward_backward needs when a weight or bias
+ * gradient is wanted: the buffer holds rows * (2 * hidden * width + hidden + width) floats; at
+ * most GF_FEED_FORWARD_MAX_PARTIAL_ROWS rows and 64 MiB (one row at the least). */
+GF_API int gf_feed_forward_backward_partial_rows(size_t num_rows, size_t width, size_t hidden,
+                                                 size_t* rows);
+/* Gradients of gf_feed_forward from dy = d_grad_y [num_rows, width], u recomputed from x and the
+ * mask drawn again from (p, seed):
+ *   dh = dy w2    du = dh * w * (0.5 * (1 + erff(u / sqrt 2)) + u * expf(-u * u / 2) / sqrt(2 pi))
+ *   grad_x = du w1    grad_w1 = du^T x    grad_b1 = colsum du    grad_w2 = dy^T (g * w)
+ *   grad_b2 = colsum dy
+ * Any of the five outputs may be NULL (skipped).  grad_x takes one launch; the other four take
+ * one launch into d_partials and one that sums its rows in ascending order, and none when all
+ * four are NULL (d_partials may then be NULL).  Every element has one writer, nothing is atomic,
+ * the same inputs give the same bits.  The same checks. */
+GF_API int gf_feed_forward_backward(const float* d_x, const float* d_w1, const float* d_b1,
+                                    const float* d_w2, size_t num_rows, size_t width,
+                                    size_t hidden, float p, uint64_t seed,
+                                    const float* d_grad_y, float* d_partials,
+                                    size_t partial_rows, float* d_grad_x, float* d_grad_w1,
+                                    float* d_grad_b1, float* d_grad_w2, float* d_grad_b2,
+                                    int device, void* stream);
+
 /* Fused epilogue of the reference's TemporalAttentionLayer (layers.py: layer_norm(relu(dropout(
  * w_out(rst)))), after the GEMM): d_x [num_rows, dim], d_gamma and d_beta [dim], d_out
  * [num_rows, dim], d_mean and d_rstd [num_rows], all fp32, row-major and contiguous.  With p an
