@@ -18,6 +18,7 @@ loss is `nn.LinkLoss`, the metrics `LinkMetrics`; nothing waits for the GPU unti
 
     python examples/graphmixer.py [--batches 5] [--batch-size 200] [--tokens 32] [--history 64]
                                   [--dim 16] [--edges 20000] [--fused-feed-forward]
+                                  [--fused-token-mix]
 """
 import argparse
 import os
@@ -35,7 +36,8 @@ from gnnflow_amd.utils import build_dynamic_graph
 
 
 def main(num_batches=5, batch_size=200, num_tokens=32, max_history=64, dim=16, num_edges=20000,
-         seed=0, lr=1e-3, verbose=True, fused_feed_forward=False):
+         seed=0, lr=1e-3, verbose=True, fused_feed_forward=False,
+         fused_token_mix=False):
     import pandas as pd
     dev = torch.device("cuda", 0)
     g = synthetic.reddit_like(seed=42, num_edges=num_edges)
@@ -48,7 +50,8 @@ def main(num_batches=5, batch_size=200, num_tokens=32, max_history=64, dim=16, n
     dsts = torch.from_numpy(np.unique(df["dst"].to_numpy()).astype(np.int64)).to(dev)
     K = num_tokens
     model = GraphMixer(dim, dim, dim_time=dim, dim_embed=dim, num_tokens=K,
-                       fused_feed_forward=fused_feed_forward).to(dev)
+                       fused_feed_forward=fused_feed_forward,
+                       fused_token_mix=fused_token_mix).to(dev)
     optimizer = torch.optim.Adam(model.parameters(), lr=lr)
     criterion = gnnflow_amd.LinkLoss()
     metrics = gnnflow_amd.LinkMetrics(dev)
@@ -106,6 +109,8 @@ if __name__ == "__main__":
     ap.add_argument("--edges", type=int, default=20000)
     ap.add_argument("--fused-feed-forward", action="store_true",
                     help="run the mixer blocks' channel MLP in ops.feed_forward")
+    ap.add_argument("--fused-token-mix", action="store_true",
+                    help="run the mixer blocks' token half in ops.token_mix")
     a = ap.parse_args()
     main(a.batches, a.batch_size, a.tokens, a.history, a.dim, a.edges,
-         fused_feed_forward=a.fused_feed_forward)
+         fused_feed_forward=a.fused_feed_forward, fused_token_mix=a.fused_token_mix)

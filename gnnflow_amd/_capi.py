@@ -310,6 +310,12 @@ PROTOTYPES = {
     "gf_feed_forward_backward_partial_rows": (C.c_int, [_sz, _sz, _sz, C.POINTER(_sz)]),
     "gf_feed_forward_backward": (C.c_int, [_p, _p, _p, _p, _sz, _sz, _sz, C.c_float, C.c_uint64,
                                            _p, _p, _sz, _p, _p, _p, _p, _p, C.c_int, _p]),
+    "gf_token_mix": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _sz, _sz, _sz, _sz, C.c_float,
+                               C.c_float, C.c_uint64, _p, _p, _p, C.c_int, _p]),
+    "gf_token_mix_backward_partial_rows": (C.c_int, [_sz, _sz, _sz, _sz, C.POINTER(_sz)]),
+    "gf_token_mix_backward": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _sz, _sz, _sz, _sz,
+                                        C.c_float, C.c_uint64, _p, _p, _sz, _p, _p, _p, _p, _p, _p,
+                                        _p, C.c_int, _p]),
     "gf_edge_score": (C.c_int, [_p, _p, _p, _p, _sz, _sz, _sz, _p, C.c_int, _p]),
     "gf_edge_score_bf16": (C.c_int, [_p, _p, _p, _p, _sz, _sz, _sz, _p, C.c_int, _p]),
     "gf_edge_score_backward_partial_rows": (C.c_int, [_sz, C.POINTER(_sz)]),

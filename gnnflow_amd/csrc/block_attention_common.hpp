@@ -77,6 +77,15 @@ __device__ inline bool kept(const Dropout& dr, uint64_t edge, uint32_t H, uint32
   return gf_philox4x32_10_first(dr.seed, edge * H + h, 0) >= dr.threshold;
 }
 
+// torch's default GELU and its derivative (feed_forward.hip, token_mix.hip)
+constexpr float kRsqrt2 = 0.70710678118654752440f;
+constexpr float kRsqrt2Pi = 0.39894228040143267794f;
+
+__device__ __forceinline__ float gelu(float u) { return 0.5f * u * (1.f + erff(u * kRsqrt2)); }
+__device__ __forceinline__ float gelu_grad(float u) {
+  return 0.5f * (1.f + erff(u * kRsqrt2)) + u * expf(-0.5f * u * u) * kRsqrt2Pi;
+}
+
 struct Shape {
   const int64_t* offsets;
   uint64_t items;

@@ -5,6 +5,7 @@
 #include "block_ops.hpp"
 #include "capi_handles.hpp"
 #include "feed_forward.hpp"
+#include "token_mix.hpp"
 #include "partition.hpp"
 #include "patch_project.hpp"
 #include "sequence_attention.hpp"
@@ -450,6 +451,42 @@ int gf_feed_forward_backward(const float* d_x, const float* d_w1, const float* d
     gf::feed_forward_backward(d_x, d_w1, d_b1, d_w2, num_rows, width, hidden, p, seed, d_grad_y,
                               d_partials, partial_rows, d_grad_x, d_grad_w1, d_grad_b1, d_grad_w2,
                               d_grad_b2, device, as_stream(stream));
+  });
+}
+
+static_assert(GF_TOKEN_MIX_MAX_TOKENS == gf::kTokenMixMaxTokens &&
+                  GF_TOKEN_MIX_MAX_WIDTH == gf::kTokenMixMaxWidth &&
+                  GF_TOKEN_MIX_MAX_PARTIAL_ROWS == gf::kTokenMixMaxPartialRows,
+              "gnnflow_hip.h and token_mix.hpp disagree on the limits");
+int gf_token_mix(const float* d_x, const float* d_gamma, const float* d_beta, const float* d_w1,
+                 const float* d_b1, const float* d_w2, const float* d_b2, size_t num_rows,
+                 size_t tokens, size_t hidden, size_t width, float eps, float p, uint64_t seed,
+                 float* d_y, float* d_mean, float* d_rstd, int device, void* stream) {
+  return guarded([&] {
+    gf::token_mix_forward(d_x, d_gamma, d_beta, d_w1, d_b1, d_w2, d_b2, num_rows, tokens, hidden,
+                          width, eps, p, seed, d_y, d_mean, d_rstd, device, as_stream(stream));
+  });
+}
+int gf_token_mix_backward_partial_rows(size_t num_rows, size_t tokens, size_t hidden,
+                                       size_t width, size_t* rows) {
+  return guarded([&] {
+    GF_REQUIRE(rows != nullptr, "gf_token_mix_backward_partial_rows: null output");
+    *rows = gf::token_mix_backward_partial_rows(num_rows, tokens, hidden, width);
+  });
+}
+int gf_token_mix_backward(const float* d_x, const float* d_gamma, const float* d_beta,
+                          const float* d_w1, const float* d_b1, const float* d_w2,
+                          const float* d_mean, const float* d_rstd, size_t num_rows,
+                          size_t tokens, size_t hidden, size_t width, float p, uint64_t seed,
+                          const float* d_grad_y, float* d_partials, size_t partial_rows,
+                          float* d_grad_x, float* d_grad_gamma, float* d_grad_beta,
+                          float* d_grad_w1, float* d_grad_b1, float* d_grad_w2, float* d_grad_b2,
+                          int device, void* stream) {
+  return guarded([&] {
+    gf::token_mix_backward(d_x, d_gamma, d_beta, d_w1, d_b1, d_w2, d_mean, d_rstd, num_rows,
+                           tokens, hidden, width, p, seed, d_grad_y, d_partials, partial_rows,
+                           d_grad_x, d_grad_gamma, d_grad_beta, d_grad_w1, d_grad_b1, d_grad_w2,
+                           d_grad_b2, device, as_stream(stream));
   });
 }
 

@@ -185,14 +185,6 @@ __device__ __forceinline__ void hidden_grad(const Geometry& g, const Lane& ln,
   }
 }
 
-constexpr float kRsqrt2 = 0.70710678118654752440f;
-constexpr float kRsqrt2Pi = 0.39894228040143267794f;
-
-__device__ __forceinline__ float gelu(float u) { return 0.5f * u * (1.f + erff(u * kRsqrt2)); }
-__device__ __forceinline__ float gelu_grad(float u) {
-  return 0.5f * (1.f + erff(u * kRsqrt2)) + u * expf(-0.5f * u * u) * kRsqrt2Pi;
-}
-
 template <bool DROP>
 __device__ __forceinline__ float weight_of(const Dropout& dr, uint64_t counter) {
   if (!DROP) return 1.f;

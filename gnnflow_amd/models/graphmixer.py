@@ -6,7 +6,7 @@ come finished from DynamicGraph.neighbor_sequence(..., edge_feats=, time_encoder
 -- one kernel, padding already zero -- into forward_tokens; forward builds the same tokens in
 torch from edge features, time deltas and lengths.  Plain torch modules; the GEMMs are torch's --
 except with fused_feed_forward=True, where each mixer block's channel MLP is one ops.feed_forward
-call."""
+call, and with fused_token_mix=True, where its token half is one ops.token_mix call."""
 from typing import Optional
 
 import torch
@@ -48,19 +48,41 @@ class _FeedForward(nn.Module):
 class MixerBlock(nn.Module):
     """One MLP-Mixer block over x [n, K, C]: x + token MLP over K of LayerNorm(x), then
     x + channel MLP over C of LayerNorm(x).  fused_feed_forward=True routes the channel MLP
-    through ops.feed_forward; the token MLP over the transposed [n, C, K] view (K tokens, a
-    hidden width of K / 2) is not routed: it stays in torch."""
+    through ops.feed_forward.  fused_token_mix=True (a route too, independent of the other: the
+    same parameters and state_dict keys) takes the whole first line -- token_norm, the token MLP
+    over the K tokens with its hidden width of K / 2, both dropouts and the residual -- of a
+    float32 x on a GPU, outside autocast, from ops.token_mix, without the transposed [n, C, K]
+    copy: the token Dropout's p in training and 0 otherwise, the seed drawn per forward from
+    torch's default CPU generator (no device sync).  Any other x takes the torch route.  With both
+    flags a block is two native calls and one LayerNorm."""
 
     def __init__(self, num_tokens: int, dim: int, token_expansion: float,
-                 channel_expansion: float, dropout: float, fused_feed_forward: bool = False):
+                 channel_expansion: float, dropout: float, fused_feed_forward: bool = False,
+                 fused_token_mix: bool = False):
         super().__init__()
+        self.fused_token_mix = bool(fused_token_mix)
+        hidden = max(1, int(token_expansion * num_tokens))
+        if self.fused_token_mix and max(num_tokens, hidden) > ops.TOKEN_MIX_MAX_TOKENS:
+            raise ValueError("fused_token_mix takes up to {} tokens and hidden units, got {} and "
+                             "{}".format(ops.TOKEN_MIX_MAX_TOKENS, num_tokens, hidden))
+        if self.fused_token_mix and dim > ops.TOKEN_MIX_MAX_WIDTH:
+            raise ValueError("fused_token_mix takes a width of up to {}, got {}".format(
+                ops.TOKEN_MIX_MAX_WIDTH, dim))
         self.token_norm = nn.LayerNorm(dim)
         self.token_mlp = _FeedForward(num_tokens, token_expansion, dropout)
         self.channel_norm = nn.LayerNorm(dim)
         self.channel_mlp = _FeedForward(dim, channel_expansion, dropout, fused_feed_forward)
 
     def forward(self, x):
-        x = x + self.token_mlp(self.token_norm(x).transpose(1, 2)).transpose(1, 2)
+        if self.fused_token_mix and x.is_cuda and x.dtype == torch.float32 and \
+                not torch.is_autocast_enabled():
+            w1, _, drop, w2, _ = self.token_mlp.net
+            p = drop.p if self.training else 0.0
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64)) if p > 0 else None
+            x = ops.token_mix(x.contiguous(), self.token_norm.weight, self.token_norm.bias,
+                              w1.weight, w1.bias, w2.weight, w2.bias, self.token_norm.eps, p, seed)
+        else:
+            x = x + self.token_mlp(self.token_norm(x).transpose(1, 2)).transpose(1, 2)
         return x + self.channel_mlp(self.channel_norm(x))
 
 
@@ -86,22 +108,29 @@ class GraphMixer(nn.Module):
     fused_feed_forward=True (off by default; README "feed_forward" has the measurements) takes
     every mixer block's channel MLP from ops.feed_forward on a GPU, the [n, K, 4 C] hidden
     tensors never stored.  A route, not state: the parameters and the state_dict are the same.
-    The token MLP is not routed.  dim_embed may then be at most ops.FEED_FORWARD_MAX_WIDTH.
+    dim_embed may then be at most ops.FEED_FORWARD_MAX_WIDTH.
+
+    fused_token_mix=True (off by default, independent of the other flag; README "token_mix" has
+    the measurements) takes every mixer block's token half -- LayerNorm, the MLP over the K
+    tokens, both dropouts and the residual -- from ops.token_mix on a GPU, with no transposed
+    copy and no [n, C, K / 2] hidden tensor.  A route too.  num_tokens and its hidden width may
+    then be at most ops.TOKEN_MIX_MAX_TOKENS, dim_embed at most ops.TOKEN_MIX_MAX_WIDTH.
     """
 
     def __init__(self, dim_node: int, dim_edge: int, dim_time: int = 100, dim_embed: int = 100,
                  num_tokens: int = 32, num_layers: int = 2, token_expansion: float = 0.5,
                  channel_expansion: float = 4.0, dropout: float = 0.1,
-                 fused_feed_forward: bool = False):
+                 fused_feed_forward: bool = False, fused_token_mix: bool = False):
         super().__init__()
         self.fused_feed_forward = bool(fused_feed_forward)
+        self.fused_token_mix = bool(fused_token_mix)
         self.dim_node, self.dim_edge, self.dim_time = dim_node, dim_edge, dim_time
         self.dim_embed, self.num_tokens, self.num_layers = dim_embed, num_tokens, num_layers
         self.time_enc = FixedTimeEncode(dim_time)
         self.link_in = nn.Linear(dim_edge + dim_time, dim_embed)
         self.mixers = nn.ModuleList(
             MixerBlock(num_tokens, dim_embed, token_expansion, channel_expansion, dropout,
-                       self.fused_feed_forward)
+                       self.fused_feed_forward, self.fused_token_mix)
             for _ in range(num_layers))
         self.out_fc = nn.Linear(dim_embed + dim_node, dim_embed)
         self.edge_predictor = EdgePredictor(dim_embed)

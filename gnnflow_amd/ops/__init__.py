@@ -58,6 +58,13 @@ make on a sampled block, on HIP segment kernels (csrc/block_ops.hip) with autogr
                                            activation and its Philox dropout mask never stored, u
                                            recomputed in the backward (csrc/feed_forward.hip); float32
                                            only, C <= 256
+    token_mix(x, gamma, beta, w1, b1,      x + token_mlp(token_norm(x).transpose(1, 2)).transpose(1, 2),
+      w2, b2)                              the token half of GraphMixer's MixerBlock, on x [N, K, C] as
+      ... dropout_p=, dropout_seed=        it lies: LayerNorm over C, two GEMMs over the token axis on the
+                                           float32 matrix instructions with GELU and both Philox
+                                           dropouts, and the residual, one launch each way; no
+                                           transposed copy and nothing of x's size stored besides y
+                                           (csrc/token_mix.hip); float32 only, K and Kh <= 64, C <= 256
 
 block_attention, block_reduce, block_max, block_gat, time_encode_cat, edge_score, link_loss,
 gru_cell and dropout_relu_layer_norm also run on bfloat16 (the tensors autocast hands them), by one rule: float32 arithmetic, one rounding on
@@ -81,7 +88,8 @@ The ops live in one module per kernel family, split as the csrc/ sources are: bl
 (edge_score.hip, edge_rank.hip), layer.py (layer_epilogue.hip, gru_cell.hip), link.py
 (link_loss.hip, link_metrics.hip), walks.py (walk_positions.hip), patch.py
 (patch_project.hip), sequence.py (sequence_attention.hip), feed_forward.py (feed_forward.hip; the
-op of that name replaces the module as this package's attribute); _common.py holds the one path
+op of that name replaces the module as this package's attribute), token_mix.py (token_mix.hip,
+likewise); _common.py holds the one path
 to a native launch and the argument checks they share.  This file only re-exports: callers look
 an op up as an attribute of this package at call time (`ops.block_attention(...)`), which is
 where a replacement of it is seen; nothing binds an op with `from .ops import ...`.
@@ -113,6 +121,7 @@ from .patch import (PATCH_MAX_CHANNELS, PATCH_MAX_LENGTH, PATCH_MAX_PARTIAL_ROWS
                     patch_project_time)
 from .sequence import (SEQ_ATTENTION_MAX_HEAD_DIM, SEQ_ATTENTION_MAX_LENGTH,
                        SEQ_ATTENTION_MAX_WIDTH, _SequenceAttention, sequence_attention)
+from .token_mix import TOKEN_MIX_MAX_TOKENS, TOKEN_MIX_MAX_WIDTH, _TokenMix, token_mix
 from .time_encoding import _time_encode_cat, _TimeEncodeCat, time_encode, time_encode_cat
 from .walks import WALK_MAX_REF_ENTRIES, check_walk_position_counts_args, walk_position_counts
 

@@ -1162,6 +1162,60 @@ GF_API int gf_feed_forward_backward(const float* d_x, const float* d_w1, const f
                                     float* d_grad_b1, float* d_grad_w2, float* d_grad_b2,
                                     int device, void* stream);
 
+/* The token-mixing half of GraphMixer's MixerBlock, x + token_mlp(LayerNorm(x)^T)^T, in one
+ * launch with no transposed copy.  d_x and d_y fp32 [num_rows, tokens, width], d_gamma and d_beta
+ * [width], d_w1 [hidden, tokens], d_b1 [hidden], d_w2 [tokens, hidden], d_b2 [tokens], d_mean and
+ * d_rstd [num_rows, tokens]; row-major and contiguous.  With n < num_rows, k < tokens = K, j <
+ * hidden = Kh, c < width = C, p an fp32 value in [0, 1), T = (uint32_t)((double)p * 4294967296.0):
+ *   mean[n,k] = sum_c x[n,k,c] / C      var[n,k] = sum_c (x - mean)^2 / C
+ *   rstd[n,k] = 1 / sqrtf(var + eps)    xh = (x - mean) * rstd    z[n,k,c] = xh * gamma[c] + beta[c]
+ *   u[n,j,c]  = b1[j] + sum_k w1[j,k] * z[n,k,c]
+ *   h[n,j,c]  = 0.5 * u * (1 + erff(u / sqrt 2)) * m1[n,j,c]
+ *   t[n,k,c]  = b2[k] + sum_j w2[k,j] * h[n,j,c]
+ *   y[n,k,c]  = x[n,k,c] + t * m2[n,k,c]
+ *   m1 = gf_philox4x32_10_first(seed, (n * C + c) * Kh + j, 0) >= T ? 1.0f / (1.0f - p) : 0
+ *   m2 = gf_philox4x32_10_first(seed, (n * C + c) * K  + k, 1) >= T ? 1.0f / (1.0f - p) : 0
+ *        p == 0: m1 = m2 = 1, seed unused
+ * float32 arithmetic, the two products on the float32 matrix instructions; z, u, h, t and the
+ * masks are never stored.  d_mean and d_rstd are what the backward needs besides the inputs.  The
+ * bits depend on the shapes alone, not on the alignment of the pointers.  1 <= tokens, hidden <=
+ * GF_TOKEN_MIX_MAX_TOKENS, 1 <= width <= GF_TOKEN_MIX_MAX_WIDTH, num_rows * width * max(tokens,
+ * hidden) < 2^63, eps > 0 and finite, else GF_ERR_INVALID_ARGUMENT; num_rows == 0 launches
+ * nothing. */
+#define GF_TOKEN_MIX_MAX_TOKENS 64
+#define GF_TOKEN_MIX_MAX_WIDTH 256
+#define GF_TOKEN_MIX_MAX_PARTIAL_ROWS 512
+GF_API int gf_token_mix(const float* d_x, const float* d_gamma, const float* d_beta,
+                        const float* d_w1, const float* d_b1, const float* d_w2,
+                        const float* d_b2, size_t num_rows, size_t tokens, size_t hidden,
+                        size_t width, float eps, float p, uint64_t seed, float* d_y,
+                        float* d_mean, float* d_rstd, int device, void* stream);
+/* Rows of the caller-owned partials buffer gf_token_mix_backward needs when a parameter gradient
+ * is wanted, one per workgroup: the buffer holds rows * (2 * tokens * hidden + tokens + hidden + 2
+ * * width) floats; at most GF_TOKEN_MIX_MAX_PARTIAL_ROWS rows and 64 MiB (one row at the least). */
+GF_API int gf_token_mix_backward_partial_rows(size_t num_rows, size_t tokens, size_t hidden,
+                                              size_t width, size_t* rows);
+/* Gradients of gf_token_mix from dy = d_grad_y [num_rows, tokens, width], with z, u, h recomputed
+ * from x, mean and rstd and both masks drawn again from (p, seed):
+ *   dt = dy * m2    dh = w2^T dt    du = dh * m1 * g'(u)    dz = w1^T du    a = dz * gamma
+ *   g'(u) = 0.5 * (1 + erff(u / sqrt 2)) + u * expf(-u * u / 2) / sqrt(2 pi)
+ *   grad_x = dy + rstd * (a - mean_c a - xh * mean_c (a * xh))
+ *   grad_w2 = sum_{n,c} dt h^T    grad_b2 = sum_{n,c} dt    grad_w1 = sum_{n,c} du z^T
+ *   grad_b1 = sum_{n,c} du    grad_gamma = sum_{n,k} dz * xh    grad_beta = sum_{n,k} dz
+ * Any of the seven outputs may be NULL (skipped).  One launch writes grad_x and, when one of the
+ * other six is wanted, one partial row per workgroup into d_partials; a second sums the rows in
+ * ascending order.  With all six NULL neither the partial rows nor the second launch are made and
+ * d_partials may be NULL.  Every element has one writer, nothing is atomic, the same inputs give
+ * the same bits.  The same checks. */
+GF_API int gf_token_mix_backward(const float* d_x, const float* d_gamma, const float* d_beta,
+                                 const float* d_w1, const float* d_b1, const float* d_w2,
+                                 const float* d_mean, const float* d_rstd, size_t num_rows,
+                                 size_t tokens, size_t hidden, size_t width, float p,
+                                 uint64_t seed, const float* d_grad_y, float* d_partials,
+                                 size_t partial_rows, float* d_grad_x, float* d_grad_gamma,
+                                 float* d_grad_beta, float* d_grad_w1, float* d_grad_b1,
+                                 float* d_grad_w2, float* d_grad_b2, int device, void* stream);
+
 /* Fused epilogue of the reference's TemporalAttentionLayer (layers.py: layer_norm(relu(dropout(
  * w_out(rst)))), after the GEMM): d_x [num_rows, dim], d_gamma and d_beta [dim], d_out
  * [num_rows, dim], d_mean and d_rstd [num_rows], all fp32, row-major and contiguous.  With p an
