@@ -20,7 +20,7 @@ REDDIT-shaped data; a usage example, not a benchmark.
     python examples/dygformer.py [--batches 5] [--eval-batches 2] [--batch-size 200]
                                  [--negatives 1] [--length 32] [--patch 1] [--dim 16]
                                  [--edges 20000] [--fused-patches] [--fused-attention]
-                                 [--fused-feed-forward]
+                                 [--fused-feed-forward [bfloat16]]
 """
 import argparse
 import os
@@ -118,8 +118,10 @@ if __name__ == "__main__":
                     help="project the node, edge and time channels with ops.patch_project")
     ap.add_argument("--fused-attention", action="store_true",
                     help="run the encoder blocks' self-attention in ops.sequence_attention")
-    ap.add_argument("--fused-feed-forward", action="store_true",
-                    help="run the encoder blocks' feed-forward in ops.feed_forward")
+    ap.add_argument("--fused-feed-forward", nargs="?", const=True, default=False,
+                    choices=["bfloat16"],
+                    help="run the encoder blocks' feed-forward in ops.feed_forward; "
+                         "'--fused-feed-forward bfloat16' on its bfloat16 matrix-core kernels")
     a = ap.parse_args()
     main(a.batches, a.eval_batches, a.batch_size, a.negatives, a.length, a.patch, a.dim, a.edges,
          fused_patches=a.fused_patches, fused_attention=a.fused_attention,

@@ -17,7 +17,7 @@ loss is `nn.LinkLoss`, the metrics `LinkMetrics`; nothing waits for the GPU unti
 `compute()` calls at the end.  Synthetic REDDIT-shaped data; a usage example, not a benchmark.
 
     python examples/graphmixer.py [--batches 5] [--batch-size 200] [--tokens 32] [--history 64]
-                                  [--dim 16] [--edges 20000] [--fused-feed-forward]
+                                  [--dim 16] [--edges 20000] [--fused-feed-forward [bfloat16]]
                                   [--fused-token-mix]
 """
 import argparse
@@ -107,8 +107,10 @@ if __name__ == "__main__":
     ap.add_argument("--history", type=int, default=64)
     ap.add_argument("--dim", type=int, default=16)
     ap.add_argument("--edges", type=int, default=20000)
-    ap.add_argument("--fused-feed-forward", action="store_true",
-                    help="run the mixer blocks' channel MLP in ops.feed_forward")
+    ap.add_argument("--fused-feed-forward", nargs="?", const=True, default=False,
+                    choices=["bfloat16"],
+                    help="run the mixer blocks' channel MLP in ops.feed_forward; "
+                         "'--fused-feed-forward bfloat16' on its bfloat16 matrix-core kernels")
     ap.add_argument("--fused-token-mix", action="store_true",
                     help="run the mixer blocks' token half in ops.token_mix")
     a = ap.parse_args()

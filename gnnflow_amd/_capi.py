@@ -310,7 +310,14 @@ PROTOTYPES = {
     "gf_feed_forward_backward_partial_rows": (C.c_int, [_sz, _sz, _sz, C.POINTER(_sz)]),
     "gf_feed_forward_backward": (C.c_int, [_p, _p, _p, _p, _sz, _sz, _sz, C.c_float, C.c_uint64,
                                            _p, _p, _sz, _p, _p, _p, _p, _p, C.c_int, _p]),
-    "gf_token_mix": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _sz, _sz, _sz, _sz, C.c_float,
+    "gf_feed_forward_bf16_workspace": (C.c_int, [_sz, _sz, C.c_int, C.POINTER(_sz)]),
+    "gf_feed_forward_bf16": (C.c_int, [_p, _p, _p, _p, _p, _sz, _sz, _sz, C.c_float, C.c_uint64,
+                                       _p, _sz, _p, C.c_int, _p]),
+    "gf_feed_forward_bf16_backward_partial_rows": (C.c_int, [_sz, _sz, _sz, C.POINTER(_sz)]),
+    "gf_feed_forward_bf16_backward": (C.c_int, [_p, _p, _p, _p, _sz, _sz, _sz, C.c_float,
+                                                C.c_uint64, _p, _p, _sz, _p, _sz, _p, _p, _p, _p,
+                                                _p, C.c_int, _p]),
+    "gf_token_mix":(C.c_int, [_p, _p, _p, _p, _p, _p, _p, _sz, _sz, _sz, _sz, C.c_float,
                                C.c_float, C.c_uint64, _p, _p, _p, C.c_int, _p]),
     "gf_token_mix_backward_partial_rows": (C.c_int, [_sz, _sz, _sz, _sz, C.POINTER(_sz)]),
     "gf_token_mix_backward": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _sz, _sz, _sz, _sz,

@@ -453,6 +453,42 @@ int gf_feed_forward_backward(const float* d_x, const float* d_w1, const float* d
                               d_grad_b2, device, as_stream(stream));
   });
 }
+int gf_feed_forward_bf16_workspace(size_t width, size_t hidden, int backward, size_t* bytes) {
+  return guarded([&] {
+    GF_REQUIRE(bytes != nullptr, "gf_feed_forward_bf16_workspace: null output");
+    *bytes = gf::feed_forward_bf16_workspace(width, hidden, backward != 0);
+  });
+}
+int gf_feed_forward_bf16(const float* d_x, const float* d_w1, const float* d_b1,
+                         const float* d_w2, const float* d_b2, size_t num_rows, size_t width,
+                         size_t hidden, float p, uint64_t seed, void* d_workspace,
+                         size_t workspace_bytes, float* d_y, int device, void* stream) {
+  return guarded([&] {
+    gf::feed_forward_bf16_forward(d_x, d_w1, d_b1, d_w2, d_b2, num_rows, width, hidden, p, seed,
+                                  d_workspace, workspace_bytes, d_y, device, as_stream(stream));
+  });
+}
+int gf_feed_forward_bf16_backward_partial_rows(size_t num_rows, size_t width, size_t hidden,
+                                               size_t* rows) {
+  return guarded([&] {
+    GF_REQUIRE(rows != nullptr, "gf_feed_forward_bf16_backward_partial_rows: null output");
+    *rows = gf::feed_forward_bf16_backward_partial_rows(num_rows, width, hidden);
+  });
+}
+int gf_feed_forward_bf16_backward(const float* d_x, const float* d_w1, const float* d_b1,
+                                  const float* d_w2, size_t num_rows, size_t width, size_t hidden,
+                                  float p, uint64_t seed, const float* d_grad_y,
+                                  void* d_workspace, size_t workspace_bytes, float* d_partials,
+                                  size_t partial_rows, float* d_grad_x, float* d_grad_w1,
+                                  float* d_grad_b1, float* d_grad_w2, float* d_grad_b2,
+                                  int device, void* stream) {
+  return guarded([&] {
+    gf::feed_forward_bf16_backward(d_x, d_w1, d_b1, d_w2, num_rows, width, hidden, p, seed,
+                                   d_grad_y, d_workspace, workspace_bytes, d_partials,
+                                   partial_rows, d_grad_x, d_grad_w1, d_grad_b1, d_grad_w2,
+                                   d_grad_b2, device, as_stream(stream));
+  });
+}
 
 static_assert(GF_TOKEN_MIX_MAX_TOKENS == gf::kTokenMixMaxTokens &&
                   GF_TOKEN_MIX_MAX_WIDTH == gf::kTokenMixMaxWidth &&

@@ -38,4 +38,36 @@ void feed_forward_backward(const float* d_x, const float* d_w1, const float* d_b
                            float* d_grad_b1, float* d_grad_w2, float* d_grad_b2, int device,
                            hipStream_t stream);
 
+// ---- feed_forward_bf16.hip: the same op with both products of every pass on
+// v_mfma_f32_16x16x32_bf16.  The interface stays float32; x, dy, w1, w2, the hidden activation and
+// du are rounded to bfloat16 where they become matrix operands, the sums are float32 (the
+// definition: include/gnnflow_hip.h, gf_feed_forward_bf16).
+
+// Bytes of the caller-owned workspace a call packs bf(w1) and bf(w2) into, every orientation its
+// passes read zero-padded to multiples of 64: two arrays for the forward ([Hd][C] of w1, [C][Hd]
+// of w2), three for the backward ([Hd][C] and [C][Hd] of w1, [Hd][C] of w2), 2 * round64(hidden) *
+// round64(width) bytes each.
+size_t feed_forward_bf16_workspace(size_t width, size_t hidden, bool backward);
+
+// feed_forward_forward's contract; a pack launch into d_workspace (16-byte aligned, at least
+// feed_forward_bf16_workspace(width, hidden, false) bytes) and the forward launch.
+void feed_forward_bf16_forward(const float* d_x, const float* d_w1, const float* d_b1,
+                               const float* d_w2, const float* d_b2, size_t num_rows,
+                               size_t width, size_t hidden, float p, uint64_t seed,
+                               void* d_workspace, size_t workspace_bytes, float* d_y, int device,
+                               hipStream_t stream);
+
+// feed_forward_backward_partial_rows' contract and row size, for the bfloat16 weight pass.
+size_t feed_forward_bf16_backward_partial_rows(size_t num_rows, size_t width, size_t hidden);
+
+// feed_forward_backward's contract; a pack launch into d_workspace (at least
+// feed_forward_bf16_workspace(width, hidden, true) bytes) goes first.
+void feed_forward_bf16_backward(const float* d_x, const float* d_w1, const float* d_b1,
+                                const float* d_w2, size_t num_rows, size_t width, size_t hidden,
+                                float p, uint64_t seed, const float* d_grad_y, void* d_workspace,
+                                size_t workspace_bytes, float* d_partials, size_t partial_rows,
+                                float* d_grad_x, float* d_grad_w1, float* d_grad_b1,
+                                float* d_grad_w2, float* d_grad_b2, int device,
+                                hipStream_t stream);
+
 }  // namespace gf

@@ -20,6 +20,7 @@ import torch.nn.functional as F
 
 from .. import ops
 from ..nn import EdgePredictor, FixedTimeEncode, NeighborCooccurrenceEncoder, TimeEncode
+from ..ops.feed_forward import _fused_route
 
 
 class EncoderBlock(nn.Module):
@@ -36,13 +37,16 @@ class EncoderBlock(nn.Module):
     x + drop(ops.feed_forward(ff_norm(x), w1.weight, w1.bias, w2.weight, w2.bias, p, seed)), with
     p = drop.p in training and 0 otherwise and a seed drawn the same way: the inner dropout is
     inside the kernel and the [n, S, 4 C] hidden tensors are never stored; LayerNorm, the outer
-    dropout and the residual stay in torch."""
+    dropout and the residual stay in torch.  fused_feed_forward="bfloat16" is that route with
+    compute_dtype=torch.bfloat16 (the products on the bfloat16 matrix instruction, float32
+    tensors in and out); it is taken inside a bfloat16 autocast region as well, where ff_norm(x)
+    is float32 already, while True falls back to torch there.  Any other value: ValueError."""
 
     def __init__(self, dim: int, num_heads: int, dropout: float, fused_attention: bool = False,
-                 fused_feed_forward: bool = False):
+                 fused_feed_forward=False):
         super().__init__()
         self.fused_attention = bool(fused_attention)
-        self.fused_feed_forward = bool(fused_feed_forward)
+        self.fused_feed_forward, self._ff_dtype = _fused_route(fused_feed_forward)
         if self.fused_feed_forward and dim > ops.FEED_FORWARD_MAX_WIDTH:
             raise ValueError("fused_feed_forward takes a dim of up to {}, got {}".format(
                 ops.FEED_FORWARD_MAX_WIDTH, dim))
@@ -62,7 +66,8 @@ class EncoderBlock(nn.Module):
 
     def forward(self, x):
         h = self.att_norm(x)
-        fusable = x.is_cuda and x.dtype == torch.float32 and not torch.is_autocast_enabled()
+        on_gpu = x.is_cuda and x.dtype == torch.float32
+        fusable = on_gpu and not torch.is_autocast_enabled()
         if self.fused_attention and fusable:
             att = self.att
             p = att.dropout if self.training else 0.0
@@ -72,11 +77,11 @@ class EncoderBlock(nn.Module):
         else:
             a = self.att(h, h, h, need_weights=False)[0]
         x = x + self.drop(a)
-        if self.fused_feed_forward and fusable:
+        if self.fused_feed_forward and (fusable or on_gpu and self._ff_dtype == torch.bfloat16):
             p = self.drop.p if self.training else 0.0
             return x + self.drop(ops.feed_forward(
                 self.ff_norm(x).contiguous(), self.w1.weight, self.w1.bias, self.w2.weight,
-                self.w2.bias, p, self._seed(p)))
+                self.w2.bias, p, self._seed(p), compute_dtype=self._ff_dtype))
         return x + self.drop(self.w2(self.drop(F.gelu(self.w1(self.ff_norm(x))))))
 
 
@@ -121,13 +126,15 @@ class DyGFormer(nn.Module):
     fused_feed_forward=True (off by default; README "feed_forward" has the measurements) makes
     every EncoderBlock take its feed-forward from ops.feed_forward on a GPU, with the inner
     dropout inside the kernel and no [N, S, 4 C] tensor stored.  A route as well.
+    fused_feed_forward="bfloat16" runs that kernel's products on the bfloat16 matrix instruction
+    (ops.feed_forward's compute_dtype), under bfloat16 autocast too; see EncoderBlock.
     """
 
     def __init__(self, dim_node: int, dim_edge: int, dim_time: int = 100, channel_dim: int = 50,
                  patch_size: int = 1, num_layers: int = 2, num_heads: int = 2,
                  dropout: float = 0.1, max_length: int = 32, dim_embed: int = 100,
                  learn_time: bool = False, fused_patches: bool = False,
-                 fused_attention: bool = False, fused_feed_forward: bool = False):
+                 fused_attention: bool = False, fused_feed_forward=False):
         super().__init__()
         for name, value, lo in (("dim_node", dim_node, 0), ("dim_edge", dim_edge, 0),
                                 ("dim_time", dim_time, 1), ("channel_dim", channel_dim, 1),
@@ -170,7 +177,7 @@ class DyGFormer(nn.Module):
                 "columns; got 2 * max_length / patch_size = {} and dim / num_heads = {}".format(
                     ops.SEQ_ATTENTION_MAX_LENGTH, ops.SEQ_ATTENTION_MAX_HEAD_DIM,
                     2 * max_length // patch_size, dim // num_heads))
-        self.fused_feed_forward = bool(fused_feed_forward)
+        self.fused_feed_forward = _fused_route(fused_feed_forward)[0]
         if self.fused_feed_forward and dim > ops.FEED_FORWARD_MAX_WIDTH:
             raise ValueError(
                 "fused_feed_forward takes up to {} columns; got {} channels of channel_dim "

@@ -14,6 +14,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..nn import EdgePredictor, FixedTimeEncode
+from ..ops.feed_forward import _fused_route
 
 
 class _FeedForward(nn.Module):
@@ -22,12 +23,15 @@ class _FeedForward(nn.Module):
     fused=True (a route, not state: the same parameters and state_dict keys) takes everything but
     the trailing dropout of a float32 x on a GPU, outside autocast, from ops.feed_forward: the
     inner Dropout's p in training and 0 otherwise, the seed drawn per forward from torch's
-    default CPU generator (no device sync).  Any other x takes the torch route."""
+    default CPU generator (no device sync).  Any other x takes the torch route.
+    fused="bfloat16" is that route with compute_dtype=torch.bfloat16, taken inside a bfloat16
+    autocast region too (the LayerNorm output it is given there is float32); any other value of
+    the flag raises ValueError."""
 
-    def __init__(self, dim: int, expansion: float, dropout: float, fused: bool = False):
+    def __init__(self, dim: int, expansion: float, dropout: float, fused=False):
         super().__init__()
         hidden = max(1, int(expansion * dim))
-        self.fused = bool(fused)
+        self.fused, self._dtype = _fused_route(fused)
         if self.fused and dim > ops.FEED_FORWARD_MAX_WIDTH:
             raise ValueError("fused_feed_forward takes a width of up to {}, got {}".format(
                 ops.FEED_FORWARD_MAX_WIDTH, dim))
@@ -36,19 +40,20 @@ class _FeedForward(nn.Module):
 
     def forward(self, x):
         if self.fused and x.is_cuda and x.dtype == torch.float32 and \
-                not torch.is_autocast_enabled():
+                (self._dtype == torch.bfloat16 or not torch.is_autocast_enabled()):
             w1, _, drop, w2, last = self.net
             p = drop.p if self.training else 0.0
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64)) if p > 0 else None
             return last(ops.feed_forward(x.contiguous(), w1.weight, w1.bias, w2.weight, w2.bias,
-                                         p, seed))
+                                         p, seed, compute_dtype=self._dtype))
         return self.net(x)
 
 
 class MixerBlock(nn.Module):
     """One MLP-Mixer block over x [n, K, C]: x + token MLP over K of LayerNorm(x), then
     x + channel MLP over C of LayerNorm(x).  fused_feed_forward=True routes the channel MLP
-    through ops.feed_forward.  fused_token_mix=True (a route too, independent of the other: the
+    through ops.feed_forward, "bfloat16" through its bfloat16 kernels.
+    fused_token_mix=True (a route too, independent of the other: the
     same parameters and state_dict keys) takes the whole first line -- token_norm, the token MLP
     over the K tokens with its hidden width of K / 2, both dropouts and the residual -- of a
     float32 x on a GPU, outside autocast, from ops.token_mix, without the transposed [n, C, K]
@@ -57,7 +62,7 @@ class MixerBlock(nn.Module):
     flags a block is two native calls and one LayerNorm."""
 
     def __init__(self, num_tokens: int, dim: int, token_expansion: float,
-                 channel_expansion: float, dropout: float, fused_feed_forward: bool = False,
+                 channel_expansion: float, dropout: float, fused_feed_forward=False,
                  fused_token_mix: bool = False):
         super().__init__()
         self.fused_token_mix = bool(fused_token_mix)
@@ -108,7 +113,9 @@ class GraphMixer(nn.Module):
     fused_feed_forward=True (off by default; README "feed_forward" has the measurements) takes
     every mixer block's channel MLP from ops.feed_forward on a GPU, the [n, K, 4 C] hidden
     tensors never stored.  A route, not state: the parameters and the state_dict are the same.
-    dim_embed may then be at most ops.FEED_FORWARD_MAX_WIDTH.
+    dim_embed may then be at most ops.FEED_FORWARD_MAX_WIDTH.  fused_feed_forward="bfloat16" runs
+    that kernel's products on the bfloat16 matrix instruction (ops.feed_forward's compute_dtype),
+    under bfloat16 autocast too, where True falls back to torch.
 
     fused_token_mix=True (off by default, independent of the other flag; README "token_mix" has
     the measurements) takes every mixer block's token half -- LayerNorm, the MLP over the K
@@ -120,9 +127,9 @@ class GraphMixer(nn.Module):
     def __init__(self, dim_node: int, dim_edge: int, dim_time: int = 100, dim_embed: int = 100,
                  num_tokens: int = 32, num_layers: int = 2, token_expansion: float = 0.5,
                  channel_expansion: float = 4.0, dropout: float = 0.1,
-                 fused_feed_forward: bool = False, fused_token_mix: bool = False):
+                 fused_feed_forward=False, fused_token_mix: bool = False):
         super().__init__()
-        self.fused_feed_forward = bool(fused_feed_forward)
+        self.fused_feed_forward = _fused_route(fused_feed_forward)[0]
         self.fused_token_mix = bool(fused_token_mix)
         self.dim_node, self.dim_edge, self.dim_time = dim_node, dim_edge, dim_time
         self.dim_embed, self.num_tokens, self.num_layers = dim_embed, num_tokens, num_layers

@@ -57,7 +57,8 @@ make on a sampled block, on HIP segment kernels (csrc/block_ops.hip) with autogr
                                            the float32 matrix instructions per pass, the [M, Hd] hidden
                                            activation and its Philox dropout mask never stored, u
                                            recomputed in the backward (csrc/feed_forward.hip); float32
-                                           only, C <= 256
+      ... compute_dtype=                   only, C <= 256; torch.bfloat16 runs the products on the
+                                           bfloat16 matrix instruction (csrc/feed_forward_bf16.hip)
     token_mix(x, gamma, beta, w1, b1,      x + token_mlp(token_norm(x).transpose(1, 2)).transpose(1, 2),
       w2, b2)                              the token half of GraphMixer's MixerBlock, on x [N, K, C] as
       ... dropout_p=, dropout_seed=        it lies: LayerNorm over C, two GEMMs over the token axis on the
@@ -78,6 +79,9 @@ source rows of block_reduce and block_max, feat of block_gat.  What autocast lea
 float32 only: edge weights (a softmax output), el and er (a float32 sum), and edge_softmax
 altogether.  A gradient of a source may meet several edges (an explicit col): it is summed in a
 float32 scratch and rounded once, never once per edge.
+feed_forward(..., compute_dtype=torch.bfloat16) is the one op whose ARITHMETIC is bfloat16 and not
+only its storage: its tensors stay float32, its matrix operands are rounded to bfloat16 inside the
+kernels (csrc/feed_forward_bf16.hip, v_mfma_f32_16x16x32_bf16) and its sums are float32.
 
 A block's edges are grouped by destination (the sampler emits them that way); blocks built by
 hand with unordered edges are handled through a stable permutation.

@@ -1162,6 +1162,40 @@ GF_API int gf_feed_forward_backward(const float* d_x, const float* d_w1, const f
                                     float* d_grad_b1, float* d_grad_w2, float* d_grad_b2,
                                     int device, void* stream);
 
+/* gf_feed_forward with both products of every pass on the bfloat16 matrix instruction
+ * (v_mfma_f32_16x16x32_bf16).  Every tensor is fp32 in memory, as above; the reduced precision is
+ * inside the kernels only.  With bf(v) = v rounded to the nearest bfloat16 (ties to even) and
+ * every sum accumulated in fp32:
+ *   u[m,j] = b1[j] + sum_c bf(x)[m,c] * bf(w1)[j,c]                      fp32, never rounded
+ *   h[m,j] = bf(0.5 * u * (1 + erff(u / sqrt 2)) * w[m,j])               w: gf_feed_forward's
+ *   y[m,c] = b2[c] + sum_j h[m,j] * bf(w2)[c,j]
+ *   dh = bf(dy) bf(w2)    du = bf(dh * w * g'(u))    grad_x = du bf(w1)    grad_w1 = du^T bf(x)
+ *   grad_w2 = bf(dy)^T h  grad_b1 = colsum du        grad_b2 = colsum bf(dy)
+ * (grad_b1 and grad_b2 sum the values after rounding).  bf(w1) and bf(w2) are packed once per call
+ * into the caller-owned d_workspace by a small launch that precedes the pass; the workspace must
+ * be 16-byte aligned and hold gf_feed_forward_bf16_workspace() bytes (backward = 0 for
+ * gf_feed_forward_bf16: 2 arrays of 2 * round64(hidden) * round64(width) bytes; nonzero for
+ * gf_feed_forward_bf16_backward: 3 arrays).  Limits, checks, launches besides the pack, the
+ * partials buffer (its own row query, the same row size), NULL outputs, determinism and the
+ * p == 0 rule are gf_feed_forward's and gf_feed_forward_backward's. */
+GF_API int gf_feed_forward_bf16_workspace(size_t width, size_t hidden, int backward,
+                                          size_t* bytes);
+GF_API int gf_feed_forward_bf16(const float* d_x, const float* d_w1, const float* d_b1,
+                                const float* d_w2, const float* d_b2, size_t num_rows,
+                                size_t width, size_t hidden, float p, uint64_t seed,
+                                void* d_workspace, size_t workspace_bytes, float* d_y, int device,
+                                void* stream);
+GF_API int gf_feed_forward_bf16_backward_partial_rows(size_t num_rows, size_t width,
+                                                      size_t hidden, size_t* rows);
+GF_API int gf_feed_forward_bf16_backward(const float* d_x, const float* d_w1, const float* d_b1,
+                                         const float* d_w2, size_t num_rows, size_t width,
+                                         size_t hidden, float p, uint64_t seed,
+                                         const float* d_grad_y, void* d_workspace,
+                                         size_t workspace_bytes, float* d_partials,
+                                         size_t partial_rows, float* d_grad_x, float* d_grad_w1,
+                                         float* d_grad_b1, float* d_grad_w2, float* d_grad_b2,
+                                         int device, void* stream);
+
 /* The token-mixing half of GraphMixer's MixerBlock, x + token_mlp(LayerNorm(x)^T)^T, in one
  * launch with no transposed copy.  d_x and d_y fp32 [num_rows, tokens, width], d_gamma and d_beta
  * [width], d_w1 [hidden, tokens], d_b1 [hidden], d_w2 [tokens, hidden], d_b2 [tokens], d_mean and

@@ -21,6 +21,16 @@ to profiles/feed_forward_bench.jsonl: the median round in microseconds per call,
 each route's peak allocated memory over one call above what was held before it, how torch
 compares with fused, and whether the difference exceeds the rounds' spread.  Host wall time only:
 the kernels alone are not measured here.
+
+    python scripts/feed_forward_bench.py --bf16 [--kinds ff mixer]
+
+measures fused_feed_forward="bfloat16" instead, on the ff and mixer lines and by the same protocol,
+four routes alternating inside every round: `bf16` (the flag, outside autocast) against `fused`
+(fused_feed_forward=True, the float32 kernels of the same build), and `bf16_autocast` (the flag
+inside torch.autocast("cuda", dtype=torch.bfloat16)) against `torch_autocast` (the plain block
+inside the same region).  In eval() the bf16 route's output is asserted to agree with the float32
+fused route's to 2e-2 of the largest output.  One JSON line per case with "bench":
+"feed_forward_bf16": every route's median, min-max and peak, and the two ratios.
 """
 import argparse
 import json
@@ -41,6 +51,8 @@ def main():
     ap.add_argument("--dropout", type=float, default=0.1)
     ap.add_argument("--calls", type=int, default=10, help="calls per round")
     ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--bf16", action="store_true",
+                    help='measure fused_feed_forward="bfloat16" against its two yardsticks')
     ap.add_argument("--label", default="", help="a name for this run, for the record")
     ap.add_argument("--measured-by", default="", help="who ran this, for the record")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "feed_forward_bench.jsonl"))
@@ -54,8 +66,19 @@ def main():
 
     dev = torch.device("cuda", 0)
 
-    def blocks(kind):
+    def make(kind, flag):
+        if kind == "mixer":
+            return MixerBlock(32, 100, 0.5, 4.0, a.dropout, fused_feed_forward=flag)
+        return EncoderBlock(200, 2, a.dropout, fused_feed_forward=flag)
+
+    def blocks(kind):      # route -> (block, inside bfloat16 autocast?)
         torch.manual_seed(0)
+        if a.bf16:
+            plain, fused, bf16 = (make(kind, flag).to(dev) for flag in (False, True, "bfloat16"))
+            fused.load_state_dict(plain.state_dict())
+            bf16.load_state_dict(plain.state_dict())
+            return {"bf16": (bf16, False), "fused": (fused, False),
+                    "bf16_autocast": (bf16, True), "torch_autocast": (plain, True)}
         if kind == "mixer":
             pair = [MixerBlock(32, 100, 0.5, 4.0, a.dropout, fused_feed_forward=f)
                     for f in (False, True)]
@@ -64,9 +87,43 @@ def main():
                     EncoderBlock(200, 2, a.dropout, fused_attention=kind == "ff+att",
                                  fused_feed_forward=True)]
         pair[1].load_state_dict(pair[0].state_dict())
-        return {"torch": pair[0].to(dev), "fused": pair[1].to(dev)}
+        return {"torch": (pair[0].to(dev), False), "fused": (pair[1].to(dev), False)}
+
+    def record(out):
+        line = json.dumps(out)
+        print(line, flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(line + "\n")
+
+    def bf16_lines(out, routes, mode, peak, timed):
+        outs, peaks = {}, {}
+        for name, route in routes.items():
+            outs[name], peaks[name] = peak(route, keep=mode == "eval")
+        if mode == "eval":      # bfloat16 operands against the float32 kernels
+            assert (outs["bf16"] - outs["fused"]).abs().max() <= 2e-2 * outs["fused"].abs().max()
+        outs.clear()
+        for route in routes.values():
+            timed(route)
+        rounds = {name: [] for name in routes}
+        for _ in range(a.rounds):
+            for name, route in routes.items():
+                rounds[name].append(timed(route))
+        med = {name: float(np.median(r)) * 1e6 for name, r in rounds.items()}
+        spread = {name: (max(r) - min(r)) * 1e6 for name, r in rounds.items()}
+        for name, r in rounds.items():
+            out[name + "_us_per_call_median"] = round(med[name], 1)
+            out[name + "_us_per_call_min_max"] = [round(min(r) * 1e6, 1), round(max(r) * 1e6, 1)]
+            out[name + "_peak_gb"] = round(peaks[name] / 2 ** 30, 3)
+        for ours, other in (("bf16", "fused"), ("bf16_autocast", "torch_autocast")):
+            out[other + "_over_" + ours] = round(med[other] / med[ours], 2)
+            out[other + "_difference_exceeds_spread"] = bool(
+                abs(med[other] - med[ours]) > max(spread[other], spread[ours]))
+        record(out)
 
     for kind in a.kinds:
+        if a.bf16 and kind == "ff+att":
+            continue
         routes = blocks(kind)
         shapes = [(N, 32, 100) for N in a.rows] if kind == "mixer" else \
             [(N, S, 200) for N in a.rows for S in a.length]
@@ -74,8 +131,10 @@ def main():
             x = torch.randn(shape, device=dev, requires_grad=True)
             dout = torch.randn(shape, device=dev)
 
-            def call(block, keep=False):
-                out = block(x)
+            def call(route, keep=False):
+                block, cast = route
+                with torch.autocast("cuda", dtype=torch.bfloat16, enabled=cast):
+                    out = block(x)
                 out.backward(dout)
                 x.grad = None
                 block.zero_grad(set_to_none=True)
@@ -98,9 +157,10 @@ def main():
                 return got, torch.cuda.max_memory_allocated() - held
 
             for mode in ("eval", "train"):
-                for block in routes.values():
+                for block, _ in routes.values():
                     block.train(mode == "train")
-                out = {"bench": "feed_forward", "kind": kind, "label": a.label,
+                out = {"bench": "feed_forward_bf16" if a.bf16 else "feed_forward", "kind": kind,
+                       "label": a.label,
                        "shape": list(shape), "mode": mode,
                        "dropout": a.dropout if mode == "train" else 0.0,
                        "calls_per_round": a.calls, "rounds": a.rounds,
@@ -109,6 +169,9 @@ def main():
                                "calls; the routes alternate inside every round; peak memory is "
                                "one call's, above what was held",
                        "measured_by": a.measured_by, "device": torch.cuda.get_device_name(0)}
+                if a.bf16:
+                    bf16_lines(out, routes, mode, peak, timed)
+                    continue
                 fused_out, fused_peak = peak(routes["fused"], keep=mode == "eval")
                 torch_out, torch_peak = peak(routes["torch"], keep=mode == "eval")
                 if mode == "eval":      # the two routes agree
@@ -133,11 +196,7 @@ def main():
                             "torch_over_fused": round(t_us / f_us, 2),
                             "difference_exceeds_spread": bool(
                                 abs(t_us - f_us) > max(t_spread, f_spread))})
-                line = json.dumps(out)
-                print(line, flush=True)
-                os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-                with open(a.out, "a") as f:
-                    f.write(line + "\n")
+                record(out)
             del x, dout
             torch.cuda.empty_cache()
 
